@@ -11,6 +11,10 @@ the 8x8 image tiles are dealt round-robin to the ranks (one process per GPU, no 
 rendering) and the step ends with ONE RCCL reduce of the float framebuffer to rank 0 over xGMI;
 the total work is fixed, so the scaling is "strong".  value = Msamples/s of the whole job.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (with the per-kernel times and counters of those
+steps).  --full adds what takes runs of its own: the traversal-counting pass and the roofline, the CPU baselines and the
+matched-seed parity check.  --dump-outputs DIR writes the frame of the last timed step to DIR/framebuffer.npy (float32).
 """
 import argparse
 import json
@@ -76,14 +80,39 @@ def parse():
     ap.add_argument("--instanced", action="store_true",
                     help="grid10m as BASELINE configs[4] words it, an INSTANCED mesh: one 8 192-triangle patch placed 1 250 times (two-level traversal)")
     ap.add_argument("--stripes", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the traversal-counting pass and roofline, the CPU baselines and the parity check (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step as DIR/framebuffer.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: no matched-seed parity check")
     ap.add_argument("--tree", default="auto", choices=["auto", "host", "device"],
                     help="accelerator build: host binned SAH, device LBVH (SLRHIP_FLAG_BVH_DEVICE_BUILD), auto = device from 2^20 triangles on")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="per-kernel HBM traffic from separate rocprofv3 --pmc passes of this same command (tools/pmc_traffic.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64000000
+
+
+def dump_outputs(path, fb):
+    """The frame the last timed step resolved (what slrhip_resolve_framebuffer hands its caller), float32, H x W x components.
+    A frame over DUMP_BYTES is written as a fixed sample of its pixels (seed 0): framebuffer_sample.npy and the pixel indices
+    (row-major, as float64) in framebuffer_sample_pixels.npy."""
+    os.makedirs(path, exist_ok=True)
+    frame = fb.cpu().numpy()
+    if frame.nbytes + 4096 <= DUMP_BYTES:
+        np.save(os.path.join(path, "framebuffer.npy"), frame)
+        return
+    pixels = frame.reshape(-1, frame.shape[-1])
+    n = (DUMP_BYTES - 4096) // (pixels.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(len(pixels), n, replace=False))
+    np.save(os.path.join(path, "framebuffer_sample.npy"), pixels[idx])
+    np.save(os.path.join(path, "framebuffer_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def traffic_entry(args, W, H, spp):
@@ -196,6 +225,8 @@ def main():
     elapsed = time.perf_counter() - t0
     prof1 = ctx.profile()
     counters = ctx.counters()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fb)
     rank_ms = [sum(shard_ms) / max(len(shard_ms), 1)]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
@@ -239,6 +270,7 @@ def main():
                 kernels[name] = {"launches": int(n), "ms_total": round(ms, 3), "avg_us": round(ms / n * 1e3, 3) if n else None}
             if kernels.get("tail", {}).get("launches") == 0:
                 kernels.pop("tail")       # listed only when it ran (SLRHIP_TAIL_SLOTS=0 turns it off)
+        if args.full and not args.no_kernel_timing:
             # traversal statistics from an instrumented, untimed pass on this rank's shard
             cctx = Context(device=local_rank, mode=mode, stripes=args.stripes, flags=abi.FLAG_COUNT_TRAVERSAL | build_flag)
             cctx.upload_scene(scene)
@@ -344,16 +376,18 @@ def main():
                 tot_s = sum(kernels[k]["ms_total"] / max(kernels[k]["launches"], 1) for k in it_kernels) * 1e-3
                 roof["iteration_traffic_bytes"] = round(tot_b)
                 roof["iteration_frac"] = round(tot_b / tot_s / 1e9 / HBM_PEAK_GBS, 5)
-        out["roofline"] = roof
+        if args.full:
+            out["roofline"] = roof
         out["kernels"] = kernels
         out["counters"] = {"samples": int(counters.samples), "extension_rays": int(counters.extension_rays),
                            "shadow_rays": int(counters.shadow_rays), "iterations": int(counters.iterations),
                            "bvh_nodes": int(counters.bvh_nodes), "bvh_depth": int(counters.bvh_depth),
                            "build_seconds": round(counters.build_seconds, 4)}
 
-        # ---- CPU baseline and matched-seed parity (N = 1 only; the checker, never the thing measured) ---
-        out["cpu_baseline"] = None
-        if world == 1 and args.cpu_seconds > 0:
+        # ---- CPU baseline and matched-seed parity (--full, N = 1 only; the checker, never the thing measured) ---
+        if args.full:
+            out["cpu_baseline"] = None
+        if args.full and world == 1 and args.cpu_seconds > 0:
             guard = quiet_stdout()
             guard.__enter__()
             from oracle import binding as ob

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/bench_counts.sh [bench.py args] — one line: throughput, kernel averages, nodes / triangles per ray, tree size and build time
-python3 bench.py --cpu-seconds 0 --no-parity "$@" 2>/dev/null | python3 -c "
+python3 bench.py --full --cpu-seconds 0 --no-parity "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']; r=d['roofline']['per_ray']; c=d['counters']

@@ -9,7 +9,7 @@
 # profiled (round 2's passes also profiled 32 small launches of the 16-spp counting render, which diluted the per-launch bytes).
 tag=$1; quick=$2; repo=$PWD; out=$repo/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $repo/bench.py --cpu-seconds 0 > $out/bench_under_rocprof.json 2> $out/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $repo/bench.py --full --cpu-seconds 0 > $out/bench_under_rocprof.json 2> $out/stats.err
 find $out/stats -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; ; rm -rf $out/stats
 echo "stats done" >&2
 echo "{}" > $out/pmc_traffic.json
