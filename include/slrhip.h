@@ -433,6 +433,52 @@ int slrhip_get_profile(slrhip_ctx* ctx, slrhip_profile* out);
  * (Intersection::dist, ::u, ::v; TriangleMesh.cpp:169-173).  Host arrays; synchronises.        */
 int slrhip_trace_rays(slrhip_ctx* ctx, const float* rays, uint32_t n, float* hits);
 
+/* ---- ray queries on device memory ------------------------------------------------------------------------------------
+ * The render's own traversal (the wave-specialised kernel of every frame, on whatever tree the upload built: float, quantized,
+ * instanced, LBVH, spatial splits; alpha-cut triangles tested as the render tests them) over a caller's array of rays.
+ *
+ * Pointers: ALL are DEVICE pointers.  rays: 16-byte aligned; hits: 16-byte aligned; instances / visible: 4-byte aligned.
+ * The call is ordered on `stream` (a hipStream_t; NULL = the null stream): it reads `rays` and writes the results after the
+ * work the caller queued there before, and returns at once.  It allocates nothing, copies nothing between host and device and
+ * does not synchronise, so it may be captured in a graph (hipStreamBeginCapture, torch.cuda.graph).  The results must not
+ * overlap `rays` or each other.
+ * Errors: bad arguments return SLRHIP_ERR_INVALID_ARGUMENT at the call (null context, a null or misaligned pointer with
+ * n > 0, n >= 2^31); SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.  n == 0 does nothing.  A traversal that gives up on a
+ * ray (a traversal stack overflow, a bounded wait that ran out: never expected) sets a bit in the context's QUERY error word,
+ * which each call clears on its stream before it traces; slrhip_query_status reads it.  A call whose status is not 0 has no
+ * trustworthy result.
+ * Independence: a query touches neither the render's path state nor its counters nor its error word; a query between two
+ * slrhip_render calls leaves the frame bit-identical.  slrhip_upload_scene and slrhip_destroy must not run while a query of
+ * the context is in flight (synchronise its stream first), and two queries of one context in flight at the same time on
+ * different streams share the query error word.                                                                          */
+typedef struct slrhip_ray {
+    float org[3];
+    float dist_min;
+    float dir[3];              /* not normalised by the library: dist is measured in units of |dir| (as slrhip_trace_rays) */
+    float dist_max;
+} slrhip_ray;                  /* 32 bytes */
+
+typedef struct slrhip_hit {
+    uint32_t triangle;         /* index into slrhip_scene_desc::triangles (the mesh-local one for an instanced hit); 0xFFFFFFFF = miss */
+    float dist;                /* Intersection::dist (INFINITY on a miss) */
+    float b0, b1;              /* Intersection::u, ::v (u = 1 - b1 - b2 of Moller-Trumbore, TriangleMesh.cpp:159,172-173); 0 on a miss */
+} slrhip_hit;                  /* 16 bytes: the record of slrhip_trace_rays */
+
+/* Closest hit: the aggregate part of Scene::intersect (SurfaceObject.cpp:267-269, 408-416); the same hits as slrhip_trace_rays
+ * (equal-distance ties: the larger (instance, triangle) pair wins).  instances (may be NULL): index into
+ * slrhip_scene_desc::instances of the placement that was hit, -1 for a loose triangle or a miss.  The environment sphere is
+ * never hit.  Replaces slrhip_trace_rays for callers that hold their rays on the device.                                  */
+int slrhip_intersect_rays(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, slrhip_hit* hits, int32_t* instances, void* stream);
+
+/* Visibility: the aggregate part of Scene::testVisibility (SurfaceObject.cpp:418-430): visible[i] = 1 if no triangle is hit
+ * in [dist_min, dist_max], else 0 (any hit ends the ray).  The environment sphere never occludes.                        */
+int slrhip_test_visibility(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, uint32_t* visible, void* stream);
+
+/* The query error word (ERR bits: 1 ring space, 2 ring release, 4 consumer idle, 8 stack overflow; 0 = every ray of the last
+ * query call was traced), read in order on `stream` — pass the queries' stream — and written to HOST memory *bits.  Waits for
+ * that stream only, not for the device.                                                                                  */
+int slrhip_query_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
+
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
 

@@ -32,6 +32,13 @@ texture_dtype = np.dtype([("kind", "<u4"), ("offset", "<f4", 2), ("scale", "<f4"
                           ("reserved", "<u4", 3)])
 instance_dtype = np.dtype([("first_triangle", "<u4"), ("num_triangles", "<u4"), ("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16)])
 TEX_CHECKER_SPECTRUM, TEX_CHECKER_FLOAT, TEX_CHECKER_NORMAL, TEX_IMAGE_SPECTRUM = 0, 1, 2, 3
+# ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): one [n, 8] float32 row per slrhip_ray, one [n, 4]
+# row per slrhip_hit (column 0 holds the triangle index's bits)
+ray_dtype = np.dtype([("org", "<f4", 3), ("dist_min", "<f4"), ("dir", "<f4", 3), ("dist_max", "<f4")])
+hit_dtype = np.dtype([("triangle", "<u4"), ("dist", "<f4"), ("b0", "<f4"), ("b1", "<f4")])
+MISS = 0xFFFFFFFF
+# bits of the query error word (slrhip_query_status)
+QUERY_ERR_RING_SPACE, QUERY_ERR_RING_RELEASE, QUERY_ERR_CONSUMER_IDLE, QUERY_ERR_STACK_OVERFLOW = 1, 2, 4, 8
 
 
 def texture_ref(t):
@@ -44,6 +51,14 @@ class Camera(C.Structure):
                 ("aspect", C.c_float), ("fov_y", C.c_float), ("lens_radius", C.c_float),
                 ("img_plane_distance", C.c_float), ("obj_plane_distance", C.c_float),
                 ("sensitivity", C.c_float)]
+
+
+class Ray(C.Structure):
+    _fields_ = [("org", C.c_float * 3), ("dist_min", C.c_float), ("dir", C.c_float * 3), ("dist_max", C.c_float)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("triangle", C.c_uint32), ("dist", C.c_float), ("b0", C.c_float), ("b1", C.c_float)]
 
 
 class EnvMap(C.Structure):

@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(CSRC, "libslrhip.so")
 
 EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_render_begin", "slrhip_render",
            "slrhip_resolve_framebuffer", "slrhip_reduce_framebuffer", "slrhip_read_framebuffer", "slrhip_synchronize", "slrhip_get_counters",
-           "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_intersect_rays", "slrhip_test_visibility",
+           "slrhip_query_status", "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -53,6 +54,9 @@ def load_library():
     lib.slrhip_components.argtypes = [C.c_void_p]
     lib.slrhip_get_profile.argtypes = [C.c_void_p, C.POINTER(abi.Profile)]
     lib.slrhip_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.slrhip_intersect_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.slrhip_test_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.slrhip_query_status.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -66,6 +70,28 @@ def load_library():
     return lib
 
 
+_hip = None
+
+
+def _hip_runtime():
+    """The HIP runtime libslrhip.so is bound to: the first copy loaded under its soname (torch's own copy, if torch was imported
+    before the library; else the system's)."""
+    global _hip
+    if _hip is None:
+        load_library()
+        h = C.CDLL("libamdhip64.so.7")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipFree.argtypes = [C.c_void_p]
+        _hip = h
+    return _hip
+
+
+def _hip_check(rc, what):
+    if rc != 0:
+        raise SlrHipError("%s failed (%d)" % (what, rc))
+
+
 def _check(lib, rc, what):
     if rc != 0:
         raise SlrHipError("%s failed (%d): %s" % (what, rc, lib.slrhip_last_error_string().decode()))
@@ -76,6 +102,7 @@ class Context:
 
     def __init__(self, device=0, mode=abi.MODE_RGB, stripes=0, flags=0):
         self.lib = load_library()
+        self.device = device
         self.handle = C.c_void_p()
         cfg = abi.Config(device, mode, stripes, flags)
         _check(self.lib, self.lib.slrhip_create(C.byref(cfg), C.byref(self.handle)), "slrhip_create")
@@ -133,6 +160,83 @@ class Context:
         hits = np.zeros((n, 4), np.float32)
         _check(self.lib, self.lib.slrhip_trace_rays(self.handle, rays.ctypes.data, n, hits.ctypes.data), "slrhip_trace_rays")
         return hits[:, 0].copy().view(np.uint32), hits[:, 1], hits[:, 2], hits[:, 3]
+
+    # ---- ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility) ----------------------------------
+    # torch ships its own copy of the HIP runtime, and only one copy can open the device in a process.  libslrhip.so binds to
+    # torch's copy when torch is imported before the library is loaded (bench.py's order); then torch tensors and streams are
+    # passed straight through.  Numpy inputs go through the runtime the library itself is bound to, whichever copy that is.
+    def _query(self, rays, stream, outs, call):
+        """outs: [(name, shape, numpy dtype)]; call(rays_ptr, n, {name: ptr}, stream_handle)."""
+        if isinstance(rays, np.ndarray):
+            return self._query_host(rays, outs, call)
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
+                and rays.is_contiguous()):
+            raise ValueError("rays: a contiguous [n, 8] float32 CUDA tensor (or a numpy array) expected")
+        if not torch.cuda.is_available() or rays.device.index != self.device:
+            raise SlrHipError("ray queries on torch tensors need libslrhip.so bound to torch's HIP runtime on the tensor's device: "
+                              "import torch before the first Context, and pass tensors on device %d" % self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            res = {name: torch.empty(shape(rays.shape[0]), dtype=getattr(torch, np.dtype(dt).name), device=rays.device) for name, shape, dt in outs}
+            call(rays.data_ptr(), rays.shape[0], {k: v.data_ptr() for k, v in res.items()}, s.cuda_stream)
+        return tuple(res[name] for name, _, _ in outs) if len(outs) > 1 else res[outs[0][0]]
+
+    def _query_host(self, rays, outs, call):
+        a = rays.view(np.float32) if rays.dtype == abi.ray_dtype else rays
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
+        n = len(a)
+        hip = _hip_runtime()
+        host = {name: np.empty(shape(n), dt) for name, shape, dt in outs}
+        ptrs = {}
+        try:
+            for name, arr in [("rays", a)] + list(host.items()):
+                p = C.c_void_p()
+                _hip_check(hip.hipMalloc(C.byref(p), max(arr.nbytes, 16)), "hipMalloc")
+                ptrs[name] = p.value
+            _hip_check(hip.hipMemcpy(ptrs["rays"], a.ctypes.data, a.nbytes, 1), "hipMemcpy")
+            call(ptrs["rays"], n, {k: ptrs[k] for k in host}, None)
+            bits = self.query_status(0)
+            for k, arr in host.items():
+                _hip_check(hip.hipMemcpy(arr.ctypes.data, ptrs[k], arr.nbytes, 2), "hipMemcpy")
+        finally:
+            for p in ptrs.values():
+                hip.hipFree(p)
+        if bits:
+            raise SlrHipError("ray query: the query error word is 0x%x (a traversal gave up)" % bits)
+        return tuple(host[name] for name, _, _ in outs) if len(outs) > 1 else host[outs[0][0]]
+
+    def intersect_rays(self, rays, stream=None, want_instances=False):
+        """Closest hits (slrhip_intersect_rays).  rays: a torch CUDA tensor [n, 8] float32 (slrhip_ray rows: org, dist_min, dir,
+        dist_max), contiguous and 16-byte aligned, passed without a copy and queried in order on `stream` (default:
+        torch.cuda.current_stream()); returns device tensors at once: hits [n, 4] float32 = slrhip_hit rows (column 0 holds the
+        triangle index's bits, 0xFFFFFFFF = miss; dist; b0; b1) and, with want_instances, instances [n] int32 (-1: a loose triangle
+        or a miss).  Check query_status(stream) before trusting them.  A numpy array of the same rows (or of abi.ray_dtype records)
+        is COPIED to the device and the results back (numpy arrays); that call synchronises and raises if the query error word
+        is set."""
+        outs = [("hits", lambda n: (n, 4), np.float32)] + ([("instances", lambda n: (n,), np.int32)] if want_instances else [])
+
+        def call(r, n, p, handle):
+            _check(self.lib, self.lib.slrhip_intersect_rays(self.handle, r, n, p["hits"], p.get("instances"), handle), "slrhip_intersect_rays")
+        return self._query(rays, stream, outs, call)
+
+    def test_visibility(self, rays, stream=None):
+        """Visibility (slrhip_test_visibility): [n] int32, 1 = no triangle in [dist_min, dist_max].  Same conventions as
+        intersect_rays (device tensors in and out without a copy; numpy arrays copied both ways)."""
+        def call(r, n, p, handle):
+            _check(self.lib, self.lib.slrhip_test_visibility(self.handle, r, n, p["visible"], handle), "slrhip_test_visibility")
+        return self._query(rays, stream, [("visible", lambda n: (n,), np.int32)], call)
+
+    def query_status(self, stream=None):
+        """The query error word after the queries ordered on `stream` (a torch stream, a raw handle, 0 = the null stream; default:
+        torch.cuda.current_stream()); waits for that stream only."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        bits = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_query_status(self.handle, C.byref(bits), getattr(stream, "cuda_stream", stream) or None),
+               "slrhip_query_status")
+        return bits.value
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

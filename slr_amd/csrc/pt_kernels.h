@@ -255,5 +255,9 @@ void launchTraceBatch(const DevScene& sc, const float4* org, const float4* dir, 
 void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, uint32_t blocks, bool count,
                    hipStream_t stream);
 int traceWsBlocksPerCU(bool quantizedTree);
+// ray queries (slrhip_intersect_rays / slrhip_test_visibility) through the same consumer: rays = n slrhip_ray records (2 x float4);
+// visible == nullptr: closest hit into hits (slrhip_hit) and, if given, instances; else visibility into visible.  n < 2^31.
+void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,
+                   int numCUs, hipStream_t stream);
 
 } // namespace slrhip

@@ -161,14 +161,62 @@ struct WsCounts {
     uint32_t nodes[2] = {0, 0}, tris[2] = {0, 0};   // [0] closest, [1] shadow
 };
 
+// The render's slots: a ring entry names a slot of the path state, results go to its hit / hitInstance / visible records.
+struct WsRenderIO {
+    const PathBuffers& pb;
+    uint32_t* const& errorWord;
+    __device__ WsRenderIO(const PathBuffers& p) : pb(p), errorWord(p.errorWord) {}
+    __device__ __forceinline__ void worldRay(uint32_t slot, float4& o, float4& d) const {
+        const uint32_t s = slot & ~kShadowBit;
+        o = pb.rayOrg[(size_t)s * pb.rayStride];
+        d = (slot & kShadowBit) ? pb.shadowDir[s] : pb.rayDir[(size_t)s * pb.rayStride];
+    }
+    template <bool INST>
+    __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
+        if (slot & kShadowBit) pb.visible[slot & ~kShadowBit] = hitTri == 0xFFFFFFFFu ? 1u : 0u;      // testVisibility
+        else {
+            pb.hit[slot] = make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2);
+            if (INST) pb.hitInstance[slot] = hitInst;
+        }
+    }
+};
+
+// Ray queries (slrhip_intersect_rays / slrhip_test_visibility): a ring entry is an index into the caller's slrhip_ray array (bit 31:
+// a visibility query), results go to the caller's arrays in the public format.
+struct WsQueryIO {
+    const float4* rays;           // slrhip_ray: {org, dist_min}, {dir, dist_max}
+    float4* hits;                 // slrhip_hit: {triangle, dist, b0, b1}
+    int32_t* instances;           // or nullptr
+    uint32_t* visible;
+    uint32_t* errorWord;          // the context's query error word (not the render's)
+    __device__ __forceinline__ void worldRay(uint32_t slot, float4& o, float4& d) const {
+        const size_t s = slot & ~kShadowBit;
+        o = rays[2 * s];
+        d = rays[2 * s + 1];
+    }
+    template <bool INST>
+    __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
+        if (slot & kShadowBit) { visible[slot & ~kShadowBit] = hitTri == 0xFFFFFFFFu ? 1u : 0u; return; }
+        // Intersection::u = 1 - b1 - b2, ::v = b1 (TriangleMesh.cpp:159,172-173), in that float order; zeros on a miss as
+        // slrhip_trace_rays reports them
+        const bool miss = hitTri == 0xFFFFFFFFu;
+        const float b0 = 1.0f - hitB1 - hitB2;
+        hits[slot] = make_float4(__uint_as_float(hitTri), hitT, miss ? 0.0f : b0, miss ? 0.0f : hitB1);
+        if (instances) instances[slot] = hitInst;       // -1: a loose triangle or a miss (always -1 when the scene has no instance)
+    }
+};
+
 // INST: the scene has instanced meshes (DevScene::instances).  A child reference that names an instance (leaf flag, count 0) takes
 // the lane's ray to the mesh's local space — TransformedSurfaceObject::intersect, Core/SurfaceObject.cpp:307-317: origin as a point,
 // direction as a vector and NOT renormalised, so distances stay world distances and tmin / tmax carry over — pushes kPopInstance
 // and goes on at the root of the mesh's tree (same node and leaf arrays).  When kPopInstance comes off the stack the mesh is done
 // and the world ray comes back from six registers of its own (they fit under the 64-VGPR cap without more scratch; reading it
 // again from the slot's record — two 16-byte loads that miss the caches, the producer streamed them — was 8 % slower).
-template <bool COUNT, int NC, bool QUANT, bool WIDE8, bool INST>
-__device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers& pb, WsLds<NC>& lds, uint32_t refill, uint32_t numTop, WsCounts& cnt, WsDebug& dbg) {
+// IO: where the consumer sends its results and its error bits, and where a lane inside an instance gets its world ray back when
+// it does not keep it in registers (SLR_WS_INST_SAVE 0) — WsRenderIO (the slots of the path state) or WsQueryIO (a caller's ray
+// array, slrhip_intersect_rays / slrhip_test_visibility).  The rays themselves always come through the LDS ring.
+template <bool COUNT, int NC, bool QUANT, bool WIDE8, bool INST, class IO>
+__device__ __forceinline__ void wsConsume(const DevScene& sc, const IO& io, WsLds<NC>& lds, uint32_t refill, uint32_t numTop, WsCounts& cnt, WsDebug& dbg) {
     const uint64_t tStart = COUNT ? __builtin_readcyclecounter() : 0;
     constexpr uint32_t kRing = WsLds<NC>::kRing;
     const uint32_t lane = threadIdx.x & 63u;
@@ -243,14 +291,14 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                     uint32_t spin = 0;
                     for (; spin < kSpinLimit && WS_LOAD(&lds.released, __ATOMIC_ACQUIRE) != start; ++spin)
                         __builtin_amdgcn_s_sleep(1);
-                    if (spin == kSpinLimit) atomicOr(pb.errorWord, ERR_RING_RELEASE);     // never expected; the render fails loudly
+                    if (spin == kSpinLimit) atomicOr(io.errorWord, ERR_RING_RELEASE);     // never expected; the render fails loudly
                     WS_STORE(&lds.released, start + take, __ATOMIC_RELEASE);
                 }
             }
             else if (nIdle == 64) {
                 // nothing in flight and nothing to take: finished, or the producer is behind
                 if (WS_LOAD(&lds.done, __ATOMIC_ACQUIRE) && WS_LOAD(&lds.tail, __ATOMIC_ACQUIRE) == WS_LOAD(&lds.reserved, __ATOMIC_RELAXED)) break;
-                if (++idleSpins > kSpinLimit) { if (lane == 0) atomicOr(pb.errorWord, ERR_CONSUMER_IDLE); break; }
+                if (++idleSpins > kSpinLimit) { if (lane == 0) atomicOr(io.errorWord, ERR_CONSUMER_IDLE); break; }
                 if (COUNT) {
                     const uint64_t t0 = __builtin_readcyclecounter();
                     __builtin_amdgcn_s_sleep(4);
@@ -276,9 +324,8 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                 ox = wox; oy = woy; oz = woz;
                 dx = wdx; dy = wdy; dz = wdz;
 #else
-                const uint32_t s = slot & ~kShadowBit;
-                const float4 o = pb.rayOrg[(size_t)s * pb.rayStride];
-                const float4 d = (slot & kShadowBit) ? pb.shadowDir[s] : pb.rayDir[(size_t)s * pb.rayStride];
+                float4 o, d;
+                io.worldRay(slot, o, d);
                 ox = o.x; oy = o.y; oz = o.z;
                 dx = d.x; dy = d.y; dz = d.z;
 #endif
@@ -309,14 +356,13 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                 dx = mx; dy = my; dz = mz;
                 if (sp < kWsLdsStack) { stack[sp * 64] = kPopInstance; ++sp; }
                 else if (!kNoSpill && sp < kWsLdsStack + kWsSpill) { spill[sp - kWsLdsStack] = kPopInstance; ++sp; }
-                else atomicOr(pb.errorWord, ERR_STACK_OVERFLOW);
+                else atomicOr(io.errorWord, ERR_STACK_OVERFLOW);
                 cur = __float_as_uint(meta.x);
                 inst = (int32_t)k;
             }
             idx = 1.0f / dx; idy = 1.0f / dy; idz = 1.0f / dz;          // Vector3.h:60 reciprocal()
             if (finished) {
-                if (slot & kShadowBit) pb.visible[slot & ~kShadowBit] = hitTri == 0xFFFFFFFFu ? 1u : 0u;
-                else { pb.hit[slot] = make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2); pb.hitInstance[slot] = hitInst; }
+                io.template finish<INST>(slot, hitTri, hitT, hitB1, hitB2, hitInst);
                 slot = kIdle;
             }
         }
@@ -351,7 +397,7 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                     if (cond) {                                                         \
                         if (sp < kWsLdsStack) { stack[sp * 64] = (ref); ++sp; }         \
                         else if (!kNoSpill && sp < kWsLdsStack + kWsSpill) { spill[sp - kWsLdsStack] = (ref); ++sp; } \
-                        else atomicOr(pb.errorWord, ERR_STACK_OVERFLOW);      /* the host falls back to the four-wide tree for deeper ones */ \
+                        else atomicOr(io.errorWord, ERR_STACK_OVERFLOW);      /* the host falls back to the four-wide tree for deeper ones */ \
                     }
 #pragma unroll
                     for (int c = 0; c < 8; ++c) {
@@ -477,7 +523,7 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                     if (cond) {                                                         \
                         if (sp < kWsLdsStack) { stack[sp * 64] = (ref); ++sp; }         \
                         else if (!kNoSpill && sp < kWsLdsStack + kWsSpill) { spill[sp - kWsLdsStack] = (ref); ++sp; } \
-                        else atomicOr(pb.errorWord, ERR_STACK_OVERFLOW);      /* the host rejects trees that could get here */ \
+                        else atomicOr(io.errorWord, ERR_STACK_OVERFLOW);      /* the host rejects trees that could get here */ \
                     }
                     WS_PUSH(v0, c0)
                     WS_PUSH(v1, c1)
@@ -553,11 +599,7 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const PathBuffers&
                 }
             }
             if (finished) {
-                if (slot & kShadowBit) pb.visible[slot & ~kShadowBit] = hitTri == 0xFFFFFFFFu ? 1u : 0u;      // testVisibility
-                else {
-                    pb.hit[slot] = make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2);
-                    if (INST) pb.hitInstance[slot] = hitInst;
-                }
+                io.template finish<INST>(slot, hitTri, hitT, hitB1, hitB2, hitInst);
                 slot = kIdle;
             }
         }
@@ -687,7 +729,7 @@ __global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8
     WsDebug dbg;
     if (threadIdx.x < 64) wsProduce(pb, lds, numSlots, shardCapacity, parity, extRays, shadowRays, dbg);
     else {
-        wsConsume<COUNT, NC, QUANT, WIDE8, INST>(sc, pb, lds, refill, numTop, cnt, dbg);
+        wsConsume<COUNT, NC, QUANT, WIDE8, INST>(sc, WsRenderIO{pb}, lds, refill, numTop, cnt, dbg);
     }
     wsBlockAdd(pb.totals, T_EXT_RAYS, extRays, lds.red);
     wsBlockAdd(pb.totals, T_SHADOW_RAYS, shadowRays, lds.red);
@@ -736,6 +778,68 @@ void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams
         if (count) launchTraceWsT<true, 3>(sc, pb, rp, parity, blocks, stream);
         else launchTraceWsT<false, 3>(sc, pb, rp, parity, blocks, stream);
     }
+}
+
+// ---- ray queries: the same consumer fed from a caller's ray array ----------------------------------------------------------
+// The producer of a query launch streams contiguous ray indices: workgroup b takes the 128-ray chunks b, b + gridDim, ... (the
+// grid is the render's resident grid, so every workgroup is resident and the chunks of one workgroup are its share).  A chunk's
+// two 32-byte records per lane are loaded before the wait for ring space, so the loads overlap it.  Every index is a ray: no
+// state flags, no queue.  tag = kShadowBit for visibility queries.
+template <class LDS>
+__device__ __forceinline__ void wsProduceRays(const WsQueryIO& io, uint32_t n, uint32_t tag, LDS& lds, WsDebug& dbg) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t chunk = kSub * 64;
+    const uint32_t numChunks = (n + chunk - 1) / chunk;           // n < 2^31: c * chunk + 127 stays inside 32 bits
+    uint32_t tailLocal = 0;
+    for (uint32_t c = blockIdx.x; c < numChunks; c += gridDim.x) {
+        float4 o[kSub], d[kSub];
+        bool live[kSub];
+#pragma unroll
+        for (int j = 0; j < kSub; ++j) {
+            const uint32_t i = c * chunk + j * 64 + lane;
+            live[j] = i < n;
+            o[j] = live[j] ? ntLoad4(&io.rays[2 * (size_t)i]) : make_float4(0, 0, 0, 0);
+            d[j] = live[j] ? ntLoad4(&io.rays[2 * (size_t)i + 1]) : make_float4(0, 0, 0, 0);
+        }
+        if (!wsWaitSpace(lds, tailLocal, chunk, &dbg.producerWaits)) { if (lane == 0) atomicOr(io.errorWord, ERR_RING_SPACE); break; }
+#pragma unroll
+        for (int j = 0; j < kSub; ++j) tailLocal += wsAppend(lds, tailLocal, live[j], (c * chunk + j * 64 + lane) | tag, o[j], d[j]);
+        WS_STORE(&lds.tail, tailLocal, __ATOMIC_RELEASE);
+    }
+    WS_STORE(&lds.done, 1u, __ATOMIC_RELEASE);
+}
+
+template <int NC, bool QUANT, bool INST>
+__global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_query_ws(DevScene sc, WsQueryIO io, uint32_t n, uint32_t tag, uint32_t refill) {
+    __shared__ WsLds<NC> lds;
+    if (threadIdx.x == 0) { lds.tail = 0; lds.reserved = 0; lds.released = 0; lds.done = 0; }
+    __syncthreads();
+    WsCounts cnt;
+    WsDebug dbg;
+    if (threadIdx.x < 64) wsProduceRays(io, n, tag, lds, dbg);
+    else wsConsume<false, NC, QUANT, false, INST>(sc, io, lds, refill, 0u, cnt, dbg);       // no staged top nodes (numTop = 0)
+}
+
+template <int NC>
+static void launchQueryWsT(const DevScene& sc, const WsQueryIO& io, uint32_t n, uint32_t tag, uint32_t blocks, hipStream_t stream) {
+    const dim3 grid(blocks), block(64 * (NC + 1));
+    // the render's tree choice (launchTraceWsT): instanced scenes have float nodes only; the eight-wide tree is not used here
+    if (sc.instances) hipLaunchKernelGGL((k_query_ws<NC, false, true>), grid, block, 0, stream, sc, io, n, tag, g_refill);
+    else if (sc.nodesQ) hipLaunchKernelGGL((k_query_ws<NC, true, false>), grid, block, 0, stream, sc, io, n, tag, g_refill);
+    else hipLaunchKernelGGL((k_query_ws<NC, false, false>), grid, block, 0, stream, sc, io, n, tag, g_refill);
+}
+
+void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,
+                   int numCUs, hipStream_t stream) {
+    const bool quant = sc.nodesQ != nullptr && !sc.instances;
+    const uint32_t chunks = (n + kSub * 64 - 1) / (kSub * 64);
+    const uint32_t blocks = std::max(1u, std::min((uint32_t)numCUs * (uint32_t)traceWsBlocksPerCU(quant), chunks));
+    const WsQueryIO io = {rays, hits, instances, visible, errorWord};
+    const uint32_t tag = visible ? kShadowBit : 0u;
+    const int nc = wsConsumers(quant);
+    if (nc == 15) launchQueryWsT<15>(sc, io, n, tag, blocks, stream);
+    else if (nc == 7) launchQueryWsT<7>(sc, io, n, tag, blocks, stream);
+    else launchQueryWsT<3>(sc, io, n, tag, blocks, stream);
 }
 
 } // namespace slrhip

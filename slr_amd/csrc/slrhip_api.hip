@@ -159,6 +159,7 @@ struct slrhip_ctx {
     DevArray<uint32_t> flags, visible, shadowQueue, tailList, queueCount, activeSlots, blockDead;
     DevArray<uint64_t> totals;
     DevArray<float> resolveScratch;
+    DevArray<uint32_t> queryError;                // ERR_* bits of the ray queries (slrhip_query_status); apart from the render's error word
     PathBuffers buffers;
     uint64_t iterations = 0;
     bool firstRenderCall = true;
@@ -798,6 +799,9 @@ int slrhip_upload_scene(slrhip_ctx* ctx, const slrhip_scene_desc* d) {
     sc.envTopPDF = ctx->envTopPDF.ptr; sc.envTopCDF = ctx->envTopCDF.ptr;
     sc.envRowPDF = ctx->envRowPDF.ptr; sc.envRowCDF = ctx->envRowCDF.ptr;
     sc.camera = cam;
+    // the ray queries' error word: allocated here, so that a query call allocates nothing (and can be captured in a graph)
+    HIP_TRY(ctx->queryError.alloc(1));
+    HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));
     ctx->bvhDepth = treeDepth;
     ctx->bvhLeafRefs = leafRefs;
     ctx->haveScene = true;
@@ -1273,6 +1277,53 @@ int slrhip_trace_rays(slrhip_ctx* ctx, const float* rays, uint32_t n, float* hit
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(hits, dOut.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
     hitsToUV(hits, n);
+    return SLRHIP_OK;
+}
+
+// Ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): the render's wave-specialised traversal fed from
+// the caller's ray array (pt_trace_ws.hip, k_query_ws).  Stream-ordered; no allocation, no copy, no host synchronisation: the
+// only other work is clearing the query error word on the same stream.
+static int checkQueryArgs(slrhip_ctx* ctx, const char* what, const void* rays, uint32_t n, const void* out, size_t outAlign, const void* extra) {
+    const std::string w(what);
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": null context");
+    if (n >= 0x80000000u) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": n >= 2^31 rays");
+    if (n && (!rays || !out)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": null ray or result pointer");
+    if (((uintptr_t)rays & 15u) || ((uintptr_t)out & (outAlign - 1)) || ((uintptr_t)extra & 3u))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": misaligned pointer (rays: 16 bytes; hits: 16; instances / visible: 4)");
+    if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, w + ": no scene uploaded");
+    return SLRHIP_OK;
+}
+
+static int runQuery(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, slrhip_hit* hits, int32_t* instances, uint32_t* visible, void* stream) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(ctx->queryError.ptr, 0, sizeof(uint32_t), s));
+    launchQueryWs(ctx->scene, reinterpret_cast<const float4*>(rays), n, reinterpret_cast<float4*>(hits), instances, visible, ctx->queryError.ptr,
+                  ctx->numCUs, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_intersect_rays(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, slrhip_hit* hits, int32_t* instances, void* stream) {
+    int rc = checkQueryArgs(ctx, "slrhip_intersect_rays", rays, n, hits, 16, instances);
+    if (rc != SLRHIP_OK || n == 0) return rc;
+    return runQuery(ctx, rays, n, hits, instances, nullptr, stream);
+}
+
+int slrhip_test_visibility(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, uint32_t* visible, void* stream) {
+    int rc = checkQueryArgs(ctx, "slrhip_test_visibility", rays, n, visible, 4, nullptr);
+    if (rc != SLRHIP_OK || n == 0) return rc;
+    return runQuery(ctx, rays, n, nullptr, nullptr, visible, stream);
+}
+
+int slrhip_query_status(slrhip_ctx* ctx, uint32_t* bits, void* stream) {
+    if (!ctx || !bits) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_query_status: null argument");
+    *bits = 0;
+    if (!ctx->queryError.ptr) return SLRHIP_OK;          // no scene was ever uploaded: no query can have run
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(bits, ctx->queryError.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return SLRHIP_OK;
 }
 
