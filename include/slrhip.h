@@ -377,7 +377,12 @@ int slrhip_destroy(slrhip_ctx* ctx);
 
 /* Replaces: the Scene pointer graph handed to render() (SurfaceObjectAggregate ctor
  * SurfaceObject.cpp:226-250 builds the accelerator and light list; Scene::build :396-406).
- * Copies everything; the caller keeps ownership of the host arrays.                       */
+ * Copies everything; the caller keeps ownership of the host arrays.
+ * Failure: an upload refused by a check on the descriptor or on a host-built tree leaves
+ * the context exactly as it was: the previous scene and render state stay usable.  An
+ * upload that fails once it has begun to write the device (a HIP error, a device-built tree
+ * beyond the traversal's limits) leaves the context with no scene: later calls return
+ * SLRHIP_ERR_NO_SCENE until an upload succeeds.                                          */
 int slrhip_upload_scene(slrhip_ctx* ctx, const slrhip_scene_desc* scene);
 
 /* Replaces: sensor->init(W,H) PathTracingRenderer.cpp:67 (ImageSensor.cpp:35-51) plus the

@@ -108,7 +108,6 @@ class Context:
         _check(self.lib, self.lib.slrhip_create(C.byref(cfg), C.byref(self.handle)), "slrhip_create")
         self.components = self.lib.slrhip_components(self.handle)
         self.settings = None
-        self._scene = None
 
     def close(self):
         if getattr(self, "handle", None):
@@ -119,7 +118,6 @@ class Context:
         self.close()
 
     def upload_scene(self, scene):
-        self._scene = scene
         desc = scene.desc(self.mode)
         _check(self.lib, self.lib.slrhip_upload_scene(self.handle, C.byref(desc)), "slrhip_upload_scene")
 

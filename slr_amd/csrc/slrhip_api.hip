@@ -1,10 +1,8 @@
 // slrhip_api.hip — the C ABI of include/slrhip.h over the HIP kernels.
 //
-// Host-side responsibilities that the reference spreads over SurfaceObjectAggregate's
-// constructor (Core/SurfaceObject.cpp:226-250: accelerator + light list), Scene::build
-// (:396-406), PerspectiveCamera's constructor (Cameras/PerspectiveCamera.cpp:15-24) and
-// PathTracingRenderer::render's set-up (Renderers/PathTracingRenderer.cpp:27-70) live here:
-// flatten, build the 4-wide BVH, upload once, then drive the wavefront iterations.
+// A scene is checked and flattened on the host by scene_prep.cpp, then committed here: the device tree build (if chosen),
+// the uploads, the DevScene.  PathTracingRenderer::render's set-up (Renderers/PathTracingRenderer.cpp:27-70) lives here too:
+// render_begin sizes the path state, render drives the wavefront iterations.
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -21,6 +19,7 @@
 #include "../../include/slrhip.h"
 #include "bvh.h"
 #include "pt_kernels.h"
+#include "scene_prep.h"
 
 using namespace slrhip;
 
@@ -97,17 +96,6 @@ uint32_t prevPowerOf2(uint32_t x) {   // defines.h:136-143
     return x - (x >> 1);
 }
 
-// Kahan sum, BasicTypes/CompensatedSum.h:24-30
-struct KahanF {
-    float result = 0.0f, comp = 0.0f;
-    void add(float value) {
-        float cInput = value - comp;
-        float sumTemp = result + cInput;
-        comp = (sumTemp - result) - cInput;
-        result = sumTemp;
-    }
-};
-
 } // namespace
 
 struct slrhip_ctx {
@@ -135,7 +123,6 @@ struct slrhip_ctx {
     DevArray<float> spectrumPool;
     DevArray<float> lightPMF, lightCDF;
     DevArray<float4> shadeTables;
-    std::vector<float> hostSpectrumPool;      // the padded pool as uploaded (goes into the packed shade tables)
     DevArray<float> envTexels, envTopPDF, envTopCDF, envRowPDF, envRowCDF;
     DevArray<uint8_t> gridCells;
     DevArray<float> pointUV, pointSpectrum;
@@ -212,6 +199,100 @@ static void hitsToUV(float* hits, uint32_t n) {
     }
 }
 
+// Points a zero-initialised DevScene at the context's scene arrays and assigns it to ctx->scene in one go.
+static void bindScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const PreparedScene& p, uint32_t numNodes, bool quantized) {
+    DevScene sc{};
+    sc.nodes = reinterpret_cast<const float4*>(ctx->nodes.ptr); sc.numNodes = numNodes;
+    sc.nodesQ = quantized ? reinterpret_cast<const float4*>(ctx->nodesQ.ptr) : nullptr;
+    sc.nodes8 = p.wide8 ? reinterpret_cast<const float4*>(ctx->nodes8.ptr) : nullptr;
+    sc.leafTris = reinterpret_cast<const float4*>(ctx->leafTris.ptr);
+    sc.shadeTris = ctx->shadeTris.ptr;
+    sc.instances = p.instances.empty() ? nullptr : reinterpret_cast<const float4*>(ctx->instances.ptr); sc.numInstances = (uint32_t)p.instances.size();
+    sc.lightTris = ctx->lightTris.ptr; sc.numLights = (uint32_t)p.lightTris.size(); sc.lightPow2 = prevPowerOf2(sc.numLights);
+    sc.lightPMF = ctx->lightPMF.ptr; sc.lightCDF = ctx->lightCDF.ptr; sc.aggImportance = p.lightIntegral;
+    sc.materials = ctx->materials.ptr; sc.materialsS = ctx->materialsS.ptr; sc.numMaterials = (uint32_t)p.materials.size();
+    sc.hasMicrofacet = p.hasMicrofacet; sc.hasMulti = p.hasMulti;
+    sc.spectra = ctx->spectra.ptr; sc.numSpectra = (uint32_t)p.spectra.size();
+    sc.spectrumPool = ctx->spectrumPool.ptr; sc.numSpectrumData = (uint32_t)p.spectrumPool.size();
+    sc.textures = ctx->textures.ptr; sc.numTextures = (uint32_t)p.textures.size(); sc.matTex = ctx->matTex.ptr;
+    sc.triUV = ctx->triUV.ptr; sc.alphaTris = ctx->alphaTris.ptr; sc.texTexels = ctx->texTexels.ptr;
+    sc.shadeTables = p.tablesFit ? ctx->shadeTables.ptr : nullptr;
+    std::memcpy(sc.tableEnd, p.tableEnd, sizeof(sc.tableEnd));
+    if (d.env) {
+        sc.hasEnv = 1; sc.envScale = d.env->scale;
+        sc.envWidth = d.env->width; sc.envHeight = d.env->height; sc.envMapWidth = d.env->map_width; sc.envMapHeight = d.env->map_height;
+    }
+    sc.envTexels = ctx->envTexels.ptr;
+    sc.envTopPDF = ctx->envTopPDF.ptr; sc.envTopCDF = ctx->envTopCDF.ptr; sc.envRowPDF = ctx->envRowPDF.ptr; sc.envRowCDF = ctx->envRowCDF.ptr;
+    sc.gridWidth = p.gridWidth; sc.gridHeight = p.gridHeight;
+    sc.gridCells = ctx->gridCells.ptr; sc.pointUV = ctx->pointUV.ptr; sc.pointSpectrum = ctx->pointSpectrum.ptr;
+    sc.camera = p.camera;
+    ctx->scene = sc;
+}
+
+// The device half of slrhip_upload_scene: the device tree build (when prepareScene chose it), the uploads, the DevScene.  An upload
+// may free an array of the previous scene before it fails, so the context holds no scene from the first statement on until the
+// last step has succeeded: a failure here leaves it without one (SLRHIP_ERR_NO_SCENE), never naming freed or mismatched arrays.
+static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const PreparedScene& p) {
+    ctx->haveScene = ctx->haveRender = false;
+    HIP_TRY(hipSetDevice(ctx->device));
+    uint32_t numNodes = (uint32_t)p.bvh.nodes.size(), depth = p.bvh.depth;
+    uint64_t leafRefs = p.bvh.leafTris.size();
+    bool quantized = p.quantized;
+    if (p.build == TreeBuild::Device) {
+        // the whole geometry on the GPU: tree, quantized nodes, leaf packets, shading records (bvh_device.hip)
+        DeviceGeometry g;
+        std::string err;
+        if (buildGeometryDevice(d.vertices, d.num_vertices, d.triangles, d.num_triangles, p.lightTriangles.data(), (uint32_t)p.lightTriangles.size(),
+                                p.wantQuantized, &g, &err) != 0)
+            return fail(SLRHIP_ERR_HIP, "slrhip_upload_scene: " + err);
+        if (const int rc = checkTreeLimits(g.depth, g.numNodes, g.numLeafTris,
+                                           "device-built tree deeper than the 64-entry traversal stack (QBVH.h:299); use the host build", &err)) {
+            for (void* a : {(void*)g.nodes, (void*)g.nodesQ, (void*)g.leafTris, (void*)g.shadeTris}) (void)hipFree(a);
+            return fail(rc, err);
+        }
+        ctx->nodes.adopt(g.nodes, g.numNodes);
+        ctx->leafTris.adopt(g.leafTris, g.numLeafTris);
+        ctx->shadeTris.adopt(g.shadeTris, d.num_triangles);
+        quantized = g.nodesQ != nullptr && useQuantizedNodes(g.numNodes);
+        if (quantized) ctx->nodesQ.adopt(g.nodesQ, g.numNodes); else (void)hipFree(g.nodesQ);
+        numNodes = g.numNodes; depth = g.depth; leafRefs = g.numLeafTris;
+    }
+    else {
+        HIP_TRY(ctx->nodes.upload(p.bvh.nodes));
+        if (p.quantized) HIP_TRY(ctx->nodesQ.upload(p.bvh.quantized));
+        if (p.wide8) HIP_TRY(ctx->nodes8.upload(p.bvh.nodes8));
+        HIP_TRY(ctx->leafTris.upload(p.bvh.leafTris));
+    }
+    HIP_TRY(ctx->textures.upload(p.textures));
+    HIP_TRY(ctx->texTexels.upload(p.texTexels));
+    HIP_TRY(ctx->matTex.upload(p.matTex));
+    HIP_TRY(ctx->triUV.upload(p.triUV));
+    HIP_TRY(ctx->alphaTris.upload(p.alphaTris));
+    if (p.build != TreeBuild::Device) HIP_TRY(ctx->shadeTris.upload(p.shadeTris));
+    HIP_TRY(ctx->lightTris.upload(p.lightTris));
+    HIP_TRY(ctx->instances.upload(p.instances));
+    HIP_TRY(ctx->materials.upload(p.materials));
+    HIP_TRY(ctx->materialsS.upload(p.materialsS));
+    HIP_TRY(ctx->spectrumPool.upload(p.spectrumPool));
+    HIP_TRY(ctx->spectra.upload(p.spectra));
+    HIP_TRY(ctx->lightPMF.upload(p.lightPMF));
+    HIP_TRY(ctx->lightCDF.upload(p.lightCDF));
+    HIP_TRY(ctx->shadeTables.upload(p.shadeTables));
+    HIP_TRY(ctx->envTexels.upload(p.envTexels));
+    HIP_TRY(ctx->envTopPDF.upload(p.envTopPDF)); HIP_TRY(ctx->envTopCDF.upload(p.envTopCDF));
+    HIP_TRY(ctx->envRowPDF.upload(p.envRowPDF)); HIP_TRY(ctx->envRowCDF.upload(p.envRowCDF));
+    HIP_TRY(ctx->gridCells.upload(p.gridCells)); HIP_TRY(ctx->pointUV.upload(p.pointUV)); HIP_TRY(ctx->pointSpectrum.upload(p.pointSpectrum));
+    // the ray queries' error word: allocated here, so that a query call allocates nothing (and can be captured in a graph)
+    HIP_TRY(ctx->queryError.alloc(1));
+    HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));
+    bindScene(ctx, d, p, numNodes, quantized);
+    ctx->bvhDepth = depth;
+    ctx->bvhLeafRefs = leafRefs;
+    ctx->haveScene = true;
+    return SLRHIP_OK;
+}
+
 extern "C" {
 
 const char* slrhip_last_error_string(void) { return g_lastError.c_str(); }
@@ -253,559 +334,11 @@ int slrhip_components(const slrhip_ctx* ctx) { return ctx && ctx->config.mode ==
 
 int slrhip_upload_scene(slrhip_ctx* ctx, const slrhip_scene_desc* d) {
     if (!ctx || !d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: null argument");
-    if (!d->vertices || !d->triangles || !d->materials || !d->spectra || d->num_triangles == 0 || d->num_vertices == 0)
-        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: empty scene");
-    // the Meng-15 tables, wherever they are given: the kernels index with these bytes
-    if (ctx->config.mode == SLRHIP_MODE_SPECTRAL && d->upsampling) {
-        const slrhip_upsampling_tables* t = d->upsampling;
-        if (!t->cells || !t->point_uv || !t->point_spectrum || t->grid_width == 0 || t->grid_height == 0 || t->num_points == 0 || t->num_points > 255)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: incomplete slrhip_scene_desc::upsampling");
-        for (size_t c = 0; c < (size_t)t->grid_width * t->grid_height; ++c) {
-            const uint8_t* cell = t->cells + c * 8;
-            if (cell[1] > 6) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: upsampling cell with more than 6 points");
-            for (int k = 0; k < (cell[0] ? 4 : cell[1]); ++k)
-                if (cell[2 + k] >= t->num_points) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: upsampling point index out of range");
-        }
-    }
-    if (d->env) {
-        const slrhip_envmap& e = *d->env;
-        if (ctx->config.mode == SLRHIP_MODE_SPECTRAL && !d->upsampling)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: an environment map in spectral mode needs slrhip_scene_desc::upsampling");
-        if (!e.texels || !e.importance || e.width == 0 || e.height == 0 || e.map_width == 0 || e.map_height == 0 ||
-            e.width > 32768 || e.height > 32768 || e.map_width > 32768 || e.map_height > 32768)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: bad environment map");
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    auto t0 = std::chrono::steady_clock::now();
-
-    // --- validate indices (a bad index would fault the GPU) --------------------------------------
-    for (uint32_t i = 0; i < d->num_triangles; ++i) {
-        const slrhip_triangle& t = d->triangles[i];
-        if (t.v[0] >= d->num_vertices || t.v[1] >= d->num_vertices || t.v[2] >= d->num_vertices || t.material >= d->num_materials)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: triangle index out of range");
-    }
-    const bool spectral = ctx->config.mode == SLRHIP_MODE_SPECTRAL;
-    // --- textures: checkerboard spectrum / float / normal textures ----------------------------------------
-    const uint32_t numTextures = d->textures ? d->num_textures : 0u;
-    if (numTextures > 32767u) return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: more than 32767 textures");
-    std::vector<DevTexture> devTextures(numTextures);
-    bool anyImageTexture = false;
-    for (uint32_t i = 0; i < numTextures; ++i) {
-        const slrhip_texture& t = d->textures[i];
-        DevTexture dt;
-        std::memset(&dt, 0, sizeof(dt));
-        dt.kind = t.kind; dt.ox = t.offset[0]; dt.oy = t.offset[1]; dt.sx = t.scale[0]; dt.sy = t.scale[1];
-        dt.v0 = t.value[0]; dt.v1 = t.value[1]; dt.spec0 = dt.spec1 = -1;
-        if (t.kind == SLRHIP_TEXTURE_CHECKER_SPECTRUM) {
-            for (int k = 0; k < 2; ++k) {
-                if (t.spectrum[k] < 0 || (uint32_t)t.spectrum[k] >= d->num_spectra)
-                    return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: texture names a spectrum out of range");
-                if (spectral && d->spectra[t.spectrum[k]].kind == SLRHIP_SPECTRUM_RGB_ONLY)
-                    return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectral mode needs a spectral descriptor for every spectrum in use");
-            }
-            dt.spec0 = t.spectrum[0]; dt.spec1 = t.spectrum[1];
-            for (int c = 0; c < 3; ++c) { dt.rgb0[c] = d->spectra[t.spectrum[0]].rgb[c]; dt.rgb1[c] = d->spectra[t.spectrum[1]].rgb[c]; }
-        }
-        else if (t.kind == SLRHIP_TEXTURE_CHECKER_NORMAL) {
-            if (!(t.value[0] > 0.0f && t.value[0] <= 1.0f))        // SLRAssert of the reference's constructor
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: checkerboard normal texture needs stepWidth in (0, 1]");
-        }
-        else if (t.kind == SLRHIP_TEXTURE_IMAGE_SPECTRUM) {
-            // ImageSpectrumTexture: width, height and the first texel travel in the record (DevTexture, device_types.h)
-            const uint64_t w = t.reserved[0], h = t.reserved[1], first = t.reserved[2];
-            if (w == 0 || h == 0 || w > 65535 || h > 65535 || !d->texture_texels || first + w * h > d->num_texture_texels)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: image texture outside slrhip_scene_desc::texture_texels");
-            if (spectral && !d->upsampling)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: image textures in spectral mode need slrhip_scene_desc::upsampling");
-            dt.spec0 = (int32_t)w; dt.spec1 = (int32_t)h; dt.pad = (uint32_t)first;
-            anyImageTexture = true;
-        }
-        else if (t.kind != SLRHIP_TEXTURE_CHECKER_FLOAT) return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: unknown texture kind");
-        devTextures[i] = dt;
-    }
-    std::vector<DevMatTex> matTex(d->num_materials);
-    std::vector<int32_t> alphaOfMaterial(d->num_materials, -1);
-    bool anyAlpha = false;
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const slrhip_material& m = d->materials[i];
-        DevMatTex mt = {{-1, -1, -1}, -1};
-        const uint32_t nmap = m.reserved & 0xFFFFu, amap = m.reserved >> 16;
-        if (nmap > numTextures || amap > numTextures) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: material names a texture out of range");
-        if (nmap) {
-            if (d->textures[nmap - 1].kind != SLRHIP_TEXTURE_CHECKER_NORMAL) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: a normal map must be a CHECKER_NORMAL texture");
-            mt.normalMap = (int32_t)nmap - 1;
-        }
-        if (amap) {
-            if (d->textures[amap - 1].kind != SLRHIP_TEXTURE_CHECKER_FLOAT) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: an alpha map must be a CHECKER_FLOAT texture");
-            alphaOfMaterial[i] = (int32_t)amap - 1;
-            anyAlpha = true;
-        }
-        if (m.emittance < -1) return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: textured emittance is not supported");
-        for (int k = 0; k < 3 && m.type != SLRHIP_MATERIAL_MULTI; ++k) {
-            if (m.spectrum[k] >= -1) continue;
-            const uint32_t t = (uint32_t)(-2 - m.spectrum[k]);
-            if (t >= numTextures || (d->textures[t].kind != SLRHIP_TEXTURE_CHECKER_SPECTRUM && d->textures[t].kind != SLRHIP_TEXTURE_IMAGE_SPECTRUM))
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: material spectrum slot names a texture that is not a spectrum texture");
-            mt.slot[k] = (int32_t)t;
-        }
-        matTex[i] = mt;
-    }
-    std::vector<DevMaterial> mats(d->num_materials);
-    std::vector<DevMaterialS> matsS(d->num_materials);
-    std::vector<char> emitting(d->num_materials, 0);
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const slrhip_material& m = d->materials[i];
-        DevMaterial dm;
-        std::memset(&dm, 0, sizeof(dm));
-        dm.type = m.type;
-        dm.param = m.param;
-        if (m.type > SLRHIP_MATERIAL_MULTI)
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: unknown material type");
-        if (m.type == SLRHIP_MATERIAL_MULTI) {
-            // MultiBSDF of two earlier materials — single lobes, or MULTI records of single lobes (include/slrhip.h); the record carries indices, scales, flags
-            if ((uint32_t)m.spectrum[2] > 3u)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: MULTI material with unknown inverse bits");
-            uint32_t childType[2];
-            for (int k = 0; k < 2; ++k) {
-                if (m.spectrum[k] < 0 || (uint32_t)m.spectrum[k] >= i)
-                    return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: MULTI component must be an earlier entry of the material table");
-                if ((uint32_t)m.spectrum[k] > kMultiMaxChildIndex)
-                    return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: MULTI component index beyond 1023");
-                const slrhip_material& cmat = d->materials[m.spectrum[k]];
-                childType[k] = cmat.type;
-                if (childType[k] == SLRHIP_MATERIAL_MULTI) {
-                    // one level of nesting: the components of a component are single lobes (four lobes in all, the reference's
-                    // MultiBSDF::maxNumElems); an InverseBSDF over a MultiBSDF is not supported
-                    if (d->materials[cmat.spectrum[0]].type >= SLRHIP_MATERIAL_MULTI || d->materials[cmat.spectrum[1]].type >= SLRHIP_MATERIAL_MULTI)
-                        return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: MULTI materials nest one level deep (at most four lobes)");
-                    if ((m.spectrum[2] >> k) & 1)
-                        return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: inverse of a MULTI component is not supported");
-                }
-                if (((m.spectrum[2] >> k) & 1) && (childType[k] == SLRHIP_MATERIAL_GLASS || childType[k] == SLRHIP_MATERIAL_MICROFACET_GLASS))
-                    return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: inverse of a two-sided lobe (glass, microfacet glass) is not supported");
-            }
-            if (m.emittance >= 0 && (uint32_t)m.emittance >= d->num_spectra)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectrum index out of range");
-            if (spectral && m.emittance >= 0 && d->spectra[m.emittance].kind == SLRHIP_SPECTRUM_RGB_ONLY)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectral mode needs a spectral descriptor for every spectrum in use");
-            dm.param = 1.0f * m.param;          // `scale * (1.0f - factor)` / `scale * factor` with scale = 1 (MixedSurfaceMaterial.cpp:16-17)
-            dm.onA = 1.0f * m.param2;
-            const uint32_t bits = packMultiBits((uint32_t)m.spectrum[0], (uint32_t)m.spectrum[1], (uint32_t)m.spectrum[2], childType[0], childType[1]);
-            std::memcpy(&dm.onB, &bits, sizeof(bits));
-            if (m.emittance >= 0)
-                for (int k = 0; k < 3; ++k) dm.emittance[k] = d->spectra[m.emittance].rgb[k];
-            emitting[i] = m.emittance >= 0;
-            mats[i] = dm;
-            DevMaterialS ds;
-            ds.type = dm.type; ds.param = dm.param; ds.onA = dm.onA; ds.onB = dm.onB;
-            ds.spec[0] = ds.spec[1] = ds.spec[2] = -1; ds.spec[3] = m.emittance;
-            matsS[i] = ds;
-            continue;
-        }
-        if (m.type == SLRHIP_MATERIAL_WARD || m.type == SLRHIP_MATERIAL_ASHIKHMIN) {
-            dm.onA = m.param2;          // the lobe's second scalar travels in the Oren-Nayar slot (unused by these types)
-            if (!(m.param > 0.0f) || !(m.param2 > 0.0f))
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: Ward / Ashikhmin need param > 0 and param2 > 0");
-        }
-        if (m.type == SLRHIP_MATERIAL_MATTE && m.param >= 0.0f) {
-            // OrenNayerBRDF ctor, OrenNayerBRDF.h:28-30: double literals in a float expression
-            const float sigma = m.param;
-            dm.onA = (float)(1.0f - 0.5f * sigma * sigma / (sigma * sigma + 0.33));
-            dm.onB = (float)(0.45 * sigma * sigma / (sigma * sigma + 0.09));
-        }
-        if ((m.type == SLRHIP_MATERIAL_MICROFACET_METAL || m.type == SLRHIP_MATERIAL_MICROFACET_GLASS) && !(m.param > 0.0f))
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: microfacet material needs alpha_g > 0");
-        auto fetch = [&](int32_t idx, float* dst) -> bool {
-            if (idx < 0) return true;
-            if ((uint32_t)idx >= d->num_spectra) return false;
-            for (int k = 0; k < 3; ++k) dst[k] = d->spectra[idx].rgb[k];   // RGBTemplate::evaluate RGBTypes.h:124-126
-            return true;
-        };
-        // `scale * spectrum` with scale = 1.0f (basic_SurfaceMaterials.cpp:22,33,42) is exact
-        if (!fetch(m.spectrum[0], dm.a) || !fetch(m.spectrum[1], dm.b) || !fetch(m.spectrum[2], dm.c) || !fetch(m.emittance, dm.emittance))
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectrum index out of range");
-        if (m.spectrum[0] == -1 && m.type <= SLRHIP_MATERIAL_GLASS)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: material without its first spectrum");
-        if (m.type == SLRHIP_MATERIAL_ASHIKHMIN && (m.spectrum[0] == -1 || m.spectrum[1] == -1))
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: Ashikhmin needs Rs and Rd");
-        if (m.type == SLRHIP_MATERIAL_WARD && m.spectrum[0] == -1)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: Ward needs R");
-        if (m.type >= SLRHIP_MATERIAL_METAL && m.type <= SLRHIP_MATERIAL_MICROFACET_GLASS && (m.spectrum[1] == -1 || m.spectrum[2] == -1))
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: material without its eta / k spectra");
-        emitting[i] = m.emittance >= 0;
-        mats[i] = dm;
-        DevMaterialS ds;
-        ds.type = dm.type; ds.param = dm.param; ds.onA = dm.onA; ds.onB = dm.onB;
-        ds.spec[0] = m.spectrum[0]; ds.spec[1] = m.spectrum[1]; ds.spec[2] = m.spectrum[2]; ds.spec[3] = m.emittance;
-        matsS[i] = ds;
-        if (spectral)
-            for (int k = 0; k < 4; ++k)
-                if (ds.spec[k] >= 0 && d->spectra[ds.spec[k]].kind == SLRHIP_SPECTRUM_RGB_ONLY)
-                    return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectral mode needs a spectral descriptor for every spectrum in use");
-    }
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const DevMatTex& mt = matTex[i];
-        if (mt.slot[0] >= 0 || mt.slot[1] >= 0 || mt.slot[2] >= 0 || mt.normalMap >= 0) { mats[i].type |= kMatTexturedBit; matsS[i].type |= kMatTexturedBit; }
-    }
-    // spectrum table (spectral mode): descriptors + the float pool, bounds-checked here because the kernels index it
-    std::vector<DevSpectrum> devSpectra(d->num_spectra);
-    for (uint32_t i = 0; i < d->num_spectra && spectral; ++i) {
-        const slrhip_spectrum& sp = d->spectra[i];
-        DevSpectrum ds;
-        std::memset(&ds, 0, sizeof(ds));
-        ds.kind = sp.kind; ds.numPoints = sp.reserved; ds.numSamples = sp.num_samples; ds.dataOffset = sp.data_offset;
-        ds.scale = sp.scale; ds.lambdaMin = sp.lambda_min; ds.lambdaMax = sp.lambda_max;
-        ds.cellOffset = 0xFFFFFFFFu;
-        size_t need = 0;
-        if (sp.kind == SLRHIP_SPECTRUM_REGULAR) need = sp.num_samples;
-        else if (sp.kind == SLRHIP_SPECTRUM_IRREGULAR) need = 2 * (size_t)sp.num_samples;
-        else if (sp.kind == SLRHIP_SPECTRUM_UPSAMPLED) need = 4 + 4 * (size_t)sp.num_samples;
-        if (sp.kind != SLRHIP_SPECTRUM_RGB_ONLY) {
-            if (sp.num_samples < 2 || (size_t)sp.data_offset + need > d->num_spectrum_data || !d->spectrum_data)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: spectrum data out of range");
-            if (sp.kind == SLRHIP_SPECTRUM_UPSAMPLED && sp.data_offset % 4 != 0)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: upsampled spectrum payload must start at a multiple of 4 floats");
-            if (sp.kind == SLRHIP_SPECTRUM_UPSAMPLED && sp.reserved != 0 && sp.reserved != 3 && sp.reserved != 4)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: upsampled spectrum must resolve to 0, 3 or 4 points");
-        }
-        devSpectra[i] = ds;
-    }
-
-    // --- accelerator -------------------------------------------------------------------------------
-    // Host build (binned SAH, bvh.cpp / spatial splits, sbvh.cpp) unless the context asks for the device build (bvh_device.hip: LBVH,
-    // the same collapse; for scenes of millions of triangles, where the host build takes seconds).  The device build also writes the
-    // per-triangle records on the GPU; it does not cover alpha-textured triangles (their leaf entries are patched on the host).
-    static const std::string envBuild = [] { const char* e = getenv("SLRHIP_BVH"); return std::string(e ? e : ""); }();      // "host" / "device": override
-    // automatic: from 2^20 triangles on (host build of 10 M triangles: 2.9 s on 16 cores; device: 0.13 s, traversal 5 % slower)
-    const bool wantDevice = envBuild == "device" || (ctx->config.flags & SLRHIP_FLAG_BVH_DEVICE_BUILD) != 0 ||
-                            (envBuild != "host" && envBuild != "sbvh" && !(ctx->config.flags & SLRHIP_FLAG_BVH_SPATIAL_SPLITS) && d->num_triangles >= (1u << 20));
-    const uint32_t numInstances = d->instances ? d->num_instances : 0u;
-    const bool deviceBuild = wantDevice && !anyAlpha && d->num_triangles >= 1024 && numInstances == 0;
-    QBVH bvh;
-    std::vector<DevInstance> devInstances;
-    if (numInstances) {
-        // instanced meshes (TransformedSurfaceObject, Core/SurfaceObject.cpp:303-392): two-level tree in one node array (bvh.h)
-        for (uint32_t k = 0; k < numInstances; ++k) {
-            const slrhip_instance& in = d->instances[k];
-            if (in.num_triangles == 0 || (uint64_t)in.first_triangle + in.num_triangles > d->num_triangles)
-                return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: instance names triangles out of range");
-            for (uint32_t t = 0; t < in.num_triangles; ++t)
-                if (emitting[d->triangles[in.first_triangle + t].material])
-                    return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: instanced triangles must not emit");
-        }
-        std::string err;
-        if (buildInstancedQBVH(d->vertices, d->triangles, d->num_triangles, d->instances, numInstances, &bvh, &devInstances, &err) != 0)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: " + err);
-        if (3 * bvh.depth + 1 > 64)
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: two-level tree deeper than the 64-entry traversal stack (QBVH.h:299)");
-        if ((uint64_t)bvh.nodes.size() * sizeof(QNode) >= (1ull << 32) || (uint64_t)bvh.leafTris.size() * sizeof(LeafTri) >= (1ull << 32))
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: node or leaf array beyond the 4 GiB the traversal kernels address with 32-bit offsets");
-    }
-    else if (!deviceBuild) {
-        static const bool wide8 = [] { const char* e = tuningEnv("SLRHIP_WIDE8"); return e && std::string(e) == "1"; }();      // measurement: the eight-wide quantized tree
-        if (buildQBVH(d->vertices, d->triangles, d->num_triangles, &bvh, (ctx->config.flags & SLRHIP_FLAG_BVH_SPATIAL_SPLITS) != 0, wide8) != 0)
-            return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_upload_scene: BVH build failed");
-        if (3 * bvh.depth + 1 > 64)
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: tree deeper than the 64-entry traversal stack (QBVH.h:299)");
-        if ((uint64_t)bvh.nodes.size() * sizeof(QNode) >= (1ull << 32) || (uint64_t)bvh.leafTris.size() * sizeof(LeafTri) >= (1ull << 32))
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: node or leaf array beyond the 4 GiB the traversal kernels address with 32-bit offsets");
-    }
-
-    // --- per-triangle shading records and the light list (SurfaceObject.cpp:232-249) ---------------------
-    std::vector<ShadeTri> shade(deviceBuild ? 0 : d->num_triangles);      // the device build writes these records itself (k_shade_tris)
-    std::vector<LightTri> lights;
-    std::vector<uint32_t> lightTriangles;
-    std::vector<float> importances;
-    float lightIntegral = 0.0f;
-    for (uint32_t i = 0; i < d->num_triangles; ++i) {
-        const slrhip_triangle& t = d->triangles[i];
-        if (deviceBuild && !emitting[t.material]) continue;
-        const slrhip_vertex &v0 = d->vertices[t.v[0]], &v1 = d->vertices[t.v[1]], &v2 = d->vertices[t.v[2]];
-        ShadeTri s;
-        std::memset(&s, 0, sizeof(s));
-        float e1[3], e2[3];
-        for (int a = 0; a < 3; ++a) {
-            s.n0[a] = v0.normal[a]; s.n1[a] = v1.normal[a]; s.n2[a] = v2.normal[a];
-            s.t0[a] = v0.tangent[a]; s.t1[a] = v1.tangent[a]; s.t2[a] = v2.tangent[a];
-            e1[a] = v1.position[a] - v0.position[a];
-            e2[a] = v2.position[a] - v0.position[a];
-        }
-        // normalize(cross(edge01, edge02)) TriangleMesh.cpp:171 — same float ops as the reference, on the host
-        float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        float len = std::sqrt(cx * cx + cy * cy + cz * cz);
-        float r = 1.0f / len;
-        s.gnx = cx * r; s.gny = cy * r; s.gnz = cz * r;
-        s.areaPDF = 1.0f / (0.5f * len);                    // 1 / Triangle::area() :217-222
-        s.material = t.material;
-        s.light = -1;
-        if (emitting[t.material]) {
-            s.light = (int32_t)lights.size();
-            LightTri l;
-            std::memset(&l, 0, sizeof(l));
-            for (int a = 0; a < 3; ++a) {
-                l.p0[a] = v0.position[a]; l.p1[a] = v1.position[a]; l.p2[a] = v2.position[a];
-                l.n0[a] = v0.normal[a]; l.n1[a] = v1.normal[a]; l.n2[a] = v2.normal[a];
-                l.t0[a] = v0.tangent[a]; l.t1[a] = v1.tangent[a]; l.t2[a] = v2.tangent[a];
-            }
-            l.tri = i; l.material = t.material; l.areaPDF = s.areaPDF;
-            l.gnx = s.gnx; l.gny = s.gny; l.gnz = s.gnz;
-            lights.push_back(l);
-            lightTriangles.push_back(i);
-            importances.push_back(1.0f);                    // SingleSurfaceObject::importance :69-71
-        }
-        if (!deviceBuild) shade[i] = s;
-    }
-    if (lights.empty() && !d->env) return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: scene has no emitting triangle and no environment light");
-
-    // RegularConstantDiscrete1D ctor, Core/distributions.cpp:76-95
-    std::vector<float> pmf = importances, cdf(importances.size() + 1, 0.0f);
-    {
-        KahanF sum;
-        for (size_t i = 0; i < pmf.size(); ++i) { sum.add(pmf[i]); cdf[i + 1] = sum.result; }
-        float integral = sum.result;
-        lightIntegral = integral;
-        for (size_t i = 0; i < pmf.size(); ++i) { pmf[i] /= integral; cdf[i + 1] /= integral; }
-    }
-
-    // --- environment sphere: texels + the importance distribution -------------------------------------------
-    // InfiniteSphereSurfaceObject ctor (SurfaceObject.cpp:137-141) -> IBLEmission::createIBLImportanceMap
-    // (IBLEmission.cpp:11-13) -> RegularConstantContinuous2D (Core/distributions.cpp:186-212) over
-    // sin(pi (y + 0.5) / mapHeight) * importance (Textures/image_textures.cpp:126-133).
-    std::vector<float> envTexels, envTopPDF, envTopCDF, envRowPDF, envRowCDF;
-    if (d->env) {
-        const slrhip_envmap& e = *d->env;
-        const uint32_t mw = e.map_width, mh = e.map_height;
-        envTexels.assign(e.texels, e.texels + (size_t)e.width * e.height * 3);
-        envRowPDF.resize((size_t)mw * mh);
-        envRowCDF.assign((size_t)(mw + 1) * mh, 0.0f);
-        envTopPDF.resize(mh);
-        envTopCDF.assign(mh + 1, 0.0f);
-        // RegularConstantContinuous1D ctor, distributions.cpp:127-147
-        auto build1D = [](float* PDF, float* CDF, uint32_t n) -> float {
-            KahanF sum;
-            CDF[0] = 0.0f;
-            for (uint32_t i = 0; i < n; ++i) { sum.add(PDF[i] / n); CDF[i + 1] = sum.result; }
-            for (uint32_t i = 0; i < n; ++i) { PDF[i] /= sum.result; CDF[i + 1] /= sum.result; }
-            return sum.result;
-        };
-        for (uint32_t y = 0; y < mh; ++y) {
-            float* row = envRowPDF.data() + (size_t)y * mw;
-            for (uint32_t x = 0; x < mw; ++x)
-                row[x] = (float)(std::sin(M_PI * (y + 0.5f) / mh) * e.importance[(size_t)y * mw + x]);
-            envTopPDF[y] = build1D(row, envRowCDF.data() + (size_t)y * (mw + 1), mw);
-        }
-        build1D(envTopPDF.data(), envTopCDF.data(), mh);
-    }
-
-    // --- camera constants, PerspectiveCamera.cpp:15-24, :55 -------------------------------------------------
-    DevCamera cam;
-    std::memcpy(cam.mat, d->camera.local_to_world, sizeof(cam.mat));
-    std::memcpy(cam.matInv, d->camera.world_to_local, sizeof(cam.matInv));
-    cam.lensRadius = d->camera.lens_radius;
-    cam.imgPlaneDistance = d->camera.img_plane_distance;
-    cam.objPlaneDistance = d->camera.obj_plane_distance;
-    cam.opHeight = 2.0f * cam.objPlaneDistance * std::tan(d->camera.fov_y * 0.5f);
-    cam.opWidth = cam.opHeight * d->camera.aspect;
-    cam.imgPlaneArea = (float)((double)(cam.opWidth * cam.opHeight) * std::pow((double)(cam.imgPlaneDistance / cam.objPlaneDistance), 2.0));
-    cam.areaPDF = cam.lensRadius > 0.0f ? (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius)) : 1.0f;
-    cam.sensitivity = d->camera.sensitivity > 0 ? d->camera.sensitivity
-                                                : (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius));
-
-    // --- upload ----------------------------------------------------------------------------------------------
-    // trees beyond the L2 (>= 64 Ki nodes = 8 MiB) are also stored with 8-bit child boxes: half the bytes per node visit
-    static const bool noQuant = [] { const char* e = tuningEnv("SLRHIP_QUANT"); return e && std::string(e) == "0"; }();
-    static const bool forceQuant = [] { const char* e = tuningEnv("SLRHIP_QUANT"); return e && std::string(e) == "1"; }();   // experiment: small trees too
-    bool quant = false, useWide8 = false;
-    uint32_t numNodes = 0, treeDepth = 0;
-    uint64_t leafRefs = 0;
-    if (deviceBuild) {
-        // the whole geometry on the GPU: tree, quantized nodes, leaf packets, shading records (bvh_device.hip)
-        DeviceGeometry g;
-        std::string err;
-        // whether the tree will pass 64 Ki nodes is not known before it is built: ask for the quantized records whenever it could
-        const bool wantQ = (d->num_triangles >= 65536 * 2 || forceQuant) && !noQuant;
-        if (buildGeometryDevice(d->vertices, d->num_vertices, d->triangles, d->num_triangles, lightTriangles.data(), (uint32_t)lightTriangles.size(), wantQ, &g, &err) != 0)
-            return fail(SLRHIP_ERR_HIP, "slrhip_upload_scene: " + err);
-        ctx->nodes.adopt(g.nodes, g.numNodes);
-        ctx->leafTris.adopt(g.leafTris, g.numLeafTris);
-        ctx->shadeTris.adopt(g.shadeTris, d->num_triangles);
-        quant = g.nodesQ != nullptr && (g.numNodes >= 65536 || forceQuant);
-        if (g.nodesQ) { if (quant) ctx->nodesQ.adopt(g.nodesQ, g.numNodes); else (void)hipFree(g.nodesQ); }
-        numNodes = g.numNodes; treeDepth = g.depth; leafRefs = g.numLeafTris;
-        if (3 * treeDepth + 1 > 64)
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: device-built tree deeper than the 64-entry traversal stack (QBVH.h:299); use the host build");
-        if ((uint64_t)numNodes * sizeof(QNode) >= (1ull << 32) || leafRefs * sizeof(LeafTri) >= (1ull << 32))
-            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_upload_scene: node or leaf array beyond the 4 GiB the traversal kernels address with 32-bit offsets");
-    }
-    else {
-        HIP_TRY(ctx->nodes.upload(bvh.nodes));
-        quant = (bvh.nodes.size() >= 65536 || forceQuant) && !noQuant && numInstances == 0;      // instanced scenes traverse float nodes
-        if (quant) { quantizeNodes(&bvh); HIP_TRY(ctx->nodesQ.upload(bvh.quantized)); }
-        numNodes = (uint32_t)bvh.nodes.size(); treeDepth = bvh.depth; leafRefs = bvh.leafTris.size();
-        useWide8 = !bvh.nodes8.empty() && 7 * bvh.depth8 + 1 <= 64;          // up to seven pushes per level on the 64-entry stack
-        if (useWide8) HIP_TRY(ctx->nodes8.upload(bvh.nodes8));
-    }
-    // alpha textures (Triangle::m_alphaTex): one record per triangle that has one, named by its leaf entries; texture coordinates
-    // of every triangle for the textured shading kernels
-    std::vector<float4> alphaTris, triUV;
-    if (anyAlpha) {
-        std::vector<uint32_t> recordOf(d->num_triangles, kNoAlpha);
-        for (uint32_t i = 0; i < d->num_triangles; ++i) {
-            const int32_t a = alphaOfMaterial[d->triangles[i].material];
-            if (a < 0) continue;
-            recordOf[i] = (uint32_t)(alphaTris.size() / 2);
-            const slrhip_triangle& t = d->triangles[i];
-            const float* u0 = d->vertices[t.v[0]].texcoord; const float* u1 = d->vertices[t.v[1]].texcoord; const float* u2 = d->vertices[t.v[2]].texcoord;
-            float texIdx; const uint32_t bits = (uint32_t)a; std::memcpy(&texIdx, &bits, 4);
-            alphaTris.push_back(make_float4(u0[0], u0[1], u1[0], u1[1]));
-            alphaTris.push_back(make_float4(u2[0], u2[1], texIdx, 0.0f));
-        }
-        for (LeafTri& lt : bvh.leafTris) lt.alpha = recordOf[lt.tri];
-    }
-    if (numTextures) {
-        triUV.resize((size_t)d->num_triangles * 2);
-        for (uint32_t i = 0; i < d->num_triangles; ++i) {
-            const slrhip_triangle& t = d->triangles[i];
-            const float* u0 = d->vertices[t.v[0]].texcoord; const float* u1 = d->vertices[t.v[1]].texcoord; const float* u2 = d->vertices[t.v[2]].texcoord;
-            triUV[(size_t)i * 2] = make_float4(u0[0], u0[1], u1[0], u1[1]);
-            triUV[(size_t)i * 2 + 1] = make_float4(u2[0], u2[1], 0.0f, 0.0f);
-        }
-    }
-    if (!deviceBuild) HIP_TRY(ctx->leafTris.upload(bvh.leafTris));
-    HIP_TRY(ctx->textures.upload(devTextures));
-    {
-        std::vector<float> texels;
-        if (anyImageTexture) texels.assign(d->texture_texels, d->texture_texels + (size_t)d->num_texture_texels * 3);
-        HIP_TRY(ctx->texTexels.upload(texels));
-    }
-    HIP_TRY(ctx->matTex.upload(matTex));
-    HIP_TRY(ctx->triUV.upload(triUV));
-    HIP_TRY(ctx->alphaTris.upload(alphaTris));
-    if (!deviceBuild) HIP_TRY(ctx->shadeTris.upload(shade));
-    HIP_TRY(ctx->lightTris.upload(lights));
-    HIP_TRY(ctx->instances.upload(devInstances));
-    HIP_TRY(ctx->materials.upload(mats));
-    HIP_TRY(ctx->materialsS.upload(matsS));
-    {
-        std::vector<float> pool;
-        if (spectral && d->spectrum_data) pool.assign(d->spectrum_data, d->spectrum_data + d->num_spectrum_data);
-        // Irregular spectra are evaluated with std::lower_bound per wavelength (SpectrumTypes.h:143-146): on the GPU that is a
-        // chain of dependent loads per component.  A path's wavelengths lie in [360, 830], so for every 1-nm cell the host
-        // stores lower_bound(cell start) as one byte: the device starts there and walks at most a step or two — the same index.
-        for (uint32_t i = 0; i < d->num_spectra && spectral; ++i) {
-            const slrhip_spectrum& sp = d->spectra[i];
-            if (sp.kind != SLRHIP_SPECTRUM_IRREGULAR || sp.num_samples > 255) continue;
-            while (pool.size() % 4) pool.push_back(0.0f);
-            const float* lambdas = d->spectrum_data + sp.data_offset;
-            const uint32_t cells = 472;                                   // 360 + j, j = 0 .. 471
-            std::vector<uint32_t> words(cells / 4, 0u);
-            for (uint32_t j = 0; j < cells; ++j) {
-                const float start = 360.0f + (float)j;
-                const uint32_t lb = (uint32_t)(std::lower_bound(lambdas, lambdas + sp.num_samples, start) - lambdas);
-                words[j / 4] |= lb << (8 * (j % 4));
-            }
-            devSpectra[i].cellOffset = (uint32_t)pool.size();
-            for (uint32_t w : words) { float f; std::memcpy(&f, &w, 4); pool.push_back(f); }
-        }
-        while (pool.size() % 4) pool.push_back(0.0f);          // the shade kernel stages the pool into LDS 16 bytes at a time
-        ctx->scene.numSpectrumData = (uint32_t)pool.size();
-        HIP_TRY(ctx->spectrumPool.upload(pool));
-        ctx->hostSpectrumPool.swap(pool);
-    }
-    HIP_TRY(ctx->spectra.upload(devSpectra));
-    HIP_TRY(ctx->lightPMF.upload(pmf));
-    HIP_TRY(ctx->lightCDF.upload(cdf));
-    {
-        // the tables the shade kernels stage in LDS, packed in the order of ShadeLds' segments (DevScene::shadeTables)
-        const bool fits = mats.size() <= (size_t)kLdsMaterials && lights.size() <= (size_t)kLdsLights &&
-                          (!spectral || (devSpectra.size() <= (size_t)kLdsSpectra && ctx->scene.numSpectrumData <= (uint32_t)kLdsPoolFloats));
-        std::vector<float4> blob;
-        uint32_t seg = 0;
-        for (uint32_t k = 0; k < 6; ++k) ctx->scene.tableEnd[k] = 0;
-        const auto append = [&](const void* src, size_t bytes) {
-            const size_t n = (bytes + 15) / 16, at = blob.size();
-            blob.resize(at + n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-            if (bytes) std::memcpy(blob.data() + at, src, bytes);
-            ctx->scene.tableEnd[seg++] = (uint32_t)blob.size();
-        };
-        if (fits) {
-            if (spectral) {
-                append(matsS.data(), matsS.size() * sizeof(DevMaterialS));
-                append(devSpectra.data(), devSpectra.size() * sizeof(DevSpectrum));
-                append(ctx->hostSpectrumPool.data(), ctx->hostSpectrumPool.size() * sizeof(float));
-            }
-            else append(mats.data(), mats.size() * sizeof(DevMaterial));
-            append(lights.data(), lights.size() * sizeof(LightTri));
-            append(pmf.data(), pmf.size() * sizeof(float));
-            append(cdf.data(), cdf.size() * sizeof(float));
-            while (seg < 6) { ctx->scene.tableEnd[seg] = (uint32_t)blob.size(); ++seg; }
-        }
-        HIP_TRY(ctx->shadeTables.upload(blob));
-        ctx->scene.shadeTables = fits ? ctx->shadeTables.ptr : nullptr;
-    }
-    HIP_TRY(ctx->envTexels.upload(envTexels));
-    HIP_TRY(ctx->envTopPDF.upload(envTopPDF)); HIP_TRY(ctx->envTopCDF.upload(envTopCDF));
-    HIP_TRY(ctx->envRowPDF.upload(envRowPDF)); HIP_TRY(ctx->envRowCDF.upload(envRowCDF));
-    DevScene& sc = ctx->scene;
-    sc.nodes = reinterpret_cast<const float4*>(ctx->nodes.ptr);
-    sc.leafTris = reinterpret_cast<const float4*>(ctx->leafTris.ptr);
-    sc.shadeTris = ctx->shadeTris.ptr;
-    sc.lightTris = ctx->lightTris.ptr;
-    sc.materials = ctx->materials.ptr;
-    sc.materialsS = ctx->materialsS.ptr;
-    sc.spectra = ctx->spectra.ptr;
-    sc.spectrumPool = ctx->spectrumPool.ptr;
-    sc.lightPMF = ctx->lightPMF.ptr;
-    sc.lightCDF = ctx->lightCDF.ptr;
-    sc.textures = ctx->textures.ptr; sc.matTex = ctx->matTex.ptr; sc.triUV = ctx->triUV.ptr; sc.alphaTris = ctx->alphaTris.ptr; sc.texTexels = ctx->texTexels.ptr;
-    sc.numTextures = numTextures;
-    sc.instances = numInstances ? reinterpret_cast<const float4*>(ctx->instances.ptr) : nullptr;
-    sc.numInstances = numInstances;
-    sc.numNodes = numNodes;
-    sc.nodesQ = quant ? reinterpret_cast<const float4*>(ctx->nodesQ.ptr) : nullptr;
-    sc.nodes8 = useWide8 ? reinterpret_cast<const float4*>(ctx->nodes8.ptr) : nullptr;
-    sc.numMaterials = (uint32_t)mats.size();
-    sc.numSpectra = (uint32_t)devSpectra.size();
-    sc.numLights = (uint32_t)lights.size();
-    sc.hasMicrofacet = 0;
-    sc.hasMulti = 0;
-    for (const DevMaterial& dm : mats) {
-        if ((dm.type & 0xFFu) >= SLRHIP_MATERIAL_MICROFACET_METAL) sc.hasMicrofacet = 1;     // GGX, Ward, Ashikhmin: the kernels with the glossy-lobe code
-        if ((dm.type & 0xFFu) == SLRHIP_MATERIAL_MULTI) sc.hasMulti = 1;
-    }
-    sc.lightPow2 = prevPowerOf2(sc.numLights);
-    sc.hasEnv = d->env ? 1u : 0u;
-    sc.aggImportance = lightIntegral;
-    if (d->env) {
-        sc.envWidth = d->env->width; sc.envHeight = d->env->height;
-        sc.envMapWidth = d->env->map_width; sc.envMapHeight = d->env->map_height;
-        sc.envScale = d->env->scale;
-    }
-    {
-        std::vector<uint8_t> cells;
-        std::vector<float> puv, psp;
-        sc.gridWidth = sc.gridHeight = 0;
-        if ((d->env || anyImageTexture) && spectral) {
-            const slrhip_upsampling_tables* t = d->upsampling;
-            cells.assign(t->cells, t->cells + (size_t)t->grid_width * t->grid_height * 8);
-            puv.assign(t->point_uv, t->point_uv + (size_t)t->num_points * 2);
-            psp.assign(t->point_spectrum, t->point_spectrum + (size_t)t->num_points * 95);
-            sc.gridWidth = t->grid_width; sc.gridHeight = t->grid_height;
-        }
-        HIP_TRY(ctx->gridCells.upload(cells)); HIP_TRY(ctx->pointUV.upload(puv)); HIP_TRY(ctx->pointSpectrum.upload(psp));
-        sc.gridCells = ctx->gridCells.ptr; sc.pointUV = ctx->pointUV.ptr; sc.pointSpectrum = ctx->pointSpectrum.ptr;
-    }
-    sc.envTexels = ctx->envTexels.ptr;
-    sc.envTopPDF = ctx->envTopPDF.ptr; sc.envTopCDF = ctx->envTopCDF.ptr;
-    sc.envRowPDF = ctx->envRowPDF.ptr; sc.envRowCDF = ctx->envRowCDF.ptr;
-    sc.camera = cam;
-    // the ray queries' error word: allocated here, so that a query call allocates nothing (and can be captured in a graph)
-    HIP_TRY(ctx->queryError.alloc(1));
-    HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));
-    ctx->bvhDepth = treeDepth;
-    ctx->bvhLeafRefs = leafRefs;
-    ctx->haveScene = true;
-    ctx->haveRender = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    PreparedScene p;
+    std::string err;
+    if (const int rc = prepareScene(*d, ctx->config, &p, &err)) return fail(rc, err);     // the context is untouched so far
+    if (const int rc = commitScene(ctx, *d, p)) return rc;
     ctx->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return SLRHIP_OK;
 }

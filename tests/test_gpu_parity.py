@@ -602,6 +602,69 @@ def test_errors_are_loud(ctx):
         c3.close()
 
 
+def test_refused_upload_leaves_the_context_as_it_was():
+    """An upload refused by a check of the host-side preparation touches nothing: one refused scene per phase (descriptor,
+    materials, instanced tree: a transform and an emitting triangle), each with its message; then the render goes on from where it
+    stopped without render_begin, bit for bit as without the refused uploads, and ray queries and counters still answer for the
+    first scene."""
+    from slr_amd.binding import SlrHipError
+    good = scenes.cornell_instanced(1.0, 8, 4)
+    st = ob.settings(32, 32, seed=7)
+    rng = np.random.default_rng(11)
+    pos = good.vertices["position"]
+    lo, hi = pos.min(0), pos.max(0)
+    cam = np.asarray(good.camera.local_to_world[12:15], np.float32)
+    rays = np.zeros((256, 8), np.float32)
+    rays[:, 0:3] = cam
+    rays[:, 4:7] = lo + (hi - lo) * rng.uniform(0.05, 0.95, (256, 3)) - cam
+    rays[:, 7] = np.inf
+
+    def refused(mutate, message):
+        bad = scenes.cornell_instanced(1.0, 8, 4)
+        mutate(bad)
+        with pytest.raises(SlrHipError, match=message):
+            c.upload_scene(bad)
+
+    def out_of_range_vertex(sc):
+        sc.triangles["v"][0][1] = len(sc.vertices) + 3
+
+    def out_of_range_spectrum(sc):
+        sc.materials["spectrum"][0][0] = len(sc.spectra) + 5
+
+    def projective_instance(sc):
+        sc.instances["local_to_world"][0][3] = 0.25
+
+    def emitting_instance(sc):
+        light = int(np.nonzero(sc.materials["emittance"] >= 0)[0][0])
+        sc.triangles["material"][int(sc.instances["first_triangle"][0])] = light
+
+    c = Context()
+    try:
+        c.upload_scene(good)
+        nodes = c.counters().bvh_nodes
+        hits = c.intersect_rays(rays)
+        assert (hits[:, 0].view(np.uint32) != abi.MISS).any()
+        c.render_begin(st)
+        c.render(0, 4)
+        first = c.read_framebuffer()
+        refused(out_of_range_vertex, r"\(1\): slrhip_upload_scene: triangle index out of range$")
+        refused(out_of_range_spectrum, r"\(1\): slrhip_upload_scene: spectrum index out of range$")
+        refused(projective_instance, r"\(1\): slrhip_upload_scene: instance transforms must be affine \(bottom row 0 0 0 1\)$")
+        refused(emitting_instance, r"\(5\): slrhip_upload_scene: instanced triangles must not emit$")
+        c.render(4, 4)                                                  # no render_begin: the render state survived
+        after = c.read_framebuffer()
+        assert after.sum() > first.sum()
+        assert_bit_equal(c.intersect_rays(rays), hits, "hits after the refused uploads")
+        assert c.counters().bvh_nodes == nodes
+        c.render_begin(st)                                              # the same passes with no refused upload in between
+        c.render(0, 4)
+        assert_bit_equal(c.read_framebuffer(), first, "first 4 passes")
+        c.render(4, 4)
+        assert_bit_equal(after, c.read_framebuffer(), "8 passes across the refused uploads")
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("name", ["rgb_oren_nayar"])
 def test_oren_nayar_matches_reference_golden(ctx, name):
     """Oren-Nayar uses no libm beyond the cosine sample: expected bit-exact like Lambert."""
