@@ -386,7 +386,13 @@ int slrhip_destroy(slrhip_ctx* ctx);
 int slrhip_upload_scene(slrhip_ctx* ctx, const slrhip_scene_desc* scene);
 
 /* Replaces: sensor->init(W,H) PathTracingRenderer.cpp:67 (ImageSensor.cpp:35-51) plus the
- * per-render setup :33-61.  Clears the accumulation state of this context's shard.        */
+ * per-render setup :33-61.  Clears the accumulation state of this context's shard.
+ * Failure: a call refused by a check on its arguments (image size, shard, too many path
+ * slots) leaves the context exactly as it was: the previous render state stays usable.  A
+ * call that fails once it has begun to allocate (a HIP error) leaves the context with no
+ * render state: slrhip_render and the resolve / reduce / read calls return
+ * SLRHIP_ERR_NO_SCENE and the counters report no samples or rays until a render_begin
+ * succeeds, while the scene and the ray queries stay usable.                               */
 int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* settings, slrhip_shard shard);
 
 /* Replaces: the pass loop PathTracingRenderer.cpp:72-81 for passes

@@ -31,6 +31,17 @@ int slrhip_bsdf_queries(slrhip_ctx* ctx, uint32_t material, uint32_t n, const fl
 int slrhip_debug_work_distribution(uint32_t num_pixels, uint32_t num_slots, uint32_t num_passes, uint32_t run_length,
                                    uint32_t* counts, uint32_t* queue_lengths);
 
+/* The render plan (slr_amd/csrc/render_plan.h), evaluated on the HOST with the very functions slrhip_render_begin and slrhip_render
+ * call: a frame of width x height, shard shard_index of shard_count, slrhip_config::stripes (0 = automatic) and mode, then a call
+ * of `num_passes` passes with `budget_bytes` for the result window.  plan[0..3] receive the shard's pixel count, the stripes, the
+ * path slots and the passes per window; *num_windows the number of windows of the call; windows[2 k], windows[2 k + 1] the pass
+ * count and the run length of window k, for the first `max_windows` windows.  If `pixels` is not NULL it receives the shard's pixel
+ * list (x | y << 16, plan[0] entries; `max_pixels` is its capacity).  No GPU is touched.  Returns SLRHIP_OK, or what
+ * slrhip_render_begin returns for the same frame and shard, with its message.                                                  */
+int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint32_t stripes, int32_t mode,
+                             uint32_t num_passes, uint64_t budget_bytes, uint32_t* plan, uint32_t* windows, uint32_t max_windows,
+                             uint32_t* num_windows, uint32_t* pixels, uint32_t max_pixels);
+
 #ifdef __cplusplus
 }
 #endif

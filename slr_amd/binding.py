@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(CSRC, "libslrhip.so")
 EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_render_begin", "slrhip_render",
            "slrhip_resolve_framebuffer", "slrhip_reduce_framebuffer", "slrhip_read_framebuffer", "slrhip_synchronize", "slrhip_get_counters",
            "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_intersect_rays", "slrhip_test_visibility",
-           "slrhip_query_status", "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_query_status", "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -122,8 +122,8 @@ class Context:
         _check(self.lib, self.lib.slrhip_upload_scene(self.handle, C.byref(desc)), "slrhip_upload_scene")
 
     def render_begin(self, settings, shard=(0, 1)):
-        self.settings = settings
         _check(self.lib, self.lib.slrhip_render_begin(self.handle, C.byref(settings), abi.Shard(*shard)), "slrhip_render_begin")
+        self.settings = settings          # a refused call leaves the previous render state, and its frame size, in place
 
     def render(self, spp_begin, spp_count, stream=None):
         _check(self.lib, self.lib.slrhip_render(self.handle, spp_begin, spp_count, stream), "slrhip_render")

@@ -1,0 +1,131 @@
+// render_plan.cpp — the arithmetic of the render set-up (render_plan.h): pure functions of their arguments.
+#include "render_plan.h"
+
+#include <algorithm>
+
+#include "../../include/slrhip.h"
+#include "pt_kernels.h"
+
+namespace slrhip {
+
+namespace {
+
+// integers t in [begin, end) with t % count == index
+uint64_t countCongruent(uint64_t begin, uint64_t end, uint32_t index, uint32_t count) {
+    const auto below = [&](uint64_t n) { return n > index ? (n - index + count - 1) / count : 0; };      // those in [0, n)
+    return below(end) - below(begin);
+}
+
+int refuse(std::string* err, const char* what) {
+    *err = std::string("slrhip_render_begin: ") + what;
+    return SLRHIP_ERR_INVALID_ARGUMENT;
+}
+
+} // namespace
+
+int planFrame(int32_t width, int32_t height, uint32_t shardIndex, uint32_t shardCount, uint32_t configStripes, bool spectral,
+              long autoStripesOverride, int pairs, FramePlan* out, std::string* err) {
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return refuse(err, "image size out of range");
+    if (shardCount == 0 || shardIndex >= shardCount) return refuse(err, "bad shard");
+    FramePlan p;
+    p.width = (uint32_t)width; p.height = (uint32_t)height;
+    p.shardIndex = shardIndex; p.shardCount = shardCount;
+    p.spectral = spectral;
+    // the shard owns the 8x8 tiles t with t % count == index (ImageSensor.cpp:43-44); only the last column and row are cut
+    const uint32_t tilesX = (p.width + 7) >> 3, tilesY = (p.height + 7) >> 3;
+    const uint32_t lastW = p.width - 8 * (tilesX - 1), lastH = p.height - 8 * (tilesY - 1);
+    uint64_t numPixels = 0;
+    for (uint32_t ty = 0; ty < tilesY; ++ty) {
+        const uint64_t rowBegin = (uint64_t)ty * tilesX, rowEnd = rowBegin + tilesX;
+        uint64_t columns = 8 * countCongruent(rowBegin, rowEnd, shardIndex, shardCount);
+        if ((rowEnd - 1) % shardCount == shardIndex) columns -= 8 - lastW;
+        numPixels += columns * (ty + 1 == tilesY ? lastH : 8u);
+    }
+    uint32_t stripes = configStripes;
+    if (stripes == 0) {
+        // Paths in flight: throughput keeps rising with the slot count (longer launches amortise the per-wave tail of the
+        // traversal kernel: 807 / 1146 / 1267 Msamples/s at 0.9 / 3.7 / 7.4 M slots on the 1280x720 Cornell scene in round 1),
+        // at ~200 B of HBM per slot; the per-pixel sample pool keeps the stripes of a pixel finishing together, so fewer, fuller
+        // iterations keep paying.  The count is a power of two (the stripes of a pixel then fill whole lane groups of the shade
+        // workgroup, PathBuffers): the smallest that reaches ~22 M slots in RGB mode, ~7.4 M in spectral mode (492 B per slot; its
+        // shade kernel is latency-bound, not launch-bound), at most 64 (the width of the pool's mask; also the best count measured
+        // for the eighth of the image a rank owns at N = 8).  Measured with the fused shade kernel, 16 vs 32 stripes at 1280x720
+        // (profiles/r03_e_*): Cornell 2 709 vs 2 719, environment light 5 630 vs 6 061, 10 M-triangle grid 1 954 vs 1 981 Msamples/s.
+        const uint32_t target = spectral ? 7372800u : 22118400u;
+        stripes = 1u;
+        while (stripes < 64u && numPixels * stripes < target) stripes *= 2u;
+        if (numPixels == 0) stripes = 1u;
+        if (autoStripesOverride >= 1 && autoStripesOverride <= 64) stripes = (uint32_t)autoStripesOverride;      // measurement: force the automatic choice
+    }
+    // Slots are paths in flight, not places in the image (pt_kernels.h): `stripes` only sizes their number
+    const uint64_t slotCapacity = std::max<uint64_t>((numPixels * stripes + 255u) / 256u, 1) * 256u;
+    if (slotCapacity > 0x7FFFFFFFull) return refuse(err, "too many path slots");
+    p.numPixels = (uint32_t)numPixels;
+    p.stripes = stripes;
+    p.slotCapacity = (size_t)slotCapacity;
+    p.numSlots = numPixels ? (uint32_t)slotCapacity : 0u;
+    // queue regions: slot block b appends to region b % kShards, so a region holds at most ceil(numBlocks / kShards) blocks
+    p.numBlocks = (uint32_t)(slotCapacity / 256u);
+    p.shardCapacity = ((p.numBlocks + kShards - 1) / kShards) * 256;
+    // SLRHIP_PAIRS (bit 0: ray origin + direction, bit 1: the path's radiance sum + its compensation, bit 2: sample header + RNG
+    // state): the two records of a pair interleaved in one array, one 32-byte sector per slot (PathBuffers::rayStride / spStride)
+    p.rayStride = (pairs & 1) ? 2u : 1u; p.spStride = (pairs & 2) ? 2u : 1u; p.hdrStride = (pairs & 4) ? 2u : 1u;
+    *out = p;
+    return SLRHIP_OK;
+}
+
+std::vector<uint32_t> shardPixels(const FramePlan& p) {
+    if (p.numPixels == 0) return {0xFFFFFFFFu};        // an empty shard keeps the buffers valid
+    // tiles in shard order, row-major inside each tile, so 64 consecutive slots (one wavefront) are one 8x8 tile
+    const uint32_t tilesX = (p.width + 7) >> 3, tilesY = (p.height + 7) >> 3;
+    std::vector<uint32_t> pixels;
+    pixels.reserve(p.numPixels);
+    for (uint32_t t = p.shardIndex; t < tilesX * tilesY; t += p.shardCount) {
+        const uint32_t tx = t % tilesX, ty = t / tilesX;
+        for (uint32_t ly = 0; ly < 8; ++ly)
+            for (uint32_t lx = 0; lx < 8; ++lx) {
+                const uint32_t x = tx * 8 + lx, y = ty * 8 + ly;
+                if (x < p.width && y < p.height) pixels.push_back(x | (y << 16));
+            }
+    }
+    return pixels;
+}
+
+// The result window (PathBuffers::results) holds one entry per pixel and pass: 16 B (RGB) / 64 B (spectral).  A call of more passes
+// than fit the budget or than 2^32 samples is rendered as several windows, one after the other; the sensor adds in pass order
+// either way, so the image does not depend on the split.
+uint32_t planWindows(uint32_t numPixels, bool spectral, uint32_t sppCount, uint64_t budgetBytes) {
+    const uint64_t entryBytes = (spectral ? 4u : 1u) * 16u;
+    const uint64_t maxPasses = std::max<uint64_t>(1, std::min<uint64_t>(budgetBytes / ((uint64_t)numPixels * entryBytes), 0xF0000000ull / numPixels));      // (run ids + one round of waves stay inside 32 bits)
+    // whole runs (RenderParams::runLength passes of a pixel in a row, pt_kernels.h) wherever the call is long enough: a window of
+    // an odd number of passes would fall back to runs of one pass and lose the coherence of a wave's slots
+    uint32_t window = (uint32_t)std::min<uint64_t>(maxPasses, std::max<uint32_t>(sppCount, 1u));
+    if (window >= kDefaultRunLength) window -= window % kDefaultRunLength;
+    return window;
+}
+
+WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthOverride) {
+    WindowPlan w;
+    w.workItems = numPixels * sppCount;                           // < 2^32: planWindows
+    // passes per run (pt_kernels.h WorkItem): the largest power-of-two fraction of the default that divides the window's pass count
+    w.runLength = runLengthOverride ? runLengthOverride : kDefaultRunLength;
+    while (w.runLength > 1 && (sppCount % w.runLength) != 0) w.runLength /= 2;
+    if (sppCount && sppCount % w.runLength) w.runLength = 1;
+    w.numRuns = numPixels * (sppCount / std::max(w.runLength, 1u));
+    return w;
+}
+
+// The end of the window (pt_tail_kernels.h): once at most tailSlots slots are alive the traversal kernel raises the tail-mode word
+// instead of tracing, the rest of the block of iterations is no-ops, and the tail kernel finishes every remaining path and sample
+// in one launch.  The image does not depend on who finishes a sample (the sensor adds in pass order).  On with the automatic slot
+// count (slrhip_config::stripes = 0) and on request (SLRHIP_FLAG_TAIL_KERNEL, SLRHIP_TAIL_SLOTS=n); a caller who fixes the slot
+// count gets the pure wavefront schedule unless he asks (the parity tests compare the two).  Never for more than numSlots /
+// divisor, an eighth of the slots (the wavefront kernels are the efficient way to advance many paths) and not in the counting
+// build (its per-ray figures come from the wavefront kernels).  SLRHIP_TAIL_SLOTS=0 turns it off.
+uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail, bool available) {
+    if (!(asked || envTail > 0) || envTail == 0 || !available) return 0u;
+    const uint32_t bound = envTail > 0 ? (uint32_t)std::min<long>(envTail, 0x7FFFFFFFL) : kDefaultTailSlots;
+    return std::min(bound, numSlots / divisor);
+}
+
+} // namespace slrhip

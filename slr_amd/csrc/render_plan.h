@@ -1,0 +1,56 @@
+// render_plan.h — the host half of the render set-up: every decision of slrhip_render_begin / slrhip_render that is integer
+// arithmetic (the shard's pixel list, the slot count, the result windows, their run lengths, the tail-kernel bound), with no device
+// call, no context state and no environment variable: every override comes in as an argument (see render_plan.cpp).
+// slrhip_api.hip allocates and launches from the result; slrhip_debug_render_plan (include/slrhip_debug.h) shows it to the tests.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace slrhip {
+
+const uint32_t kDefaultRunLength = 64;         // SLRHIP_RUN_LENGTH: passes of a pixel a wave takes in a row (pt_kernels.h WorkItem; measured: DESIGN.md)
+const uint32_t kDefaultTailSlots = 1u << 18;   // SLRHIP_TAIL_SLOTS: measured on the headline frame and its N = 8 shard
+
+struct FramePlan {
+    uint32_t width = 0, height = 0;
+    uint32_t shardIndex = 0, shardCount = 1;
+    bool spectral = false;
+    uint32_t numPixels = 0;                    // pixels of this shard; 0 = the shard owns no tile
+    uint32_t stripes = 1;                      // slots per pixel: the caller's, or the automatic choice
+    uint32_t numSlots = 0;                     // paths in flight, a multiple of 256; 0 for an empty shard
+    size_t slotCapacity = 256;                 // elements of the per-slot arrays: numSlots, or one block for an empty shard
+    uint32_t numBlocks = 1;                    // slotCapacity / 256
+    uint32_t shardCapacity = 256;              // entries per queue region = ceil(numBlocks / kShards) * 256
+    uint32_t rayStride = 1, spStride = 1, hdrStride = 1;      // PathBuffers: 2 = the pair shares one array
+};
+
+// The checks of slrhip_render_begin on the frame and the shard, then the sizes.  `configStripes` is slrhip_config::stripes (0 =
+// automatic), `autoStripesOverride` replaces the automatic choice when it is in 1 .. 64, `pairs` is the SLRHIP_PAIRS mask.
+// Returns SLRHIP_OK, or SLRHIP_ERR_INVALID_ARGUMENT with the message in *err.  Costs one step per row of tiles: the shard's
+// pixels are counted, not listed, so a frame that will be refused is refused before anything of its size exists.
+int planFrame(int32_t width, int32_t height, uint32_t shardIndex, uint32_t shardCount, uint32_t configStripes, bool spectral,
+              long autoStripesOverride, int pairs, FramePlan* out, std::string* err);
+
+// The shard's pixels as x | y << 16 (plan.numPixels entries), or the single placeholder 0xFFFFFFFF for an empty shard.
+std::vector<uint32_t> shardPixels(const FramePlan& plan);
+
+// Passes per result window of a call of `sppCount` passes over `numPixels` (> 0) pixels with `budgetBytes` for the window.
+uint32_t planWindows(uint32_t numPixels, bool spectral, uint32_t sppCount, uint64_t budgetBytes);
+
+struct WindowPlan {
+    uint32_t workItems;                        // numPixels x sppCount
+    uint32_t runLength;                        // passes per run (divides sppCount)
+    uint32_t numRuns;                          // numPixels x sppCount / runLength
+};
+// One window of `sppCount` passes; `runLengthOverride` (0 = none) replaces kDefaultRunLength as the longest run.
+WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthOverride);
+
+// RenderParams::tailSlots of a window: 0 = the tail kernel stays off.  `asked`: the caller's flag or the automatic slot count;
+// `envTail`: SLRHIP_TAIL_SLOTS (-1 = unset, 0 = off, n = the bound); `available`: the tail kernel exists for this scene and the
+// build does not count traversal steps; never more than numSlots / `divisor` (SLR_TAIL_DIVISOR of slrhip_api.hip).
+uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail, bool available);
+
+} // namespace slrhip

@@ -1,8 +1,9 @@
 // slrhip_api.hip — the C ABI of include/slrhip.h over the HIP kernels.
 //
 // A scene is checked and flattened on the host by scene_prep.cpp, then committed here: the device tree build (if chosen),
-// the uploads, the DevScene.  PathTracingRenderer::render's set-up (Renderers/PathTracingRenderer.cpp:27-70) lives here too:
-// render_begin sizes the path state, render drives the wavefront iterations.
+// the uploads, the DevScene.  PathTracingRenderer::render's set-up (Renderers/PathTracingRenderer.cpp:27-70) is planned on the
+// host by render_plan.cpp (pixel list, slot count, result windows, run lengths); render_begin allocates and binds the path state
+// from that plan in one commit, and renderWindow drives the wavefront iterations of a window through one launch loop.
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -19,6 +20,7 @@
 #include "../../include/slrhip.h"
 #include "bvh.h"
 #include "pt_kernels.h"
+#include "render_plan.h"
 #include "scene_prep.h"
 
 using namespace slrhip;
@@ -27,11 +29,15 @@ namespace {
 
 const int kDefaultPairs = 1;                   // SLRHIP_PAIRS: the ray pair pays, the radiance-sum pair does not
 const uint32_t kStatusWords = 8;               // PathBuffers::activeSlots .. tailWords: one small array, read back in one copy
-const uint32_t kDefaultRunLength = 64;         // SLRHIP_RUN_LENGTH: passes of a pixel a wave takes in a row (pt_kernels.h WorkItem; measured: DESIGN.md)
+enum StatusWord : uint32_t {                   // its words (bindBuffers points PathBuffers at them)
+    S_LIVE = 0, S_ERROR = 1,                   // live slots; device error word
+    S_TAIL_IDLED = 2, S_TAIL_MODE = 3,         // slots the tail kernel left idle; 1 + parity once the traversal kernel has handed over to it
+    S_TAIL_LENGTH = 4, S_TAIL_CURSOR = 5,      // tail list length / cursor
+    S_WINDOW_SAMPLES = 6                       // samples the queues handed out in the window
+};
 #ifndef SLR_TAIL_DIVISOR
 #define SLR_TAIL_DIVISOR 8u      // the tail kernel never takes more than this fraction of the slots (1u in a variant build: the tail kernel as the whole renderer, measured in DESIGN.md)
 #endif
-const uint32_t kDefaultTailSlots = 1u << 18;   // SLRHIP_TAIL_SLOTS: measured on the headline frame and its N = 8 shard
 
 thread_local std::string g_lastError;
 
@@ -293,6 +299,228 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     return SLRHIP_OK;
 }
 
+// Overrides of the render plan, each read once per process (the first two by measurement builds only: tuningEnv).
+static long autoStripesOverride() { static const long v = [] { const char* e = tuningEnv("SLRHIP_AUTO_STRIPES"); return e ? atol(e) : 0L; }(); return v; }
+static int pairsMask() { static const int v = [] { const char* e = tuningEnv("SLRHIP_PAIRS"); return e ? atoi(e) : kDefaultPairs; }(); return v; }
+static uint32_t runLengthOverride() {
+    static const uint32_t v = [] { const char* e = getenv("SLRHIP_RUN_LENGTH"); const long n = e ? atol(e) : 0L; return n >= 1 && n <= 4096 ? (uint32_t)n : 0u; }();
+    return v;
+}
+
+static size_t frameFloats(const RenderParams& rp) { return (size_t)rp.imageWidth * rp.imageHeight * (rp.spectral ? 16 : 3); }
+
+// Points a zero-initialised PathBuffers at the context's render arrays and assigns it to ctx->buffers in one go.
+static void bindBuffers(slrhip_ctx* ctx, const FramePlan& plan) {
+    PathBuffers pb{};
+    // per-slot path state; the second record of a pair (stride 2) is element 1 of the first one's array
+    pb.rayStride = plan.rayStride; pb.spStride = plan.spStride; pb.hdrStride = plan.hdrStride;
+    pb.rayOrg = ctx->rayOrg.ptr; pb.rayDir = plan.rayStride == 2 ? ctx->rayOrg.ptr + 1 : ctx->rayDir.ptr;
+    pb.spR = ctx->spR.ptr; pb.spC = plan.spStride == 2 ? ctx->spR.ptr + 1 : ctx->spC.ptr;
+    pb.hdr = ctx->hdr.ptr; pb.rng = plan.hdrStride == 2 ? ctx->hdr.ptr + 1 : ctx->rng.ptr;
+    pb.hit = ctx->hit.ptr; pb.hitInstance = ctx->scene.instances ? ctx->hitInstance.ptr : nullptr;
+    pb.alpha = ctx->alpha.ptr; pb.pdfPrev = plan.spectral ? ctx->pdfPrev.ptr : nullptr;
+    pb.nee = ctx->nee.ptr; pb.shadowDir = ctx->shadowDir.ptr; pb.visible = ctx->visible.ptr; pb.flags = ctx->flags.ptr;
+    // result window (slrhip_render sizes it), sensor, pixel list
+    pb.results = ctx->results.ptr; pb.fbSum = ctx->fbSum.ptr; pb.fbComp = ctx->fbComp.ptr; pb.pixelXY = ctx->pixelXY.ptr;
+    // queues and counters
+    pb.cursor = ctx->cursor.ptr; pb.shadowQueue = ctx->shadowQueue.ptr; pb.tailList = ctx->tailList.ptr; pb.queueCount = ctx->queueCount.ptr;
+    pb.idleShards = ctx->idleShards.ptr; pb.blockDead = ctx->blockDead.ptr; pb.totals = ctx->totals.ptr;
+    // the status words
+    uint32_t* const status = ctx->activeSlots.ptr;
+    pb.activeSlots = status + S_LIVE; pb.errorWord = status + S_ERROR; pb.windowSamples = status + S_WINDOW_SAMPLES;
+    pb.tailIdled = status + S_TAIL_IDLED; pb.tailMode = status + S_TAIL_MODE; pb.tailWords = status + S_TAIL_LENGTH;
+    ctx->buffers = pb;
+}
+
+// Copies the first `count` status words to the host and waits for them.
+static hipError_t readStatus(slrhip_ctx* ctx, uint32_t* words, uint32_t count, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(words, ctx->activeSlots.ptr, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
+// The window is complete only if the queues handed out exactly one sample per pixel and pass: the device's own count
+// (k_count_samples over the queues' cursors) against the host's arithmetic.  A lost or repeated sample would leave a stale
+// or overwritten entry in the result window — never silent.
+static int checkWindow(slrhip_ctx* ctx, hipStream_t s) {
+    uint32_t words[kStatusWords] = {};
+    HIP_TRY(readStatus(ctx, words, kStatusWords, s));
+    if (words[S_ERROR]) return deviceError(words[S_ERROR]);
+    if (words[S_WINDOW_SAMPLES] != ctx->params.workItems)
+        return fail(SLRHIP_ERR_HIP, "slrhip_render: the work queues handed out " + std::to_string(words[S_WINDOW_SAMPLES]) + " samples for a window of " +
+                                        std::to_string(ctx->params.workItems) + " (internal error)");
+    return SLRHIP_OK;
+}
+
+// Tail mode seen in the status words: list the live slots, finish them, read the words again (live slots must be 0 then).
+// `status` are the loop's words (S_LIVE .. S_TAIL_MODE), updated here.
+static int runTail(slrhip_ctx* ctx, uint32_t* status, hipStream_t s, bool timed) {
+    struct Timer {
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        ~Timer() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
+    } timer;
+    if (timed) { HIP_TRY(hipEventCreate(&timer.t0)); HIP_TRY(hipEventCreate(&timer.t1)); HIP_TRY(hipEventRecord(timer.t0, s)); }
+    launchTail(ctx->scene, ctx->buffers, ctx->params, status[S_LIVE], ctx->numCUs, s);
+    if (timed) HIP_TRY(hipEventRecord(timer.t1, s));
+    HIP_TRY(hipGetLastError());
+    const uint32_t liveBefore = status[S_LIVE];
+    uint32_t words[S_TAIL_CURSOR + 1] = {};
+    HIP_TRY(readStatus(ctx, words, S_TAIL_CURSOR + 1, s));
+    std::memcpy(status, words, (S_TAIL_MODE + 1) * sizeof(uint32_t));
+    if (timed) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, timer.t0, timer.t1));
+        ctx->profMs[SLRHIP_KERNEL_TAIL] += ms;
+        ++ctx->profLaunches[SLRHIP_KERNEL_TAIL];
+    }
+    if (status[S_ERROR]) return deviceError(status[S_ERROR]);
+    if (words[S_TAIL_IDLED] != words[S_TAIL_LENGTH])
+        return fail(SLRHIP_ERR_HIP, "slrhip_render: the tail kernel left " + std::to_string(words[S_TAIL_LENGTH] - words[S_TAIL_IDLED]) + " of " +
+                                        std::to_string(words[S_TAIL_LENGTH]) + " listed slots live (live count before: " + std::to_string(liveBefore) +
+                                        ", cursor " + std::to_string(words[S_TAIL_CURSOR]) + "; internal error)");
+    // every listed slot ended idle and the wavefront kernels are off (tail mode): nothing is live any more
+    HIP_TRY(hipMemsetAsync(ctx->activeSlots.ptr + S_LIVE, 0, sizeof(uint32_t), s));
+    status[S_LIVE] = 0;
+    return SLRHIP_OK;
+}
+
+// One wavefront iteration = k_shade (advance every live path by one vertex; finish and restart the paths that end) then
+// k_trace_ws (the extension and shadow rays that left).  Each check of the live-slot word costs one small copy + stream
+// sync; 16 iterations between checks keeps it < 1 %.
+const int kCheckEvery = 16;
+const int kEventsPerIteration = 3;    // SLRHIP_FLAG_TIME_KERNELS: before shade, after shade, after trace
+
+// One block of kCheckEvery iterations as plain launches on `s`, with the context's timing events around each kernel if `timed`.
+static hipError_t launchBlock(slrhip_ctx* ctx, uint32_t traceBlocks, bool timed, hipStream_t s) {
+    const bool count = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < kCheckEvery; ++k) {
+        const uint32_t parity = (uint32_t)(k & 1);
+        hipEvent_t* ev = timed ? &ctx->events[(size_t)k * kEventsPerIteration] : nullptr;
+        if (ev && e == hipSuccess) e = hipEventRecord(ev[0], s);
+        launchShade(ctx->scene, ctx->buffers, ctx->params, parity, s);
+        if (ev && e == hipSuccess) e = hipEventRecord(ev[1], s);
+        launchTraceWs(ctx->scene, ctx->buffers, ctx->params, parity, traceBlocks, count, s);
+        if (ev && e == hipSuccess) e = hipEventRecord(ev[2], s);
+    }
+    return e;
+}
+
+// SLRHIP_ITER_LOG=path (with SLRHIP_FLAG_TIME_KERNELS): per-iteration kernel times of a window, one line per iteration
+// "iteration shade_ms trace_ms live_slots_at_block_end" — how the drain of a render's last paths was measured
+struct IterationTimes { float ms[2]; uint32_t live; };
+static void writeIterationLog(const char* path, const RenderParams& rp, const std::vector<IterationTimes>& log) {
+    FILE* f = log.empty() ? nullptr : fopen(path, "a");
+    if (!f) return;
+    fprintf(f, "# render: %u slots, %u passes from %u\n", rp.numSlots, rp.sppCount, rp.sppBegin);
+    for (size_t i = 0; i < log.size(); ++i) fprintf(f, "%zu %.4f %.4f %u\n", i, log[i].ms[0], log[i].ms[1], log[i].live);
+    fclose(f);
+}
+
+// The event times of the block just finished: into the profile, and into the iteration log if there is one.
+static int readBlockTimes(slrhip_ctx* ctx, uint32_t live, std::vector<IterationTimes>* log) {
+    static const int cls[2] = {SLRHIP_KERNEL_SHADE, SLRHIP_KERNEL_TRACE};
+    for (int k = 0; k < kCheckEvery; ++k) {
+        hipEvent_t* ev = &ctx->events[(size_t)k * kEventsPerIteration];
+        IterationTimes t = {{0.0f, 0.0f}, live};
+        for (int j = 0; j < 2; ++j) {
+            HIP_TRY(hipEventElapsedTime(&t.ms[j], ev[j], ev[j + 1]));
+            ctx->profMs[cls[j]] += t.ms[j];
+            ++ctx->profLaunches[cls[j]];
+        }
+        if (log) log->push_back(t);
+    }
+    return SLRHIP_OK;
+}
+
+// hipGraph of one block of iterations: released on every path out of renderWindow
+struct BlockGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    ~BlockGraph() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
+};
+
+// One window of passes [sppBegin, sppBegin + sppCount): every sample of the window rendered into the result window, then folded
+// into the sensor in pass order.  slrhip_render sizes the windows.
+static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, hipStream_t stream) {
+    RenderParams& rp = ctx->params;
+    const WindowPlan window = planWindow(rp.numPixels, sppCount, runLengthOverride());
+    rp.sppBegin = sppBegin; rp.sppCount = sppCount;
+    rp.workItems = window.workItems; rp.runLength = window.runLength; rp.numRuns = window.numRuns;
+    // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
+    // it is asked for zero passes
+    launchResetSlots(ctx->buffers, rp, ctx->firstRenderCall, stream);
+    ctx->firstRenderCall = false;
+    if (sppCount == 0) return SLRHIP_OK;
+    // persistent traversal workgroups of the wave-specialised kernel (pt_trace_ws.hip): a fixed number per CU
+    const uint32_t traceBlocks = (uint32_t)ctx->numCUs * (uint32_t)traceWsBlocksPerCU(ctx->scene.nodesQ != nullptr);
+
+    // the end of the window: the tail kernel's bound (render_plan.cpp, tailSlots)
+    static const long envTail = [] { const char* e = getenv("SLRHIP_TAIL_SLOTS"); return e ? atol(e) : -1L; }();
+    const bool counting = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
+    rp.tailSlots = tailSlots(rp.numSlots, SLR_TAIL_DIVISOR, (ctx->config.flags & SLRHIP_FLAG_TAIL_KERNEL) != 0 || ctx->config.stripes == 0, envTail,
+                             tailKernelAvailable(ctx->scene, rp.spectral != 0) && !counting);
+
+    const bool timeKernels = (ctx->config.flags & SLRHIP_FLAG_TIME_KERNELS) != 0;
+    if (timeKernels && ctx->events.empty()) {
+        ctx->events.resize((size_t)kCheckEvery * kEventsPerIteration);
+        for (hipEvent_t& e : ctx->events) HIP_TRY(hipEventCreate(&e));
+    }
+    static const char* iterLogPath = getenv("SLRHIP_ITER_LOG");
+    std::vector<IterationTimes> iterLog;
+
+    // The block of kCheckEvery iterations is the same sequence of launches every time (the parity alternates inside it and is
+    // back to 0 at its end), so it is captured ONCE per window into a hipGraph and replayed: one submission per block instead
+    // of 32 launches with their dispatch gaps — what is left of the cost of the nearly empty iterations at the end of a
+    // render.  Capture needs a real stream, so the work runs on the context's own stream, ordered after the caller's by an
+    // event; render() returns only after that stream is idle, which orders the caller's later work after it.  Not when the
+    // kernels are timed (the events go between the launches) and not for small frames.
+    static const bool noGraph = [] { const char* e = getenv("SLRHIP_GRAPH"); return e && std::string(e) == "0"; }();
+    BlockGraph block;
+    hipStream_t s = stream;          // the stream of everything below
+    if (!timeKernels && !noGraph && rp.numSlots >= (1u << 18)) {
+        if (!ctx->workStream) {
+            HIP_TRY(hipStreamCreateWithFlags(&ctx->workStream, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&ctx->userReady, hipEventDisableTiming));
+        }
+        s = ctx->workStream;
+        HIP_TRY(hipEventRecord(ctx->userReady, stream));          // the reset kernel above and whatever the caller queued before
+        HIP_TRY(hipStreamWaitEvent(s, ctx->userReady, 0));
+        HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        (void)launchBlock(ctx, traceBlocks, false, s);
+        hipError_t ce = hipStreamEndCapture(s, &block.graph);
+        if (ce == hipSuccess) ce = hipGraphInstantiate(&block.exec, block.graph, nullptr, nullptr, 0);
+        if (ce != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: hipGraph capture failed: ") + hipGetErrorString(ce));
+    }
+
+    const uint64_t maxIterations = ((uint64_t)rp.workItems / rp.numSlots + 2) * 128 + 1024;   // paths are <= 100 vertices long
+    uint64_t it = 0;
+    uint32_t status[S_TAIL_MODE + 1] = {rp.numSlots, 0u, 0u, 0u};
+    while (status[S_LIVE] > 0) {
+        hipError_t e = block.exec ? hipGraphLaunch(block.exec, s) : launchBlock(ctx, traceBlocks, timeKernels, s);
+        if (e == hipSuccess && !block.exec) e = hipGetLastError();          // a failed launch surfaces here, not at the end of the render
+        if (e == hipSuccess) e = readStatus(ctx, status, S_TAIL_MODE + 1, s);
+        if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: ") + hipGetErrorString(e));
+        it += kCheckEvery;
+        if (status[S_ERROR]) return deviceError(status[S_ERROR]);
+        if (timeKernels) {
+            const int rc = readBlockTimes(ctx, status[S_LIVE], iterLogPath ? &iterLog : nullptr);
+            if (rc != SLRHIP_OK) return rc;
+        }
+        if (status[S_TAIL_MODE] && status[S_LIVE]) {
+            const int rc = runTail(ctx, status, s, timeKernels);
+            if (rc != SLRHIP_OK) return rc;
+        }
+        if (it > maxIterations) return fail(SLRHIP_ERR_HIP, "slrhip_render: iteration bound exceeded (internal error)");
+    }
+    ctx->iterations += it;
+    launchCountSamples(ctx->buffers, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
+    launchFold(ctx->buffers, rp, s);               // sensor->add, in pass order
+    HIP_TRY(hipGetLastError());
+    const int rc = checkWindow(ctx, s);
+    if (rc == SLRHIP_OK && iterLogPath) writeIterationLog(iterLogPath, rp, iterLog);
+    return rc;
+}
+
 extern "C" {
 
 const char* slrhip_last_error_string(void) { return g_lastError.c_str(); }
@@ -346,71 +574,33 @@ int slrhip_upload_scene(slrhip_ctx* ctx, const slrhip_scene_desc* d) {
 int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhip_shard shard) {
     if (!ctx || !st) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_begin: null argument");
     if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_render_begin: no scene uploaded");
-    if (st->image_width <= 0 || st->image_height <= 0 || st->image_width > 65535 || st->image_height > 65535)
-        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_begin: image size out of range");
-    if (shard.shard_count == 0 || shard.shard_index >= shard.shard_count)
-        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_begin: bad shard");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t W = (uint32_t)st->image_width, H = (uint32_t)st->image_height;
-    const uint32_t tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;     // ImageSensor.cpp:43-44, 8x8 tiles
-    // pixel list of this shard: tiles t with t % count == index, row-major inside each tile, so 64
-    // consecutive slots (one wavefront) are one 8x8 tile
-    std::vector<uint32_t> pixels;
-    for (uint32_t t = shard.shard_index; t < tilesX * tilesY; t += shard.shard_count) {
-        uint32_t tx = t % tilesX, ty = t / tilesX;
-        for (uint32_t ly = 0; ly < 8; ++ly)
-            for (uint32_t lx = 0; lx < 8; ++lx) {
-                uint32_t x = tx * 8 + lx, y = ty * 8 + ly;
-                if (x < W && y < H) pixels.push_back(x | (y << 16));
-            }
-    }
-    if (pixels.empty()) pixels.push_back(0xFFFFFFFFu);   // an empty shard keeps the buffers valid; numPixels = 0 below
-    const uint32_t numPixels = pixels[0] == 0xFFFFFFFFu ? 0u : (uint32_t)pixels.size();
-    uint32_t stripes = ctx->config.stripes;
-    if (stripes == 0) {
-        // Paths in flight: throughput keeps rising with the slot count (longer launches amortise the per-wave tail of the
-        // traversal kernel: 807 / 1146 / 1267 Msamples/s at 0.9 / 3.7 / 7.4 M slots on the 1280x720 Cornell scene in round 1),
-        // at ~200 B of HBM per slot; the per-pixel sample pool keeps the stripes of a pixel finishing together, so fewer, fuller
-        // iterations keep paying.  The count is a power of two (the stripes of a pixel then fill whole lane groups of the shade
-        // workgroup, PathBuffers): the smallest that reaches ~22 M slots in RGB mode, ~7.4 M in spectral mode (492 B per slot; its
-        // shade kernel is latency-bound, not launch-bound), at most 64 (the width of the pool's mask; also the best count measured
-        // for the eighth of the image a rank owns at N = 8).  Measured with the fused shade kernel, 16 vs 32 stripes at 1280x720
-        // (profiles/r03_e_*): Cornell 2 709 vs 2 719, environment light 5 630 vs 6 061, 10 M-triangle grid 1 954 vs 1 981 Msamples/s.
-        const uint32_t target = ctx->config.mode == SLRHIP_MODE_SPECTRAL ? 7372800u : 22118400u;
-        static const long envStripes = [] { const char* e = tuningEnv("SLRHIP_AUTO_STRIPES"); return e ? atol(e) : 0L; }();      // measurement: force the automatic choice
-        stripes = 1u;
-        while (stripes < 64u && (uint64_t)numPixels * stripes < target) stripes *= 2u;
-        if (numPixels == 0) stripes = 1u;
-        if (envStripes >= 1 && envStripes <= 64) stripes = (uint32_t)envStripes;
-    }
-    // Slots are paths in flight, not places in the image (pt_kernels.h): `stripes` only sizes their number
-    const size_t numSlots = std::max<size_t>(((size_t)numPixels * stripes + 255u) / 256u, 1) * 256u;
-    if (numSlots > 0x7FFFFFFFull) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_begin: too many path slots");
-
     const bool spectral = ctx->config.mode == SLRHIP_MODE_SPECTRAL;
-    const size_t planes = spectral ? 4 : 1;
-    HIP_TRY(ctx->pixelXY.upload(pixels));
-    // SLRHIP_PAIRS (bit 0: ray origin + direction, bit 1: the path's radiance sum + its compensation, bit 2: sample header + RNG state): the two records of a pair
-    // interleaved in one array, one 32-byte sector per slot (PathBuffers::rayStride / spStride)
-    static const int envPairs = [] { const char* e = tuningEnv("SLRHIP_PAIRS"); return e ? atoi(e) : kDefaultPairs; }();
-    const uint32_t rayStride = (envPairs & 1) ? 2u : 1u, spStride = (envPairs & 2) ? 2u : 1u, hdrStride = (envPairs & 4) ? 2u : 1u;
-    HIP_TRY(ctx->rayOrg.alloc(numSlots * rayStride, true)); HIP_TRY(ctx->rayDir.alloc(rayStride == 2 ? 1 : numSlots, true)); HIP_TRY(ctx->hit.alloc(numSlots, true));
-    HIP_TRY(ctx->alpha.alloc(numSlots * planes, true)); HIP_TRY(ctx->spR.alloc(numSlots * planes * spStride, true)); HIP_TRY(ctx->spC.alloc(spStride == 2 ? 1 : numSlots * planes, true));
-    HIP_TRY(ctx->fbSum.alloc((size_t)std::max(numPixels, 1u) * planes, true)); HIP_TRY(ctx->fbComp.alloc((size_t)std::max(numPixels, 1u) * planes, true));
-    HIP_TRY(ctx->nee.alloc(numSlots * planes, true));
-    HIP_TRY(ctx->shadowDir.alloc(numSlots, true));
-    HIP_TRY(ctx->pdfPrev.alloc(spectral ? numSlots : 1, true));
-    HIP_TRY(ctx->hdr.alloc(numSlots * hdrStride, true)); HIP_TRY(ctx->rng.alloc(hdrStride == 2 ? 1 : numSlots, true));
-    HIP_TRY(ctx->cursor.alloc(numSlots / 64u)); HIP_TRY(ctx->idleShards.alloc(kShards * kCounterStride));
-    HIP_TRY(ctx->flags.alloc(numSlots, true)); HIP_TRY(ctx->visible.alloc(numSlots, true));
-    if (ctx->scene.instances) HIP_TRY(ctx->hitInstance.alloc(numSlots, true));
-    // queue regions: slot block b appends to region b % kShards, so a region holds at most ceil(numBlocks / kShards) blocks
-    const uint32_t numBlocks = (uint32_t)((numSlots + 255) / 256);
-    const uint32_t shardCapacity = ((numBlocks + kShards - 1) / kShards) * 256;
-    HIP_TRY(ctx->shadowQueue.alloc((size_t)shardCapacity * kShards, true)); HIP_TRY(ctx->tailList.alloc(numSlots, true));
-    HIP_TRY(ctx->blockDead.alloc(numBlocks));
-    HIP_TRY(ctx->queueCount.alloc(2 * kQueueSetWords)); HIP_TRY(ctx->activeSlots.alloc(kStatusWords));      // [0] live slots, [1] device error word, [2] unused, [3] tail mode (1 + parity), [4..5] tail list length / cursor
-    HIP_TRY(ctx->totals.alloc((size_t)T_KINDS * kShards * kTotalStride));
+    FramePlan plan;
+    std::string err;
+    if (const int rc = planFrame(st->image_width, st->image_height, shard.shard_index, shard.shard_count, ctx->config.stripes, spectral,
+                                 autoStripesOverride(), pairsMask(), &plan, &err))
+        return fail(rc, err);                                                          // the context is untouched so far
+    // An allocation may free an array of the previous render state before it fails, so the context holds no render state from
+    // here on until the last step has succeeded (as commitScene does for the scene).
+    ctx->haveRender = false;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t slots = plan.slotCapacity, planes = spectral ? 4 : 1, pixels = std::max(plan.numPixels, 1u);
+    // The ORDER of the skewed allocations is part of the measured layout: g_skewCounter advances once per skewed array that
+    // really allocates, so the order fixes every array's offset modulo the HBM channel interleave.
+    hipError_t e = ctx->pixelXY.upload(shardPixels(plan));
+    const auto alloc = [&e](auto& array, size_t n, bool skew) { if (e == hipSuccess) e = array.alloc(n, skew); };
+    alloc(ctx->rayOrg, slots * plan.rayStride, true); alloc(ctx->rayDir, plan.rayStride == 2 ? 1 : slots, true); alloc(ctx->hit, slots, true);
+    alloc(ctx->alpha, slots * planes, true); alloc(ctx->spR, slots * planes * plan.spStride, true); alloc(ctx->spC, plan.spStride == 2 ? 1 : slots * planes, true);
+    alloc(ctx->fbSum, pixels * planes, true); alloc(ctx->fbComp, pixels * planes, true);
+    alloc(ctx->nee, slots * planes, true); alloc(ctx->shadowDir, slots, true); alloc(ctx->pdfPrev, spectral ? slots : 1, true);
+    alloc(ctx->hdr, slots * plan.hdrStride, true); alloc(ctx->rng, plan.hdrStride == 2 ? 1 : slots, true);
+    alloc(ctx->cursor, slots / 64u, false); alloc(ctx->idleShards, kShards * kCounterStride, false);
+    alloc(ctx->flags, slots, true); alloc(ctx->visible, slots, true);
+    if (ctx->scene.instances) alloc(ctx->hitInstance, slots, true);
+    alloc(ctx->shadowQueue, (size_t)plan.shardCapacity * kShards, true); alloc(ctx->tailList, slots, true);
+    alloc(ctx->blockDead, plan.numBlocks, false); alloc(ctx->queueCount, 2 * kQueueSetWords, false);
+    alloc(ctx->activeSlots, kStatusWords, false); alloc(ctx->totals, (size_t)T_KINDS * kShards * kTotalStride, false);
+    if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render_begin: allocating the path state: ") + hipGetErrorString(e));
     // The statistics restart here.  A memset of device memory is only ordered on the null stream, and slrhip_render may be
     // given a NON-BLOCKING stream, which the null stream does not wait for and which does not wait for it: the memset has to
     // be complete before this call returns.  (Round 1, gpurun_out/overlap.log: this function also cleared queueCount with a
@@ -421,26 +611,18 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     HIP_TRY(hipMemsetAsync(ctx->activeSlots.ptr, 0, kStatusWords * sizeof(uint32_t), nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
 
-    PathBuffers& pb = ctx->buffers;
-    pb.rng = hdrStride == 2 ? ctx->hdr.ptr + 1 : ctx->rng.ptr; pb.hdrStride = hdrStride; pb.rayOrg = ctx->rayOrg.ptr; pb.rayDir = rayStride == 2 ? ctx->rayOrg.ptr + 1 : ctx->rayDir.ptr; pb.hit = ctx->hit.ptr;
-    pb.rayStride = rayStride; pb.spStride = spStride;
-    pb.alpha = ctx->alpha.ptr; pb.spR = ctx->spR.ptr; pb.spC = spStride == 2 ? ctx->spR.ptr + 1 : ctx->spC.ptr; pb.fbSum = ctx->fbSum.ptr; pb.fbComp = ctx->fbComp.ptr; pb.results = ctx->results.ptr; pb.cursor = ctx->cursor.ptr;
-    pb.nee = ctx->nee.ptr;
-    pb.pdfPrev = spectral ? ctx->pdfPrev.ptr : nullptr; pb.hdr = ctx->hdr.ptr; pb.shadowDir = ctx->shadowDir.ptr; pb.flags = ctx->flags.ptr;
-    pb.hitInstance = ctx->scene.instances ? ctx->hitInstance.ptr : nullptr;
-    pb.visible = ctx->visible.ptr; pb.shadowQueue = ctx->shadowQueue.ptr; pb.tailList = ctx->tailList.ptr;
-    pb.queueCount = ctx->queueCount.ptr; pb.activeSlots = ctx->activeSlots.ptr; pb.errorWord = ctx->activeSlots.ptr + 1; pb.tailMode = ctx->activeSlots.ptr + 3; pb.tailWords = ctx->activeSlots.ptr + 4; pb.tailIdled = ctx->activeSlots.ptr + 2; pb.windowSamples = ctx->activeSlots.ptr + 6; pb.idleShards = ctx->idleShards.ptr; pb.blockDead = ctx->blockDead.ptr; pb.totals = ctx->totals.ptr;
-    pb.pixelXY = ctx->pixelXY.ptr;
-
-    RenderParams& rp = ctx->params;
-    rp.numSlots = numPixels ? (uint32_t)numSlots : 0u; rp.numBlocks = rp.numSlots / 256u; rp.numPixels = numPixels; rp.stripes = stripes;
-    rp.sppBegin = 0; rp.sppCount = 0; rp.workItems = 0; rp.numWaves = rp.numSlots / 64u; rp.runLength = 1; rp.numRuns = 0;
+    bindBuffers(ctx, plan);
+    RenderParams rp{};
+    rp.numSlots = plan.numSlots; rp.numBlocks = rp.numSlots / 256u; rp.numWaves = rp.numSlots / 64u;
+    rp.numPixels = plan.numPixels; rp.stripes = plan.stripes;
+    rp.runLength = 1;                                     // the window's passes, runs and tail bound: renderWindow
     rp.rngSeed = st->rng_seed; rp.timeStart = st->time_start; rp.timeEnd = st->time_end;
-    rp.imageWidth = W; rp.imageHeight = H;
+    rp.imageWidth = plan.width; rp.imageHeight = plan.height;
     rp.countSlots = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) ? 1u : 0u;
-    rp.shardCapacity = shardCapacity;
+    rp.shardCapacity = plan.shardCapacity;
     rp.spectral = spectral ? 1u : 0u;
     rp.injectError = (ctx->config.flags & SLRHIP_FLAG_TEST_DEVICE_ERROR) ? 1u : 0u;
+    ctx->params = rp;
     ctx->settings = *st;
     ctx->shard = shard;
     ctx->iterations = 0;
@@ -449,232 +631,17 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     return SLRHIP_OK;
 }
 
-// One window of passes [sppBegin, sppBegin + sppCount): every sample of the window rendered into the result window, then folded
-// into the sensor in pass order.  slrhip_render sizes the windows.
-static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, hipStream_t stream) {
-    RenderParams& rp = ctx->params;
-    rp.sppBegin = sppBegin;
-    rp.sppCount = sppCount;
-    rp.workItems = rp.numPixels * sppCount;                        // < 2^32: slrhip_render
-    // passes per run (pt_kernels.h WorkItem): the largest power of two <= the default that divides the window's pass count
-    static const uint32_t envRun = [] { const char* e = getenv("SLRHIP_RUN_LENGTH"); const long v = e ? atol(e) : 0L; return v >= 1 && v <= 4096 ? (uint32_t)v : 0u; }();
-    rp.runLength = envRun ? envRun : kDefaultRunLength;
-    while (rp.runLength > 1 && (sppCount % rp.runLength) != 0) rp.runLength /= 2;
-    if (sppCount && sppCount % rp.runLength) rp.runLength = 1;
-    rp.numRuns = rp.numPixels * (sppCount / std::max(rp.runLength, 1u));
-
-    // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
-    // it is asked for zero passes
-    launchResetSlots(ctx->buffers, rp, ctx->firstRenderCall, stream);
-    ctx->firstRenderCall = false;
-    if (sppCount == 0) return SLRHIP_OK;
-    // persistent traversal workgroups of the wave-specialised kernel (pt_trace_ws.hip): a fixed number per CU
-    const uint32_t traceBlocks = (uint32_t)ctx->numCUs * (uint32_t)traceWsBlocksPerCU(ctx->scene.nodesQ != nullptr);
-
-    uint32_t active = rp.numSlots;
-    uint32_t status[4] = {active, 0u, 0u, 0u};       // device words: live slots, error bits, slots idled by the tail kernel, tail mode (PathBuffers)
-    // The end of the window (pt_tail_kernels.h): once at most tailSlots slots are alive the traversal kernel raises the tail-mode
-    // word instead of tracing, the rest of the block of iterations is no-ops, and the tail kernel finishes every remaining path
-    // and sample in one launch.  The image does not depend on who finishes a sample (the sensor adds in pass order).  On with
-    // the automatic slot count (slrhip_config::stripes = 0) and on request (SLRHIP_FLAG_TAIL_KERNEL, SLRHIP_TAIL_SLOTS=n); a
-    // caller who fixes the slot count gets the pure wavefront schedule unless he asks (the parity tests compare the two).  Never
-    // for more than an eighth of the slots (the wavefront kernels are the efficient way to advance many paths) and not in the
-    // counting build (its per-ray figures come from the wavefront kernels).  SLRHIP_TAIL_SLOTS=0 turns it off.
-    static const long envTail = [] { const char* e = getenv("SLRHIP_TAIL_SLOTS"); return e ? atol(e) : -1L; }();
-    {
-        const bool asked = (ctx->config.flags & SLRHIP_FLAG_TAIL_KERNEL) != 0 || envTail > 0 || ctx->config.stripes == 0;
-        const uint32_t bound = envTail > 0 ? (uint32_t)std::min<long>(envTail, 0x7FFFFFFFL) : kDefaultTailSlots;
-        const bool off = !asked || envTail == 0 || !tailKernelAvailable(ctx->scene, rp.spectral != 0) || (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
-        rp.tailSlots = off ? 0u : std::min(bound, active / SLR_TAIL_DIVISOR);
-    }
-    // The window is complete only if the queues handed out exactly one sample per pixel and pass: the device's own count
-    // (k_count_samples over the queues' cursors) against the host's arithmetic.  A lost or repeated sample would leave a stale
-    // or overwritten entry in the result window — never silent.
-    const auto checkWindow = [&](hipStream_t s) -> int {
-        uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(words, ctx->activeSlots.ptr, kStatusWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (words[1]) return deviceError(words[1]);
-        if (words[6] != rp.workItems)
-            return fail(SLRHIP_ERR_HIP, "slrhip_render: the work queues handed out " + std::to_string(words[6]) + " samples for a window of " +
-                                            std::to_string(rp.workItems) + " (internal error)");
-        return SLRHIP_OK;
-    };
-    // tail mode seen in the status words: list the live slots, finish them, read the words again (live slots must be 0 then)
-    const auto runTail = [&](hipStream_t s, bool timed) -> int {
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        if (timed) { HIP_TRY(hipEventCreate(&t0)); HIP_TRY(hipEventCreate(&t1)); HIP_TRY(hipEventRecord(t0, s)); }
-        launchTail(ctx->scene, ctx->buffers, rp, status[0], ctx->numCUs, s);
-        if (timed) HIP_TRY(hipEventRecord(t1, s));
-        HIP_TRY(hipGetLastError());
-        const uint32_t liveBefore = status[0];
-        uint32_t words[6] = {0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(words, ctx->activeSlots.ptr, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        std::memcpy(status, words, 4 * sizeof(uint32_t));
-        if (timed) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-            ctx->profMs[SLRHIP_KERNEL_TAIL] += ms;
-            ++ctx->profLaunches[SLRHIP_KERNEL_TAIL];
-            (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
-        }
-        if (status[1]) return deviceError(status[1]);
-        if (words[2] != words[4])
-            return fail(SLRHIP_ERR_HIP, "slrhip_render: the tail kernel left " + std::to_string(words[4] - words[2]) + " of " + std::to_string(words[4]) +
-                                            " listed slots live (live count before: " + std::to_string(liveBefore) + ", cursor " + std::to_string(words[5]) + "; internal error)");
-        // every listed slot ended idle and the wavefront kernels are off (tail mode): nothing is live any more
-        HIP_TRY(hipMemsetAsync(ctx->activeSlots.ptr, 0, sizeof(uint32_t), s));
-        status[0] = 0;
-        return SLRHIP_OK;
-    };
-    // One wavefront iteration = k_shade (advance every live path by one vertex; finish and restart the paths that end) then
-    // k_trace_ws (the extension and shadow rays that left).  Each check of the live-slot word costs one small copy + stream
-    // sync; 16 iterations between checks keeps it < 1 %.
-    const int kCheckEvery = 16;
-    const int kEv = 3;    // events per iteration: before shade, after shade, after trace
-    const bool timeKernels = (ctx->config.flags & SLRHIP_FLAG_TIME_KERNELS) != 0;
-    const bool count = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
-    if (timeKernels && ctx->events.empty()) {
-        ctx->events.resize((size_t)kCheckEvery * kEv);
-        for (hipEvent_t& e : ctx->events) HIP_TRY(hipEventCreate(&e));
-    }
-    const uint64_t maxIterations = ((uint64_t)rp.workItems / rp.numSlots + 2) * 128 + 1024;   // paths are <= 100 vertices long
-    uint64_t it = 0;
-
-    // The block of kCheckEvery iterations is the same sequence of launches every time (the parity alternates inside it and is
-    // back to 0 at its end), so it is captured ONCE per call into a hipGraph and replayed: one submission per block instead
-    // of 32 launches with their dispatch gaps — what is left of the cost of the nearly empty iterations at the end of a
-    // render.  Capture needs a real stream, so the work runs on the context's own stream, ordered after the caller's by an
-    // event; render() returns only after that stream is idle, which orders the caller's later work after it.
-    static const bool noGraph = [] { const char* e = getenv("SLRHIP_GRAPH"); return e && std::string(e) == "0"; }();
-    if (!timeKernels && !noGraph && rp.numSlots >= (1u << 18)) {
-        if (!ctx->workStream) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->workStream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->userReady, hipEventDisableTiming));
-        }
-        hipStream_t ws = ctx->workStream;
-        HIP_TRY(hipEventRecord(ctx->userReady, stream));          // the reset kernel above and whatever the caller queued before
-        HIP_TRY(hipStreamWaitEvent(ws, ctx->userReady, 0));
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        HIP_TRY(hipStreamBeginCapture(ws, hipStreamCaptureModeThreadLocal));
-        for (int k = 0; k < kCheckEvery; ++k) {
-            launchShade(ctx->scene, ctx->buffers, rp, (uint32_t)(k & 1), ws);
-            launchTraceWs(ctx->scene, ctx->buffers, rp, (uint32_t)(k & 1), traceBlocks, count, ws);
-        }
-        hipError_t ce = hipStreamEndCapture(ws, &graph);
-        if (ce == hipSuccess) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ce != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: hipGraph capture failed: ") + hipGetErrorString(ce));
-        }
-        int rc = SLRHIP_OK;
-        while (active > 0 && rc == SLRHIP_OK) {
-            hipError_t e = hipGraphLaunch(exec, ws);
-            if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->activeSlots.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ws);
-            if (e == hipSuccess) e = hipStreamSynchronize(ws);
-            if (e != hipSuccess) rc = fail(SLRHIP_ERR_HIP, std::string("slrhip_render: ") + hipGetErrorString(e));
-            it += kCheckEvery;
-            if (rc == SLRHIP_OK && status[1]) rc = deviceError(status[1]);
-            if (rc == SLRHIP_OK && status[3] && status[0]) rc = runTail(ws, false);
-            active = status[0];
-            if (rc == SLRHIP_OK && it > maxIterations) rc = fail(SLRHIP_ERR_HIP, "slrhip_render: iteration bound exceeded (internal error)");
-        }
-        (void)hipGraphExecDestroy(exec);
-        (void)hipGraphDestroy(graph);
-        if (rc != SLRHIP_OK) return rc;
-        ctx->iterations += it;
-        launchCountSamples(ctx->buffers, rp, ws);      // samples rendered in this window, counted on the device (T_SAMPLES)
-        launchFold(ctx->buffers, rp, ws);              // sensor->add, in pass order
-        HIP_TRY(hipGetLastError());
-        return checkWindow(ws);
-    }
-
-    // SLRHIP_ITER_LOG=path (with SLRHIP_FLAG_TIME_KERNELS): per-iteration kernel times of this call, one line per iteration
-    // "iteration shade_ms trace_ms live_slots_at_block_end" — how the drain of a render's last paths was measured
-    static const char* iterLog = getenv("SLRHIP_ITER_LOG");
-    std::vector<float> iterMs;
-    std::vector<uint32_t> iterActive;
-    uint32_t parity = 0;
-    while (active > 0) {
-        for (int k = 0; k < kCheckEvery; ++k) {
-            hipEvent_t* ev = timeKernels ? &ctx->events[(size_t)k * kEv] : nullptr;
-            if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
-            launchShade(ctx->scene, ctx->buffers, rp, parity, stream);
-            if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
-            launchTraceWs(ctx->scene, ctx->buffers, rp, parity, traceBlocks, count, stream);
-            if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
-            parity ^= 1;
-            ++it;
-        }
-        HIP_TRY(hipGetLastError());                  // a failed launch surfaces here, not at the end of the render
-        HIP_TRY(hipMemcpyAsync(status, ctx->activeSlots.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        active = status[0];
-        if (status[1]) return deviceError(status[1]);
-        if (timeKernels) {
-            static const int cls[2] = {SLRHIP_KERNEL_SHADE, SLRHIP_KERNEL_TRACE};
-            for (int k = 0; k < kCheckEvery; ++k) {
-                hipEvent_t* ev = &ctx->events[(size_t)k * kEv];
-                for (int j = 0; j < 2; ++j) {
-                    float ms = 0.0f;
-                    HIP_TRY(hipEventElapsedTime(&ms, ev[j], ev[j + 1]));
-                    ctx->profMs[cls[j]] += ms;
-                    ++ctx->profLaunches[cls[j]];
-                    if (iterLog) iterMs.push_back(ms);
-                }
-                if (iterLog) iterActive.push_back(active);
-            }
-        }
-        if (status[3] && status[0]) {
-            const int rc = runTail(stream, timeKernels);
-            if (rc != SLRHIP_OK) return rc;
-            active = status[0];
-        }
-        if (it > maxIterations) return fail(SLRHIP_ERR_HIP, "slrhip_render: iteration bound exceeded (internal error)");
-    }
-    ctx->iterations += it;
-    launchCountSamples(ctx->buffers, rp, stream);       // samples rendered in this window, counted on the device (T_SAMPLES)
-    launchFold(ctx->buffers, rp, stream);               // sensor->add, in pass order
-    HIP_TRY(hipGetLastError());
-    {
-        const int rc = checkWindow(stream);
-        if (rc != SLRHIP_OK) return rc;
-    }
-    if (iterLog && timeKernels && !iterActive.empty()) {
-        if (FILE* f = fopen(iterLog, "a")) {
-            const size_t per = iterMs.size() / iterActive.size();
-            fprintf(f, "# render: %u slots, %u passes from %u\n", rp.numSlots, sppCount, sppBegin);
-            for (size_t i = 0; i < iterActive.size(); ++i) {
-                fprintf(f, "%zu", i);
-                for (size_t j = 0; j < per; ++j) fprintf(f, " %.4f", iterMs[i * per + j]);
-                fprintf(f, " %u\n", iterActive[i]);
-            }
-            fclose(f);
-        }
-    }
-    return SLRHIP_OK;
-}
-
 int slrhip_render(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
     if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render: null context");
     if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_render: call slrhip_render_begin first");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)streamPtr;
-    RenderParams& rp = ctx->params;
+    const RenderParams& rp = ctx->params;
     if (rp.numSlots == 0) { ctx->firstRenderCall = false; return SLRHIP_OK; }
-    // The result window (PathBuffers::results) holds one entry per pixel and pass: 16 B (RGB) / 64 B (spectral).  A call of more
-    // passes than fit the budget — 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides — or than 2^32 samples is rendered as
-    // several windows, one after the other; the sensor adds in pass order either way, so the image does not depend on the split.
-    const uint64_t entryBytes = (rp.spectral ? 4u : 1u) * sizeof(float4);
+    // the result window's budget (render_plan.cpp, planWindows): 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides
     uint64_t budget = 16ull << 30;
     if (const char* e = getenv("SLRHIP_RESULT_WINDOW_MB")) { const long mb = atol(e); if (mb > 0) budget = (uint64_t)mb << 20; }
-    const uint64_t maxPasses = std::max<uint64_t>(1, std::min<uint64_t>(budget / ((uint64_t)rp.numPixels * entryBytes), 0xF0000000ull / rp.numPixels));      // (run ids + one round of waves stay inside 32 bits)
-    // whole runs (RenderParams::runLength passes of a pixel in a row, pt_kernels.h) wherever the call is long enough: a window of
-    // an odd number of passes would fall back to runs of one pass and lose the coherence of a wave's slots
-    uint32_t window = (uint32_t)std::min<uint64_t>(maxPasses, std::max<uint32_t>(sppCount, 1u));
-    if (window >= kDefaultRunLength) window -= window % kDefaultRunLength;
+    const uint32_t window = planWindows(rp.numPixels, rp.spectral != 0, sppCount, budget);
     HIP_TRY(ctx->results.alloc((size_t)window * rp.numPixels * (rp.spectral ? 4u : 1u)));
     ctx->buffers.results = ctx->results.ptr;
     if (sppCount == 0) return renderWindow(ctx, sppBegin, 0, stream);
@@ -689,7 +656,7 @@ int slrhip_resolve_framebuffer(slrhip_ctx* ctx, float* deviceDst, size_t numFloa
     if (!ctx || !deviceDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_framebuffer: null argument");
     if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_resolve_framebuffer: nothing rendered");
     const RenderParams& rp = ctx->params;
-    const size_t need = (size_t)rp.imageWidth * rp.imageHeight * (rp.spectral ? 16 : 3);
+    const size_t need = frameFloats(rp);
     if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_framebuffer: destination too small");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)streamPtr;
@@ -706,7 +673,7 @@ int slrhip_reduce_framebuffer(slrhip_ctx* ctx, void* ncclComm, int root, float* 
     if (!ctx || !ncclComm) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_reduce_framebuffer: null argument");
     if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_reduce_framebuffer: nothing rendered");
     const RenderParams& rp = ctx->params;
-    const size_t need = (size_t)rp.imageWidth * rp.imageHeight * (rp.spectral ? 16 : 3);
+    const size_t need = frameFloats(rp);
     if (deviceDst && numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_reduce_framebuffer: destination too small");
     typedef int (*reduce_fn)(const void*, void*, size_t, int, int, int, void*, hipStream_t);
     typedef int (*rank_fn)(void*, int*);
@@ -735,7 +702,7 @@ int slrhip_read_framebuffer(slrhip_ctx* ctx, float* hostDst, size_t numFloats) {
     if (!ctx || !hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_framebuffer: null argument");
     if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_read_framebuffer: nothing rendered");
     const RenderParams& rp = ctx->params;
-    const size_t need = (size_t)rp.imageWidth * rp.imageHeight * (rp.spectral ? 16 : 3);
+    const size_t need = frameFloats(rp);
     if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_framebuffer: destination too small");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->resolveScratch.alloc(need));
@@ -879,6 +846,32 @@ int slrhip_debug_work_distribution(uint32_t numPixels, uint32_t numSlots, uint32
         }
         queueLengths[w] = taken;
         if (workSamplesTaken(rp, w, taken + 7u) != taken) return fail(SLRHIP_ERR_HIP, "slrhip_debug_work_distribution: workSamplesTaken disagrees with the queue");
+    }
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the render plan of render_plan.cpp for a frame, a shard and a call of num_passes passes.
+int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shardIndex, uint32_t shardCount, uint32_t stripes, int32_t mode,
+                             uint32_t numPasses, uint64_t budgetBytes, uint32_t* plan, uint32_t* windows, uint32_t maxWindows,
+                             uint32_t* numWindows, uint32_t* pixels, uint32_t maxPixels) {
+    if (!plan || !numWindows || (maxWindows && !windows) || budgetBytes == 0 || stripes > SLRHIP_MAX_STRIPES ||
+        (mode != SLRHIP_MODE_RGB && mode != SLRHIP_MODE_SPECTRAL))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_render_plan: bad arguments");
+    const bool spectral = mode == SLRHIP_MODE_SPECTRAL;
+    FramePlan frame;
+    std::string err;
+    if (const int rc = planFrame(width, height, shardIndex, shardCount, stripes, spectral, autoStripesOverride(), pairsMask(), &frame, &err))
+        return fail(rc, err);
+    const uint32_t window = frame.numPixels ? planWindows(frame.numPixels, spectral, numPasses, budgetBytes) : 0u;
+    plan[0] = frame.numPixels; plan[1] = frame.stripes; plan[2] = frame.numSlots; plan[3] = window;
+    *numWindows = window ? (numPasses + window - 1) / window : 0u;
+    for (uint32_t k = 0; k < std::min(*numWindows, maxWindows); ++k) {
+        windows[2 * k] = std::min(window, numPasses - k * window);
+        windows[2 * k + 1] = planWindow(frame.numPixels, windows[2 * k], runLengthOverride()).runLength;
+    }
+    if (pixels) {
+        if (maxPixels < frame.numPixels) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_render_plan: pixel buffer too small");
+        if (frame.numPixels) { const std::vector<uint32_t> list = shardPixels(frame); std::memcpy(pixels, list.data(), list.size() * sizeof(uint32_t)); }
     }
     return SLRHIP_OK;
 }

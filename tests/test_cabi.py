@@ -60,6 +60,130 @@ def test_work_queues_hand_out_every_sample_exactly_once(lib, num_pixels, num_slo
     assert f(num_pixels, num_slots, num_passes, num_passes + 1, counts.ctypes.data, lengths.ctypes.data) != 0      # the run length must divide the passes
 
 
+GIB = 1 << 30
+MIB = 1 << 20
+
+
+def render_plan(lib, width, height, shard=(0, 1), stripes=0, mode=abi.MODE_RGB, passes=1, budget=16 * GIB, want_pixels=False):
+    """slrhip_debug_render_plan: (numPixels, stripes, numSlots, window), [(passes, run length) per window], pixel list or None."""
+    f = lib.slrhip_debug_render_plan
+    f.argtypes = [C.c_int32, C.c_int32] + [C.c_uint32] * 3 + [C.c_int32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                              C.c_void_p, C.c_void_p, C.c_uint32]
+    plan = np.zeros(4, np.uint32)
+    max_windows = max(passes, 1)
+    windows = np.zeros(2 * max_windows, np.uint32)
+    num_windows = C.c_uint32(0)
+    pixels = np.full(width * height, 0xDEADBEEF, np.uint32) if want_pixels else None
+    rc = f(width, height, shard[0], shard[1], stripes, mode, passes, budget, plan.ctypes.data, windows.ctypes.data, max_windows,
+           C.byref(num_windows), pixels.ctypes.data if want_pixels else None, pixels.size if want_pixels else 0)
+    if rc != 0:
+        raise binding.SlrHipError("(%d): %s" % (rc, lib.slrhip_last_error_string().decode()))
+    assert num_windows.value <= max_windows
+    return tuple(int(v) for v in plan), [tuple(int(v) for v in w) for w in windows[:2 * num_windows.value].reshape(-1, 2)], \
+        (pixels[:int(plan[0])] if want_pixels else None)
+
+
+@pytest.mark.parametrize("width, height, shard, mode, stripes, slots",
+                         [(1280, 720, (0, 1), abi.MODE_RGB, 32, 29491200),
+                          (1280, 720, (0, 1), abi.MODE_SPECTRAL, 8, 7372800),
+                          (1280, 720, (5, 8), abi.MODE_RGB, 64, 7372800),          # 115 200 pixels: capped at the 64 stripes of the pool's mask
+                          (64, 64, (0, 1), abi.MODE_RGB, 64, 262144),
+                          (64, 64, (0, 1), abi.MODE_SPECTRAL, 64, 262144)])
+def test_render_plan_automatic_slot_count(lib, width, height, shard, mode, stripes, slots):
+    """The automatic stripe count (slrhip_config::stripes = 0): the smallest power of two that reaches 22 118 400 slots in RGB mode,
+    7 372 800 in spectral mode, at most 64; slots = pixels x stripes rounded up to 256.  Values derived by hand from that rule."""
+    (num_pixels, got_stripes, got_slots, _), _, _ = render_plan(lib, width, height, shard, 0, mode)
+    assert num_pixels == width * height // shard[1]
+    assert (got_stripes, got_slots) == (stripes, slots)
+
+
+@pytest.mark.parametrize("width, height, mode, passes, budget, window, windows",
+                         [(1280, 720, abi.MODE_RGB, 1024, 16 * GIB, 1024, [(1024, 64)]),
+                          (1280, 720, abi.MODE_SPECTRAL, 1024, 16 * GIB, 256, [(256, 64)] * 4),
+                          (1280, 720, abi.MODE_RGB, 100, 16 * GIB, 64, [(64, 64), (36, 4)]),
+                          (1280, 720, abi.MODE_RGB, 2048, 16 * GIB, 1152, [(1152, 64), (896, 64)]),
+                          (64, 64, abi.MODE_RGB, 32, MIB, 16, [(16, 16)] * 2),          # the windows test_stripes_do_not_change_the_image forces
+                          (64, 64, abi.MODE_SPECTRAL, 32, MIB, 4, [(4, 4)] * 8)])
+def test_render_plan_result_windows(lib, width, height, mode, passes, budget, window, windows):
+    """The split of a render call into result windows (16 B per pixel and pass, 64 B in spectral mode): as many passes as fit the
+    budget, whole runs of 64 once there are 64, and per window the largest power-of-two fraction of 64 that divides it as its run
+    length.  Values derived by hand from slrhip_render's arithmetic."""
+    plan, got, _ = render_plan(lib, width, height, mode=mode, passes=passes, budget=budget)
+    assert plan[0] == width * height and plan[3] == window
+    assert got == windows
+
+
+def _tile_major_pixels(width, height, index, count):
+    """The shard's pixel list as slrhip.h states it: the 8x8 tiles t (row-major over the frame) with t % count == index, each tile
+    row-major, cut at the frame's edge."""
+    tiles_x, tiles_y = (width + 7) // 8, (height + 7) // 8
+    out = []
+    for t in range(index, tiles_x * tiles_y, count):
+        tx, ty = t % tiles_x, t // tiles_x
+        out += [(x, y) for y in range(8 * ty, min(8 * ty + 8, height)) for x in range(8 * tx, min(8 * tx + 8, width))]
+    return out
+
+
+@pytest.mark.parametrize("shard_count", [1, 3, 8])
+@pytest.mark.parametrize("width, height", [(1, 1), (3, 5), (9, 8), (37, 21), (64, 64), (1280, 720)])
+def test_render_plan_shards_partition_the_frame(lib, width, height, shard_count):
+    """The pixel lists of the shards of a frame are disjoint and cover every pixel once, each is 8x8-tile-major, a shard without
+    a tile has no pixel and no slot, and the arithmetic pixel count agrees with the list."""
+    seen = np.zeros((height, width), np.uint32)
+    tiles = ((width + 7) // 8) * ((height + 7) // 8)
+    for index in range(shard_count):
+        (num_pixels, stripes, slots, window), windows, pixels = render_plan(lib, width, height, (index, shard_count), passes=8, want_pixels=True)
+        assert len(pixels) == num_pixels
+        if index >= tiles:
+            assert (num_pixels, slots, window, windows) == (0, 0, 0, [])
+            continue
+        x, y = pixels & 0xFFFF, pixels >> 16
+        if width * height <= 64 * 64:
+            assert list(zip(x.tolist(), y.tolist())) == _tile_major_pixels(width, height, index, shard_count)
+        else:          # the same statement without the Python loop: the tile sequence is the shard's, and inside a tile y, x ascend
+            tile = (y // 8) * ((width + 7) // 8) + x // 8
+            order = tile.astype(np.int64) * 64 + (y % 8) * 8 + x % 8
+            assert (np.diff(order) > 0).all() and (tile % shard_count == index).all()
+        np.add.at(seen, (y, x), 1)
+        assert slots % 256 == 0 and slots >= num_pixels * stripes > slots - 256
+    assert (seen == 1).all()
+
+
+@pytest.mark.parametrize("mode", [abi.MODE_RGB, abi.MODE_SPECTRAL])
+@pytest.mark.parametrize("width, height, shard, passes, budget",
+                         [(1, 1, (0, 1), 7, 16 * GIB), (3, 5, (0, 3), 1000, 4096), (9, 8, (0, 3), 130, MIB), (37, 21, (7, 8), 97, 64 * 1024),
+                          (1280, 720, (0, 1), 5000, 16 * GIB), (1280, 720, (2, 8), 333, 100 * MIB), (1280, 720, (0, 1), 3, MIB)])
+def test_render_plan_windows_cover_the_call(lib, mode, width, height, shard, passes, budget):
+    """The windows of a call sum to its pass count, all but the last have the window length, each window's run length divides it
+    and is a power of two <= 64, each window fits the budget unless that would mean less than one pass, and a fixed stripe count
+    is honoured."""
+    (num_pixels, stripes, slots, window), windows, _ = render_plan(lib, width, height, shard, 5, mode, passes, budget)
+    assert stripes == 5 and slots == (num_pixels * 5 + 255) // 256 * 256
+    entry = 64 if mode == abi.MODE_SPECTRAL else 16
+    assert sum(n for n, _ in windows) == passes
+    assert all(n == window for n, _ in windows[:-1]) and 0 < windows[-1][0] <= window
+    for n, run in windows:
+        assert n % run == 0 and run in (1, 2, 4, 8, 16, 32, 64)
+        assert n * num_pixels * entry <= budget or n == 1
+        assert n * num_pixels < 1 << 32
+    assert window < 64 or window % 64 == 0
+
+
+def test_render_plan_refuses_before_it_builds_anything(lib):
+    """The refusals of slrhip_render_begin, with their texts; a 65535 x 65535 frame (4.29e9 pixels) is refused for its slot count
+    without its pixel list being built: the plan counts the pixels row of tiles by row of tiles, so the call returns at once (the
+    list alone would be 17 GB)."""
+    import time
+    for args, message in [((0, 5), "image size out of range"), ((65536, 8), "image size out of range"),
+                          ((8, 8, (1, 1)), "bad shard"), ((8, 8, (0, 0)), "bad shard")]:
+        with pytest.raises(binding.SlrHipError, match=r"^\(1\): slrhip_render_begin: %s$" % message):
+            render_plan(lib, *args)
+    t0 = time.monotonic()
+    with pytest.raises(binding.SlrHipError, match=r"^\(1\): slrhip_render_begin: too many path slots$"):
+        render_plan(lib, 65535, 65535)
+    assert time.monotonic() - t0 < 1.0
+
+
 def test_version(lib):
     text = open(os.path.join(ROOT, "include", "slrhip.h")).read()
     assert lib.slrhip_version() == int(re.search(r"#define SLRHIP_VERSION (\d+)", text).group(1)) == 7

@@ -665,6 +665,52 @@ def test_refused_upload_leaves_the_context_as_it_was():
         c.close()
 
 
+def test_refused_render_begin_leaves_the_context_as_it_was():
+    """A render_begin refused by a check of the host-side plan touches nothing: one refused call per check (image size, shard,
+    slot count: 65535 x 65535 is 4.29e9 pixels), each with its message; then the render goes on from where it stopped without
+    render_begin, bit for bit as without the refused calls, and counters and ray queries still answer."""
+    from slr_amd.binding import SlrHipError
+    sc = scenes.cornell_instanced(1.0, 8, 4)
+    st = ob.settings(32, 32, seed=7)
+    rng = np.random.default_rng(11)
+    pos = sc.vertices["position"]
+    lo, hi = pos.min(0), pos.max(0)
+    cam = np.asarray(sc.camera.local_to_world[12:15], np.float32)
+    rays = np.zeros((256, 8), np.float32)
+    rays[:, 0:3] = cam
+    rays[:, 4:7] = lo + (hi - lo) * rng.uniform(0.05, 0.95, (256, 3)) - cam
+    rays[:, 7] = np.inf
+
+    def refused(settings, shard, message):
+        with pytest.raises(SlrHipError, match=message):
+            c.render_begin(settings, shard)
+
+    c = Context()
+    try:
+        c.upload_scene(sc)
+        hits = c.intersect_rays(rays)
+        assert (hits[:, 0].view(np.uint32) != abi.MISS).any()
+        c.render_begin(st)
+        c.render(0, 4)
+        first = c.read_framebuffer()
+        samples = c.counters().samples
+        assert samples == 4 * 32 * 32
+        refused(ob.settings(0, 32, seed=7), (0, 1), r"\(1\): slrhip_render_begin: image size out of range$")
+        refused(st, (2, 2), r"\(1\): slrhip_render_begin: bad shard$")
+        refused(ob.settings(65535, 65535, seed=7), (0, 1), r"\(1\): slrhip_render_begin: too many path slots$")
+        assert c.counters().samples == samples
+        c.render(4, 4)                                                  # no render_begin: the render state survived
+        after = c.read_framebuffer()
+        assert after.sum() > first.sum()
+        assert c.counters().samples == 2 * samples
+        assert_bit_equal(c.intersect_rays(rays), hits, "hits after the refused calls")
+        c.render_begin(st)                                              # the same 8 passes, uninterrupted
+        c.render(0, 8)
+        assert_bit_equal(after, c.read_framebuffer(), "8 passes across the refused calls")
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("name", ["rgb_oren_nayar"])
 def test_oren_nayar_matches_reference_golden(ctx, name):
     """Oren-Nayar uses no libm beyond the cosine sample: expected bit-exact like Lambert."""
