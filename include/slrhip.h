@@ -490,6 +490,68 @@ int slrhip_test_visibility(slrhip_ctx* ctx, const slrhip_ray* rays, uint32_t n, 
  * that stream only, not for the device.                                                                                  */
 int slrhip_query_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
 
+/* ---- first-hit feature buffers and camera rays ------------------------------------------------------------------------------
+ * What a host needs next to the beauty frame (denoiser guides, picking / masking buffers, a "what does the camera see" view): the
+ * reference's DebugRenderer (Renderers/DebugRenderer.cpp:132-216) — the path tracer's own camera sample, the closest hit of the
+ * aggregate with the alpha test the render applies, the surface point in world space (bump map and instance transform as in the
+ * path tracer) — accumulated per pixel.  One traversal per sample, fused: the camera rays are made inside the traversal kernel.
+ *
+ * Channels (bits; `channels` of slrhip_render_features is a set, `channel` of slrhip_resolve_features is ONE bit):           */
+#define SLRHIP_FEATURE_GEOMETRIC_NORMAL 1u   /* 3 floats  SurfacePoint::gNormal          (DebugRenderer ExtraChannel::GeometricNormal) */
+#define SLRHIP_FEATURE_SHADING_NORMAL   2u   /* 3 floats  shadingFrame.z, after bump     (ExtraChannel::ShadingNormal)                 */
+#define SLRHIP_FEATURE_SHADING_TANGENT  4u   /* 3 floats  shadingFrame.x, after bump     (ExtraChannel::ShadingTangent)                */
+#define SLRHIP_FEATURE_DISTANCE         8u   /* 1 float   Intersection::dist of the camera ray (ExtraChannel::Distance)                */
+#define SLRHIP_FEATURE_COVERAGE        16u   /* 1 float   number of samples of the pixel that hit a triangle                          */
+#define SLRHIP_FEATURE_IDS             32u   /* 3 uint32  triangle, instance (0xFFFFFFFF: loose), material; all 0xFFFFFFFF on a miss   */
+#define SLRHIP_FEATURE_ALL             63u
+
+/* Passes [spp_begin, spp_begin + spp_count) of every pixel of the shard (after slrhip_render_begin): the camera ray slrhip_render
+ * traces for that (pixel, pass) -> closest hit -> surface point -> per-pixel accumulation.  The float channels are PLAIN float32
+ * SUMS IN PASS ORDER; a miss (the environment sphere is a miss) adds nothing, so sum / COVERAGE is the mean over the hits and
+ * COVERAGE / spp the alpha of the pixel.  IDS holds the record of the highest pass rendered so far.  The accumulation is cleared
+ * by slrhip_render_begin and is apart from the beauty accumulation: feature passes and slrhip_render calls may interleave in any
+ * order and neither changes the other's result in any bit, nor the render's counters or error word.  The result does not depend
+ * on the shard split, on how the passes are cut into calls (ascending), on the tree kind or on scheduling, and RGB and spectral
+ * contexts give the same buffers for the same seed.
+ * Every feature call between two slrhip_render_begin calls names the SAME channel set (another set is
+ * SLRHIP_ERR_INVALID_ARGUMENT): every channel then sums over the same passes.  DISTANCE and COVERAGE come with every set at no
+ * cost, but only the channels of the set can be resolved.
+ * Stream-ordered and NON-BLOCKING: the call queues its launches on `stream` and returns.  The first feature call after a
+ * slrhip_render_begin allocates the sums (64 B per pixel) and the record window (a render that never asks for features pays
+ * nothing) and is therefore not capturable in a graph; every later call allocates nothing, copies nothing and does not
+ * synchronise, and may be captured.  The record window holds 16 B per (pixel, pass), 20 B with SHADING_NORMAL or SHADING_TANGENT:
+ * as many passes as fit in 512 MiB (at most 64, at least one: a shard of more than 26 M pixels takes more than 512 MiB); a
+ * longer call runs window after window.  The arrays are kept for the next slrhip_render_begin and freed with the context.
+ * The feature calls of one context go on ONE stream, or the caller synchronises between them: the first call after a
+ * slrhip_render_begin clears the reused sums on ITS stream, which is not ordered after feature work still in flight elsewhere.
+ * Errors: SLRHIP_ERR_NO_SCENE before slrhip_render_begin; SLRHIP_ERR_INVALID_ARGUMENT for no or unknown channel bits, a channel
+ * set that differs from the first call's, or a pass range beyond 2^32; spp_count == 0 does nothing.  A traversal that gives up
+ * (never expected) sets a bit in the context's FEATURE error word, sticky until the next slrhip_render_begin:
+ * slrhip_features_status reads it.                                                                                         */
+int slrhip_render_features(slrhip_ctx* ctx, uint32_t channels, uint32_t spp_begin, uint32_t spp_count, void* stream);
+
+/* One channel into DEVICE memory as [height][width][k] (k = 3 or 1; float32, IDS: uint32; 4-byte aligned), zeros (IDS:
+ * 0xFFFFFFFF) outside the shard, so that shards sum / merge like the framebuffer.  num_elements: room at device_dst, in
+ * elements; at least width x height x k.  Stream-ordered, non-blocking, allocates nothing.  A channel that no
+ * slrhip_render_features call since slrhip_render_begin asked for is SLRHIP_ERR_INVALID_ARGUMENT.                          */
+int slrhip_resolve_features(slrhip_ctx* ctx, uint32_t channel, void* device_dst, size_t num_elements, void* stream);
+
+/* The same into HOST memory: resolves, waits for the device, and fails with SLRHIP_ERR_HIP if the feature error word is set.  */
+int slrhip_read_features(slrhip_ctx* ctx, uint32_t channel, void* host_dst, size_t num_elements);
+
+/* The camera ray of sample `pass` of every pixel of the shard (after slrhip_render_begin), in DEVICE memory: rays[i] (16-byte
+ * aligned; dist_min = 0, dist_max = INFINITY) and pixel_xy[i] = x | y << 16 (4-byte aligned; may be NULL), i < *count.  It is
+ * the ray slrhip_render and slrhip_render_features trace for that (pixel, pass): same seed (slrhip_sample_seed), same draws in
+ * the same order (time, pixel x, pixel y, wavelength offset, wavelength selection, two lens draws), same float operations.
+ * capacity: room at rays / pixel_xy in rays; smaller than the shard's pixel count is SLRHIP_ERR_INVALID_ARGUMENT.  *count (HOST
+ * memory) is known from the render plan and written at the call; rays == pixel_xy == NULL with capacity 0 asks for the count alone.  Stream-ordered, non-blocking, allocates nothing, does not
+ * synchronise: capturable like the ray queries.                                                                             */
+int slrhip_camera_rays(slrhip_ctx* ctx, uint32_t pass, slrhip_ray* rays, uint32_t* pixel_xy, uint32_t capacity, uint32_t* count, void* stream);
+
+/* The feature error word (the bits of slrhip_query_status; 0 = every sample of every feature call since slrhip_render_begin was
+ * traced), read in order on `stream` and written to HOST memory *bits.  Waits for that stream only.                          */
+int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
+
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
 

@@ -39,6 +39,12 @@ hit_dtype = np.dtype([("triangle", "<u4"), ("dist", "<f4"), ("b0", "<f4"), ("b1"
 MISS = 0xFFFFFFFF
 # bits of the query error word (slrhip_query_status)
 QUERY_ERR_RING_SPACE, QUERY_ERR_RING_RELEASE, QUERY_ERR_CONSUMER_IDLE, QUERY_ERR_STACK_OVERFLOW = 1, 2, 4, 8
+# first-hit feature buffers (slrhip_render_features): channel bits, and per channel (file / npz name, components, numpy dtype)
+FEATURE_GEOMETRIC_NORMAL, FEATURE_SHADING_NORMAL, FEATURE_SHADING_TANGENT, FEATURE_DISTANCE, FEATURE_COVERAGE, FEATURE_IDS = 1, 2, 4, 8, 16, 32
+FEATURE_ALL = 63
+FEATURE_CHANNELS = {FEATURE_GEOMETRIC_NORMAL: ("geometric_normal", 3, np.float32), FEATURE_SHADING_NORMAL: ("shading_normal", 3, np.float32),
+                    FEATURE_SHADING_TANGENT: ("shading_tangent", 3, np.float32), FEATURE_DISTANCE: ("distance", 1, np.float32),
+                    FEATURE_COVERAGE: ("coverage", 1, np.float32), FEATURE_IDS: ("ids", 3, np.uint32)}
 
 
 def texture_ref(t):

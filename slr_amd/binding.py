@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(CSRC, "libslrhip.so")
 EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_render_begin", "slrhip_render",
            "slrhip_resolve_framebuffer", "slrhip_reduce_framebuffer", "slrhip_read_framebuffer", "slrhip_synchronize", "slrhip_get_counters",
            "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_intersect_rays", "slrhip_test_visibility",
-           "slrhip_query_status", "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_query_status", "slrhip_render_features", "slrhip_resolve_features", "slrhip_read_features", "slrhip_camera_rays", "slrhip_features_status",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -57,6 +58,14 @@ def load_library():
     lib.slrhip_intersect_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.slrhip_test_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.slrhip_query_status.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    # (an alternate build from before the feature buffers lacks these five: calling one there is an AttributeError)
+    for name, argtypes in (("slrhip_render_features", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_resolve_features", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_read_features", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_camera_rays", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
+                           ("slrhip_features_status", [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -235,6 +244,75 @@ class Context:
         _check(self.lib, self.lib.slrhip_query_status(self.handle, C.byref(bits), getattr(stream, "cuda_stream", stream) or None),
                "slrhip_query_status")
         return bits.value
+
+    # ---- first-hit feature buffers and camera rays (slrhip_render_features / slrhip_resolve_features / slrhip_camera_rays) ----
+    def _stream_handle(self, stream):
+        return getattr(stream, "cuda_stream", stream) or None
+
+    def _num_pixels(self):
+        """Pixels of this context's shard, as the render plan counts them (slrhip_camera_rays reports it at the call)."""
+        count = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_camera_rays(self.handle, 0, None, None, 0, C.byref(count), None), "slrhip_camera_rays")
+        return count.value
+
+    def render_features(self, channels, spp, spp_begin=0, stream=None):
+        """Feature passes [spp_begin, spp_begin + spp) of every pixel of the shard (slrhip_render_features): ordered on `stream`
+        (a torch stream, a raw handle, None = the null stream), returns at once."""
+        _check(self.lib, self.lib.slrhip_render_features(self.handle, channels, spp_begin, spp, self._stream_handle(stream)), "slrhip_render_features")
+
+    def features_status(self, stream=None):
+        bits = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_features_status(self.handle, C.byref(bits), self._stream_handle(stream)), "slrhip_features_status")
+        return bits.value
+
+    def features_into(self, channel, device_ptr, num_elements, stream=None):
+        """One channel into device memory at `device_ptr` (slrhip_resolve_features), ordered on `stream`."""
+        _check(self.lib, self.lib.slrhip_resolve_features(self.handle, channel, device_ptr, num_elements, self._stream_handle(stream)),
+               "slrhip_resolve_features")
+
+    def features(self, channel):
+        """One channel as a numpy array [height, width, k] (k = 3, or [height, width] for DISTANCE / COVERAGE; float32, IDS:
+        uint32): the per-pixel sums in pass order, zeros (IDS: 0xFFFFFFFF) outside the shard.  Synchronises, and raises if the
+        feature error word is set."""
+        if channel not in abi.FEATURE_CHANNELS:
+            raise ValueError("channel: one abi.FEATURE_* bit expected")
+        _, k, dt = abi.FEATURE_CHANNELS[channel]
+        h, w = self.settings.image_height, self.settings.image_width
+        out = np.empty((h, w, k), dt)
+        _check(self.lib, self.lib.slrhip_read_features(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_features")
+        return out if k == 3 else out[:, :, 0]
+
+    def camera_rays(self, pass_, device=False, stream=None):
+        """The camera rays of sample `pass_` of every pixel of the shard (slrhip_camera_rays): (rows, pixel_xy), rows [n, 8] float32
+        in the format intersect_rays takes, pixel_xy [n] = x | y << 16.  Numpy arrays by default (the call synchronises);
+        device=True: torch CUDA tensors (float32, int32) written in order on `stream` (default: torch.cuda.current_stream()),
+        returned at once."""
+        n = self._num_pixels()
+        count = C.c_uint32(0)
+        if device:
+            import torch
+            s = stream if stream is not None else torch.cuda.current_stream(self.device)
+            with torch.cuda.stream(s):
+                rows = torch.empty((n, 8), dtype=torch.float32, device="cuda:%d" % self.device)
+                xy = torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self.device)
+                _check(self.lib, self.lib.slrhip_camera_rays(self.handle, pass_, rows.data_ptr(), xy.data_ptr(), n, C.byref(count), s.cuda_stream),
+                       "slrhip_camera_rays")
+            return rows, xy
+        rows, xy = np.empty((n, 8), np.float32), np.empty((n,), np.uint32)
+        hip = _hip_runtime()
+        pr, px = C.c_void_p(), C.c_void_p()
+        try:
+            _hip_check(hip.hipMalloc(C.byref(pr), max(rows.nbytes, 16)), "hipMalloc")
+            _hip_check(hip.hipMalloc(C.byref(px), max(xy.nbytes, 16)), "hipMalloc")
+            _check(self.lib, self.lib.slrhip_camera_rays(self.handle, pass_, pr.value, px.value, n, C.byref(count), None), "slrhip_camera_rays")
+            self.synchronize()
+            _hip_check(hip.hipMemcpy(rows.ctypes.data, pr.value, rows.nbytes, 2), "hipMemcpy")
+            _hip_check(hip.hipMemcpy(xy.ctypes.data, px.value, xy.nbytes, 2), "hipMemcpy")
+        finally:
+            for p in (pr, px):
+                if p.value:
+                    hip.hipFree(p)
+        return rows, xy
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

@@ -248,4 +248,52 @@ void PathTracingRenderer::render(const Scene& scene, const RenderSettings& setti
     slrhip_destroy(ctx);
 }
 
+void DebugRenderer::render(const Scene& scene, const RenderSettings& settings) const {
+    slrhip_config cfg = {m_device, SLRHIP_MODE_RGB, 0, 0};
+    slrhip_ctx* ctx = nullptr;
+    int rc = slrhip_create(&cfg, &ctx);
+    if (rc) die("slrhip_create", rc);
+    slrhip_scene_desc desc = scene.desc();
+    if ((rc = slrhip_upload_scene(ctx, &desc))) die("slrhip_upload_scene", rc);
+    slrhip_render_settings st;
+    st.image_width = settings.getInt(RenderSettingItem::ImageWidth);
+    st.image_height = settings.getInt(RenderSettingItem::ImageHeight);
+    st.time_start = settings.getFloat(RenderSettingItem::TimeStart);
+    st.time_end = settings.getFloat(RenderSettingItem::TimeEnd);
+    st.brightness = settings.getFloat(RenderSettingItem::Brightness);
+    st.rng_seed = settings.getInt(RenderSettingItem::RNGSeed);
+    slrhip_shard whole = {0, 1};
+    if ((rc = slrhip_render_begin(ctx, &st, whole))) die("slrhip_render_begin", rc);
+    if ((rc = slrhip_render_features(ctx, m_channels | SLRHIP_FEATURE_COVERAGE, 0, m_samplesPerPixel, nullptr))) die("slrhip_render_features", rc);
+
+    const uint32_t w = (uint32_t)st.image_width, h = (uint32_t)st.image_height;
+    const size_t pixels = (size_t)w * h;
+    std::vector<float> coverage(pixels), sums(pixels * 3);
+    if ((rc = slrhip_read_features(ctx, SLRHIP_FEATURE_COVERAGE, coverage.data(), pixels))) die("slrhip_read_features", rc);
+    const uint32_t byteWidth = 3u * w + w % 4u;
+    std::vector<uint8_t> bmp((size_t)byteWidth * h);
+    const struct { uint32_t channel; const char* file; } outputs[3] = {{SLRHIP_FEATURE_GEOMETRIC_NORMAL, "geometric_normal.bmp"},
+                                                                       {SLRHIP_FEATURE_SHADING_NORMAL, "shading_normal.bmp"},
+                                                                       {SLRHIP_FEATURE_SHADING_TANGENT, "shading_tangent.bmp"}};
+    for (const auto& o : outputs) {
+        if (!(m_channels & o.channel)) continue;
+        if ((rc = slrhip_read_features(ctx, o.channel, sums.data(), sums.size()))) die("slrhip_read_features", rc);
+        for (uint32_t y = 0; y < h; ++y) {
+            uint8_t* row = bmp.data() + (size_t)(h - 1 - y) * byteWidth;              // bottom-up, BGR
+            for (uint32_t x = 0; x < w; ++x) {
+                const size_t p = (size_t)y * w + x;
+                for (int c = 0; c < 3; ++c) {
+                    const float mean = coverage[p] > 0.0f ? sums[3 * p + c] / coverage[p] : 0.0f;
+                    const float v = (0.5f * mean + 0.5f) * 255.0f;
+                    row[3 * x + (2 - c)] = (uint8_t)(v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v);
+                }
+            }
+        }
+        const std::string path = m_outputDir + "/" + o.file;
+        if ((rc = slrhip_save_bmp(path.c_str(), bmp.data(), st.image_width, st.image_height))) die("slrhip_save_bmp", rc);
+        std::printf("debug: %s, %u passes\n", o.file, m_samplesPerPixel);
+    }
+    slrhip_destroy(ctx);
+}
+
 } // namespace SLRHip

@@ -111,4 +111,18 @@ public:
     void render(const Scene& scene, const RenderSettings& settings) const override;
 };
 
+// DebugRenderer (Renderers/DebugRenderer.h:18-61): the first-hit channels of the path tracer's own camera rays.  channels:
+// SLRHIP_FEATURE_* bits; writes geometric_normal.bmp / shading_normal.bmp / shading_tangent.bmp (DebugRenderer.cpp:112-127) with
+// its encoding (uint8)clamp((0.5 n + 0.5) * 255, 0, 255) of the per-pixel mean (:162-185) for the vector channels asked for.
+class DebugRenderer : public Renderer {
+    uint32_t m_channels;
+    uint32_t m_samplesPerPixel;
+    int m_device;
+    std::string m_outputDir;
+public:
+    explicit DebugRenderer(uint32_t channels, uint32_t spp = 1, int device = 0, const std::string& outputDir = ".")
+        : m_channels(channels), m_samplesPerPixel(spp), m_device(device), m_outputDir(outputDir) {}
+    void render(const Scene& scene, const RenderSettings& settings) const override;
+};
+
 } // namespace SLRHip

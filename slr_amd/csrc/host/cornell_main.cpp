@@ -34,5 +34,10 @@ int main(int argc, char** argv) {
 
     std::unique_ptr<Renderer> renderer(new PathTracingRenderer(spp, 0, outdir, spectral ? SLRHIP_MODE_SPECTRAL : SLRHIP_MODE_RGB));
     renderer->render(scene, settings);
+    // a seventh argument "debug": also the DebugRenderer's three normal images of the same scene and passes
+    if (argc > 7 && std::string(argv[7]) == "debug") {
+        renderer.reset(new DebugRenderer(SLRHIP_FEATURE_GEOMETRIC_NORMAL | SLRHIP_FEATURE_SHADING_NORMAL | SLRHIP_FEATURE_SHADING_TANGENT, spp, 0, outdir));
+        renderer->render(scene, settings);
+    }
     return 0;
 }

@@ -1,0 +1,58 @@
+// pt_camera.h — the camera half of Job::kernel (Renderers/PathTracingRenderer.cpp:100-120) as device functions: the sample's
+// draws and PerspectiveCamera::sample + PerspectiveIDF::sample (Cameras/PerspectiveCamera.cpp:33-74).  One statement of the
+// reference's arithmetic, used by the path tracer's startSample (pt_shade_kernels.h), by the feature pass and by
+// slrhip_camera_rays (k_features_ws, k_camera_rays: pt_trace_ws.hip).
+#pragma once
+#include "pt_device.h"
+
+namespace slrhip {
+
+// What Job::kernel draws before the camera is sampled, in source (left-to-right) order: time, pixel x, pixel y, wavelength
+// offset, wavelength selection, two lens draws.  The stream is left where the path's first bounce goes on.
+struct CameraDraws {
+    float px, py;               // p.x, p.y: the jittered position on the image, in pixels
+    float wlOffset, uLambda;    // WavelengthSamples::createWithEqualOffsets (RGBTypes.h:37-45 / SpectrumTypes.h:54-64)
+    float lu0, lu1;             // LensPosSample
+};
+SLR_DEV CameraDraws drawCameraSample(Rng& rng, int32_t rngSeed, uint32_t px, uint32_t py, uint32_t pass, float timeStart, float timeEnd) {
+    rng.seed(sampleSeed(rngSeed, px, py, pass));
+    float v = rng.nextFloat();
+    float time = timeStart * (1 - v) + timeEnd * v;
+    (void)time;
+    CameraDraws d;
+    d.px = px + rng.nextFloat();
+    d.py = py + rng.nextFloat();
+    d.wlOffset = rng.nextFloat();
+    d.uLambda = rng.nextFloat();
+    d.lu0 = rng.nextFloat();
+    d.lu1 = rng.nextFloat();
+    return d;
+}
+
+struct CameraRay {
+    V3 org, dir;                // world space; the ray is Ray(org, dir, time) with distMin 0 and distMax INFINITY
+    V3 lensN;                   // the lens surface's normal in world space
+    float dirLocalZ;            // z of the direction in camera space (PerspectiveIDF's dirPDF needs it)
+};
+// PerspectiveCamera::sample (PerspectiveCamera.cpp:33-57), then PerspectiveIDF::sample (:63-74) with IDFSample(p.x / W, p.y / H)
+SLR_DEV CameraRay sampleCameraRay(const DevCamera& cam, uint32_t imageWidth, uint32_t imageHeight, const CameraDraws& d) {
+    float lx, ly;
+    concentricSampleDisk(d.lu0, d.lu1, &lx, &ly);
+    V3 orgLocal(cam.lensRadius * lx, cam.lensRadius * ly, 0.0f);
+    CameraRay r;
+    r.org = mulPoint(cam.mat, orgLocal);
+    r.lensN = mulNormal(cam.matInv, V3(0, 0, 1));
+    Frame lf;
+    lf.z = r.lensN;
+    lf.x = mulVector(cam.mat, V3(1, 0, 0));
+    lf.y = cross(lf.z, lf.x);
+    float sx = d.px / (float)imageWidth;
+    float sy = d.py / (float)imageHeight;
+    V3 pFocus(cam.opWidth * (0.5f - sx), cam.opHeight * (0.5f - sy), cam.objPlaneDistance);
+    V3 dirLocal = normalize(pFocus - orgLocal);
+    r.dirLocalZ = dirLocal.z;
+    r.dir = lf.fromLocal(dirLocal);
+    return r;
+}
+
+} // namespace slrhip

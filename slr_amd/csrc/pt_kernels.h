@@ -260,4 +260,29 @@ int traceWsBlocksPerCU(bool quantizedTree);
 void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,
                    int numCUs, hipStream_t stream);
 
+// First-hit feature pass (slrhip_render_features; pt_trace_ws.hip): the passes [passBegin, passBegin + numPasses) of every pixel of
+// the shard in one launch.  records: numPixels x numPasses float4 {triangle, instance, dist, b1}, pass-major; b2: as many floats,
+// or nullptr when no vector channel is asked for (see WsFeatureIO).
+struct FeatureParams {
+    const uint32_t* pixelXY;      // pixel-of-shard -> x | y << 16 (the render's list)
+    float4* records;
+    float* b2;
+    uint32_t* errorWord;          // ERR_* bits of the feature passes, sticky since slrhip_render_begin
+    uint32_t numPixels, numPasses, passBegin;
+    uint32_t channels;            // SLRHIP_FEATURE_* bits of this call
+    int32_t rngSeed;
+    float timeStart, timeEnd;
+    uint32_t imageWidth, imageHeight;
+};
+// per pixel of the shard: plain float32 sums in pass order; .w of the three: distance, coverage, unused
+struct FeatureSums {
+    float4* geometric;
+    float4* shading;
+    float4* tangent;
+    uint4* ids;                   // triangle, instance, material of the highest pass rendered so far
+};
+void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream);
+void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays, uint32_t* pixelXY, hipStream_t stream);
+void launchFeatureResolve(const FeatureParams& fp, const FeatureSums& sums, uint32_t channel, void* dst, hipStream_t stream);
+
 } // namespace slrhip

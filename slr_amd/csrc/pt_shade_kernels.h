@@ -27,7 +27,9 @@
 
 #include "pt_bsdf.h"
 #include "pt_bsdf_multi.h"
+#include "pt_camera.h"
 #include "pt_kernels.h"
+#include "pt_surface.h"
 #include "pt_tex.h"
 
 namespace slrhip {
@@ -141,15 +143,6 @@ __device__ __forceinline__ void blockPush(PushLds& pl, bool emit, uint32_t slot,
         queue[(size_t)shard * shardCapacity + off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = slot;
     }
 }
-
-struct SurfPt {       // Core/geometry.h:239-258 (fields the path uses)
-    V3 p;
-    V3 gNormal;
-    Frame frame;
-    uint32_t material;
-    int32_t light;
-    float areaPDF;
-};
 
 // RegularConstantDiscrete1D::sample, Core/distributions.cpp:97-107
 __device__ __forceinline__ uint32_t selectLight(const DevScene& sc, const float* cdf, const float* pmf, float u, float* prob) {
@@ -600,46 +593,19 @@ __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers&
             surf.light = (int32_t)__float_as_uint(q1.w);
             surf.areaPDF = q2.w;
             m = MatIO<S>::template load<LDS_TABLES>(sc, lds.mats, surf.material, wlOffset);
-            // the hit record carries Moller-Trumbore's (b1, b2); Intersection::u = b0 = 1 - b1 - b2 as Triangle::intersect
-            // computes it (TriangleMesh.cpp:159), and getSurfacePoint re-derives ITS b2 from (u, v) (:190-191)
+            // the hit record carries Moller-Trumbore's (b1, b2)
             const float b1 = h.z, b2hit = h.w;
-            const float b0 = 1.0f - b1 - b2hit;
-            const float b2 = 1.0f - b0 - b1;
             if constexpr (TEX) {
                 // texCoord from the original barycentrics (TriangleMesh.cpp:160-161), then the textures of this material
                 const float4 uvA = sc.triUV[(size_t)tri * 2], uvB = sc.triUV[(size_t)tri * 2 + 1];
                 hitTexCoord(uvA, uvB, b1, b2hit, &texU, &texV);
                 if (m.type & kMatTexturedBit) normalMap = texturize(m, surf.material);
             }
-            surf.frame.z = normalize(b0 * xyz(q0) + b1 * xyz(q1) + b2 * xyz(q2));
-            surf.frame.x = normalize(b0 * xyz(q3) + b1 * xyz(q4) + b2 * xyz(q5));
-            const float dotNT = dot(surf.frame.z, surf.frame.x);
-            if (fabsf(dotNT) >= 0.01f) surf.frame.x = normalize(surf.frame.x - dotNT * surf.frame.z);
-            surf.frame.y = cross(surf.frame.z, surf.frame.x);
+            surf.frame = triangleShadingFrame(q0, q1, q2, q3, q4, q5, b1, b2hit);
             if constexpr (TEX) {
-                if (normalMap >= 0) {
-                    // BumpSingleSurfaceObject::getSurfacePoint, Core/SurfaceObject.cpp:123-134
-                    const DevTexture nt = loadTexture(sc.textures, (uint32_t)normalMap);
-                    float uc, vc;
-                    checkerNormalComponents(nt, texU, texV, &uc, &vc);
-                    const V3 nLocal = normalize(V3(uc, vc, 1.0f));
-                    const V3 tLocal = V3(1.0f, 0.0f, 0.0f) - dot(nLocal, V3(1.0f, 0.0f, 0.0f)) * nLocal;
-                    const V3 bLocal = V3(0.0f, 1.0f, 0.0f) - dot(nLocal, V3(0.0f, 1.0f, 0.0f)) * nLocal;
-                    const V3 tt = normalize(surf.frame.fromLocal(tLocal));
-                    const V3 bb = normalize(surf.frame.fromLocal(bLocal));
-                    const V3 nn = normalize(surf.frame.fromLocal(nLocal));
-                    surf.frame.x = tt; surf.frame.y = bb; surf.frame.z = nn;
-                }
+                if (normalMap >= 0) bumpShadingFrame(sc.textures, (uint32_t)normalMap, texU, texV, surf.frame);
             }
-            if (instMats) {
-                // *surfPt = sampledTF * *surfPt (SurfaceObject.cpp:329-336; SurfacePoint x StaticTransform, geometry.cpp:63-78): p as a
-                // point, the geometric normal through the inverse transpose (Transform.h:47-52), the frame's axes as vectors, re-normalised
-                surf.p = mulPoint(instMats, surf.p);
-                surf.gNormal = normalize(mulNormal(instMats + 16, surf.gNormal));
-                surf.frame.x = normalize(mulVector(instMats, surf.frame.x));
-                surf.frame.y = normalize(mulVector(instMats, surf.frame.y));
-                surf.frame.z = normalize(mulVector(instMats, surf.frame.z));
-            }
+            if (instMats) instanceSurfaceToWorld(instMats, surf);
             haveSurf = true;
             dirOut_sn = surf.frame.toLocal(-rayDir);
             if (surf.light >= 0) {
@@ -902,37 +868,16 @@ __device__ __forceinline__ void startSample(const DevScene& sc, const PathBuffer
     const uint32_t xy = pb.pixelXY[pix];
     const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
     Rng rng;
-    rng.seed(sampleSeed(rp.rngSeed, px, py, rp.sppBegin + passOfWindow));
-    float v = rng.nextFloat();
-    float time = rp.timeStart * (1 - v) + rp.timeEnd * v;
-    (void)time;
-    float pxx = px + rng.nextFloat();
-    float pyy = py + rng.nextFloat();
+    const CameraDraws draws = drawCameraSample(rng, rp.rngSeed, px, py, rp.sppBegin + passOfWindow, rp.timeStart, rp.timeEnd);
     // createWithEqualOffsets: RGBTypes.h:37-45 (offset unused, PDF 1) / SpectrumTypes.h:54-64 (PDF N / 470)
-    const float wlOffset = rng.nextFloat();
-    float uLambda = rng.nextFloat();
-    const uint32_t wl = min((uint32_t)(uint16_t)(S::N * uLambda), (uint32_t)(S::N - 1));
+    const float wlOffset = draws.wlOffset;
+    const uint32_t wl = min((uint32_t)(uint16_t)(S::N * draws.uLambda), (uint32_t)(S::N - 1));
     const float selectWLPDF = S::N == 3 ? 1.0f : S::N / (830.0f - 360.0f);
-    float lu0 = rng.nextFloat();
-    float lu1 = rng.nextFloat();
-    // PerspectiveCamera::sample PerspectiveCamera.cpp:33-57
-    float lx, ly;
-    concentricSampleDisk(lu0, lu1, &lx, &ly);
-    V3 orgLocal(sc.camera.lensRadius * lx, sc.camera.lensRadius * ly, 0.0f);
-    V3 lensP = mulPoint(sc.camera.mat, orgLocal);
-    V3 lensN = mulNormal(sc.camera.matInv, V3(0, 0, 1));
-    Frame lf;
-    lf.z = lensN;
-    lf.x = mulVector(sc.camera.mat, V3(1, 0, 0));
-    lf.y = cross(lf.z, lf.x);
-    // PerspectiveIDF::sample :63-74 with IDFSample(p.x / W, p.y / H)
-    float sx = pxx / (float)rp.imageWidth;
-    float sy = pyy / (float)rp.imageHeight;
-    V3 pFocus(sc.camera.opWidth * (0.5f - sx), sc.camera.opHeight * (0.5f - sy), sc.camera.objPlaneDistance);
-    V3 dirLocal = normalize(pFocus - orgLocal);
+    // PerspectiveCamera::sample + PerspectiveIDF::sample (pt_camera.h)
+    const CameraRay cam = sampleCameraRay(sc.camera, rp.imageWidth, rp.imageHeight, draws);
+    const V3 lensP = cam.org, lensN = cam.lensN, rayDir = cam.dir;
     float dirPDF = sc.camera.imgPlaneDistance * sc.camera.imgPlaneDistance /
-                   ((dirLocal.z * dirLocal.z * dirLocal.z) * sc.camera.imgPlaneArea);
-    V3 rayDir = lf.fromLocal(dirLocal);
+                   ((cam.dirLocalZ * cam.dirLocalZ * cam.dirLocalZ) * sc.camera.imgPlaneArea);
     // weight :126
     float camWeight = absDot(rayDir, lensN) / (sc.camera.areaPDF * dirPDF * selectWLPDF);
     pb.flags[slot] = F_MAKE((uint32_t)ST_FIRST_HIT, 0u, wl, 0u, 0u, 0u);

@@ -22,8 +22,10 @@
 
 #include <algorithm>
 
+#include "pt_camera.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
+#include "pt_surface.h"
 #include "pt_tex.h"
 
 namespace slrhip {
@@ -781,12 +783,13 @@ void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams
 }
 
 // ---- ray queries: the same consumer fed from a caller's ray array ----------------------------------------------------------
-// The producer of a query launch streams contiguous ray indices: workgroup b takes the 128-ray chunks b, b + gridDim, ... (the
-// grid is the render's resident grid, so every workgroup is resident and the chunks of one workgroup are its share).  A chunk's
-// two 32-byte records per lane are loaded before the wait for ring space, so the loads overlap it.  Every index is a ray: no
-// state flags, no queue.  tag = kShadowBit for visibility queries.
-template <class LDS>
-__device__ __forceinline__ void wsProduceRays(const WsQueryIO& io, uint32_t n, uint32_t tag, LDS& lds, WsDebug& dbg) {
+// The producer of a launch whose rays are numbered 0 .. n-1 (ray queries: indices into the caller's array; feature pass: samples of
+// the window): workgroup b takes the 128-ray chunks b, b + gridDim, ... (the grid is the render's resident grid, so every
+// workgroup is resident and the chunks of one workgroup are its share).  makeRay(i, o, d) loads or computes ray i; a chunk's rays
+// are made before the wait for ring space, so that their loads overlap it.  Every index is a ray: no state flags, no queue.
+// tag = kShadowBit for visibility queries.
+template <class LDS, class MakeRay>
+__device__ __forceinline__ void wsProduceIndexed(uint32_t n, uint32_t tag, uint32_t* errorWord, LDS& lds, WsDebug& dbg, const MakeRay& makeRay) {
     const uint32_t lane = threadIdx.x;
     const uint32_t chunk = kSub * 64;
     const uint32_t numChunks = (n + chunk - 1) / chunk;           // n < 2^31: c * chunk + 127 stays inside 32 bits
@@ -798,10 +801,10 @@ __device__ __forceinline__ void wsProduceRays(const WsQueryIO& io, uint32_t n, u
         for (int j = 0; j < kSub; ++j) {
             const uint32_t i = c * chunk + j * 64 + lane;
             live[j] = i < n;
-            o[j] = live[j] ? ntLoad4(&io.rays[2 * (size_t)i]) : make_float4(0, 0, 0, 0);
-            d[j] = live[j] ? ntLoad4(&io.rays[2 * (size_t)i + 1]) : make_float4(0, 0, 0, 0);
+            o[j] = make_float4(0, 0, 0, 0); d[j] = make_float4(0, 0, 0, 0);
+            if (live[j]) makeRay(i, o[j], d[j]);
         }
-        if (!wsWaitSpace(lds, tailLocal, chunk, &dbg.producerWaits)) { if (lane == 0) atomicOr(io.errorWord, ERR_RING_SPACE); break; }
+        if (!wsWaitSpace(lds, tailLocal, chunk, &dbg.producerWaits)) { if (lane == 0) atomicOr(errorWord, ERR_RING_SPACE); break; }
 #pragma unroll
         for (int j = 0; j < kSub; ++j) tailLocal += wsAppend(lds, tailLocal, live[j], (c * chunk + j * 64 + lane) | tag, o[j], d[j]);
         WS_STORE(&lds.tail, tailLocal, __ATOMIC_RELEASE);
@@ -816,7 +819,8 @@ __global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8
     __syncthreads();
     WsCounts cnt;
     WsDebug dbg;
-    if (threadIdx.x < 64) wsProduceRays(io, n, tag, lds, dbg);
+    if (threadIdx.x < 64)
+        wsProduceIndexed(n, tag, io.errorWord, lds, dbg, [&](uint32_t i, float4& o, float4& d) { o = ntLoad4(&io.rays[2 * (size_t)i]); d = ntLoad4(&io.rays[2 * (size_t)i + 1]); });
     else wsConsume<false, NC, QUANT, false, INST>(sc, io, lds, refill, 0u, cnt, dbg);       // no staged top nodes (numTop = 0)
 }
 
@@ -840,6 +844,158 @@ void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* h
     if (nc == 15) launchQueryWsT<15>(sc, io, n, tag, blocks, stream);
     else if (nc == 7) launchQueryWsT<7>(sc, io, n, tag, blocks, stream);
     else launchQueryWsT<3>(sc, io, n, tag, blocks, stream);
+}
+
+// ---- first-hit feature pass (slrhip_render_features, slrhip_camera_rays): the same consumer fed with camera rays made on the spot ----
+// A ring entry is a sample of the launch's window, index = pass of the window x pixels of the shard + pixel of the shard (< 2^31:
+// the host sizes the windows).  The producer wave GENERATES the camera ray of each index into the LDS ring — the path tracer's own
+// draws and camera arithmetic (pt_camera.h) — so no ray array exists in HBM; the consumer's finish writes the sample's hit record, and
+// k_feature_fold computes the surface point of each hit (pt_surface.h, as logicSlot does) and adds it to the pixel in pass order.
+SLR_DEV void featureCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+    const uint32_t pass = index / fp.numPixels, pix = index - pass * fp.numPixels;
+    xy = fp.pixelXY[pix];
+    Rng rng;
+    const CameraDraws draws = drawCameraSample(rng, fp.rngSeed, xy & 0xFFFFu, xy >> 16, fp.passBegin + pass, fp.timeStart, fp.timeEnd);
+    const CameraRay r = sampleCameraRay(cam, fp.imageWidth, fp.imageHeight, draws);
+    o = make_float4(r.org.x, r.org.y, r.org.z, 0.0f);
+    d = make_float4(r.dir.x, r.dir.y, r.dir.z, INFINITY);
+}
+
+// The consumer's side of the feature pass: the hit record of the sample, as the query kernel writes it, plus the instance — the
+// record plane {triangle, instance, dist, b1} and, when a vector channel is asked for, Moller-Trumbore's b2 in a float plane.  The
+// surface point is computed by the fold kernel, one lane per pixel: with it inside `finish` (inlined at the two places a lane can
+// finish) the instanced instantiation spilled 20 registers and wrote 64 B per sample; measured in DESIGN.md 7.9.
+struct WsFeatureIO {
+    const DevScene& sc;
+    const FeatureParams& fp;
+    uint32_t* const& errorWord;           // the feature passes' own error word (not the render's, not the queries')
+    __device__ WsFeatureIO(const DevScene& s, const FeatureParams& f) : sc(s), fp(f), errorWord(f.errorWord) {}
+    __device__ __forceinline__ void worldRay(uint32_t slot, float4& o, float4& d) const {
+        uint32_t xy;
+        featureCameraRay(sc.camera, fp, slot, o, d, xy);
+    }
+    template <bool INST>
+    __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
+        ntStore4(fp.records + slot, make_float4(__uint_as_float(hitTri), __uint_as_float((uint32_t)hitInst), hitT, hitB1));
+        if (fp.b2) __builtin_nontemporal_store(hitB2, fp.b2 + slot);
+    }
+};
+
+template <int NC, bool QUANT, bool INST>
+__global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_features_ws(DevScene sc, FeatureParams fp, uint32_t n, uint32_t refill) {
+    __shared__ WsLds<NC> lds;
+    if (threadIdx.x == 0) { lds.tail = 0; lds.reserved = 0; lds.released = 0; lds.done = 0; }
+    __syncthreads();
+    WsCounts cnt;
+    WsDebug dbg;
+    if (threadIdx.x < 64)
+        wsProduceIndexed(n, 0u, fp.errorWord, lds, dbg, [&](uint32_t i, float4& o, float4& d) { uint32_t xy; featureCameraRay(sc.camera, fp, i, o, d, xy); });
+    else wsConsume<false, NC, QUANT, false, INST>(sc, WsFeatureIO(sc, fp), lds, refill, 0u, cnt, dbg);       // no staged top nodes (numTop = 0)
+}
+
+template <int NC>
+static void launchFeaturesWsT(const DevScene& sc, const FeatureParams& fp, uint32_t n, uint32_t blocks, hipStream_t stream) {
+    const dim3 grid(blocks), block(64 * (NC + 1));
+    // the query kernels' tree choice (launchQueryWsT)
+    if (sc.instances) hipLaunchKernelGGL((k_features_ws<NC, false, true>), grid, block, 0, stream, sc, fp, n, g_refill);
+    else if (sc.nodesQ) hipLaunchKernelGGL((k_features_ws<NC, true, false>), grid, block, 0, stream, sc, fp, n, g_refill);
+    else hipLaunchKernelGGL((k_features_ws<NC, false, false>), grid, block, 0, stream, sc, fp, n, g_refill);
+}
+
+// The accumulation of a window's records: one lane owns a pixel and takes its passes in pass order — the surface point of the hit
+// (pt_surface.h: the triangle's frame, the bump map, the instance transform, as logicSlot does) for the vector channels asked for,
+// then plain float32 adds; a miss (the environment sphere included) adds nothing.  idsPass: the pass of the window whose ids
+// become the pixel's (the highest pass rendered so far), or 0xFFFFFFFF to leave them.
+__global__ __launch_bounds__(256) void k_feature_fold(DevScene sc, FeatureParams fp, FeatureSums sums, uint32_t idsPass) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= fp.numPixels) return;
+    const bool gn = (fp.channels & SLRHIP_FEATURE_GEOMETRIC_NORMAL) != 0, sn = (fp.channels & SLRHIP_FEATURE_SHADING_NORMAL) != 0,
+               tn = (fp.channels & SLRHIP_FEATURE_SHADING_TANGENT) != 0;
+    float4 g = sums.geometric[pix], s = sums.shading[pix], t = sums.tangent[pix];      // .w: distance, coverage, unused
+    for (uint32_t p = 0; p < fp.numPasses; ++p) {
+        const size_t e = (size_t)p * fp.numPixels + pix;
+        const float4 r = ntLoad4(fp.records + e);
+        const uint32_t tri = __float_as_uint(r.x);
+        const bool hit = tri != 0xFFFFFFFFu;
+        const float4* st = reinterpret_cast<const float4*>(sc.shadeTris) + (size_t)(hit ? tri : 0u) * 6;
+        if (p == idsPass) sums.ids[pix] = make_uint4(tri, hit ? __float_as_uint(r.y) : 0xFFFFFFFFu, hit ? reinterpret_cast<const uint32_t*>(st)[3] : 0xFFFFFFFFu, 0u);
+        if (!hit) continue;
+        g.w += r.z;
+        s.w += 1.0f;
+        if (!(gn || sn || tn)) continue;
+        const float4 q0 = st[0], q1 = st[1], q2 = st[2], q3 = st[3], q4 = st[4], q5 = st[5];
+        const int32_t inst = (int32_t)__float_as_uint(r.y);
+        const float* instMats = sc.instances && inst >= 0 ? reinterpret_cast<const float*>(sc.instances + (size_t)inst * 9u) : nullptr;
+        if (gn) {
+            V3 n(q3.w, q4.w, q5.w);
+            if (instMats) n = instanceNormalToWorld(instMats, n);
+            g.x += n.x; g.y += n.y; g.z += n.z;
+        }
+        if (sn || tn) {
+            const float b1 = r.w, b2 = __builtin_nontemporal_load(fp.b2 + e);
+            Frame frame = triangleShadingFrame(q0, q1, q2, q3, q4, q5, b1, b2);
+            if (sc.numTextures) {
+                const int32_t normalMap = sc.matTex[__float_as_uint(q0.w)].normalMap;
+                if (normalMap >= 0) {
+                    // texCoord from the original barycentrics (TriangleMesh.cpp:160-161)
+                    const float4 uvA = sc.triUV[(size_t)tri * 2], uvB = sc.triUV[(size_t)tri * 2 + 1];
+                    float texU, texV;
+                    hitTexCoord(uvA, uvB, b1, b2, &texU, &texV);
+                    bumpShadingFrame(sc.textures, (uint32_t)normalMap, texU, texV, frame);
+                }
+            }
+            if (instMats) { frame.x = instanceAxisToWorld(instMats, frame.x); frame.z = instanceAxisToWorld(instMats, frame.z); }
+            if (sn) { s.x += frame.z.x; s.y += frame.z.y; s.z += frame.z.z; }
+            if (tn) { t.x += frame.x.x; t.y += frame.x.y; t.z += frame.x.z; }
+        }
+    }
+    sums.geometric[pix] = g; sums.shading[pix] = s; sums.tangent[pix] = t;
+}
+
+void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream) {
+    const bool quant = sc.nodesQ != nullptr && !sc.instances;
+    const uint32_t n = fp.numPixels * fp.numPasses;
+    const uint32_t chunks = (n + kSub * 64 - 1) / (kSub * 64);
+    const uint32_t blocks = std::max(1u, std::min((uint32_t)numCUs * (uint32_t)traceWsBlocksPerCU(quant), chunks));
+    const int nc = wsConsumers(quant);
+    if (nc == 15) launchFeaturesWsT<15>(sc, fp, n, blocks, stream);
+    else if (nc == 7) launchFeaturesWsT<7>(sc, fp, n, blocks, stream);
+    else launchFeaturesWsT<3>(sc, fp, n, blocks, stream);
+    hipLaunchKernelGGL(k_feature_fold, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, sc, fp, sums, idsPass);
+}
+
+// slrhip_camera_rays: the producer's half alone, written out in the public slrhip_ray format; one lane per pixel of the shard
+__global__ __launch_bounds__(256) void k_camera_rays(DevCamera cam, FeatureParams fp, float4* rays, uint32_t* pixelXY) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= fp.numPixels) return;
+    float4 o, d;
+    uint32_t xy;
+    featureCameraRay(cam, fp, pix, o, d, xy);
+    rays[2 * (size_t)pix] = o;
+    rays[2 * (size_t)pix + 1] = d;
+    if (pixelXY) pixelXY[pix] = xy;
+}
+void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays, uint32_t* pixelXY, hipStream_t stream) {
+    hipLaunchKernelGGL(k_camera_rays, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, sc.camera, fp, rays, pixelXY);
+}
+
+// slrhip_resolve_features: one channel scattered into a [height][width][k] image the caller has filled with the value of
+// "outside the shard"; channel = one SLRHIP_FEATURE_* bit
+__global__ __launch_bounds__(256) void k_feature_resolve(FeatureParams fp, FeatureSums sums, uint32_t channel, uint32_t* dst) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= fp.numPixels) return;
+    const uint32_t xy = fp.pixelXY[pix];
+    const size_t at = (size_t)(xy >> 16) * fp.imageWidth + (xy & 0xFFFFu);
+    if (channel == SLRHIP_FEATURE_IDS) { const uint4 v = sums.ids[pix]; dst[3 * at] = v.x; dst[3 * at + 1] = v.y; dst[3 * at + 2] = v.z; }
+    else if (channel == SLRHIP_FEATURE_DISTANCE) dst[at] = __float_as_uint(sums.geometric[pix].w);
+    else if (channel == SLRHIP_FEATURE_COVERAGE) dst[at] = __float_as_uint(sums.shading[pix].w);
+    else {
+        const float4 v = channel == SLRHIP_FEATURE_GEOMETRIC_NORMAL ? sums.geometric[pix] : channel == SLRHIP_FEATURE_SHADING_NORMAL ? sums.shading[pix] : sums.tangent[pix];
+        dst[3 * at] = __float_as_uint(v.x); dst[3 * at + 1] = __float_as_uint(v.y); dst[3 * at + 2] = __float_as_uint(v.z);
+    }
+}
+void launchFeatureResolve(const FeatureParams& fp, const FeatureSums& sums, uint32_t channel, void* dst, hipStream_t stream) {
+    hipLaunchKernelGGL(k_feature_resolve, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, fp, sums, channel, static_cast<uint32_t*>(dst));
 }
 
 } // namespace slrhip

@@ -153,6 +153,15 @@ struct slrhip_ctx {
     DevArray<uint64_t> totals;
     DevArray<float> resolveScratch;
     DevArray<uint32_t> queryError;                // ERR_* bits of the ray queries (slrhip_query_status); apart from the render's error word
+    // first-hit feature buffers (slrhip_render_features): allocated by the first feature call after render_begin, never by a render
+    DevArray<float4> featGeometric, featShading, featTangent, featRecords;
+    DevArray<float> featB2;
+    DevArray<uint4> featIds;
+    DevArray<uint32_t> featError;                 // ERR_* bits of the feature passes (slrhip_features_status)
+    bool featReady = false;                       // sums allocated and cleared since render_begin
+    uint32_t featChannels = 0;                    // the channel set of the feature calls since render_begin (0: none yet)
+    uint32_t featWindow = 0;                      // passes per launch (the record window)
+    uint64_t featPassEnd = 0;                     // 1 + the highest pass rendered since render_begin (whose ids the pixels hold)
     PathBuffers buffers;
     uint64_t iterations = 0;
     bool firstRenderCall = true;
@@ -627,6 +636,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->shard = shard;
     ctx->iterations = 0;
     ctx->firstRenderCall = true;
+    ctx->featReady = false; ctx->featChannels = 0; ctx->featPassEnd = 0;      // the feature accumulation restarts (its arrays are kept for reuse)
     ctx->haveRender = true;
     return SLRHIP_OK;
 }
@@ -823,6 +833,131 @@ int slrhip_query_status(slrhip_ctx* ctx, uint32_t* bits, void* stream) {
     HIP_TRY(hipSetDevice(ctx->device));
     const hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(bits, ctx->queryError.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SLRHIP_OK;
+}
+
+// ---- first-hit feature buffers (slrhip_render_features / slrhip_resolve_features / slrhip_camera_rays) -------------------------
+static const uint64_t kFeatureRecordBytes = 512ull << 20;      // the record window: 16 B per (pixel, pass), 20 B with a vector channel
+static const uint32_t kFeatureVectors = SLRHIP_FEATURE_GEOMETRIC_NORMAL | SLRHIP_FEATURE_SHADING_NORMAL | SLRHIP_FEATURE_SHADING_TANGENT;
+
+static FeatureParams featureParams(const slrhip_ctx* ctx, uint32_t channels, uint32_t passBegin, uint32_t numPasses) {
+    const RenderParams& rp = ctx->params;
+    FeatureParams fp{};
+    fp.pixelXY = ctx->pixelXY.ptr; fp.records = ctx->featRecords.ptr; fp.b2 = (channels & (kFeatureVectors & ~SLRHIP_FEATURE_GEOMETRIC_NORMAL)) ? ctx->featB2.ptr : nullptr; fp.errorWord = ctx->featError.ptr;
+    fp.numPixels = rp.numPixels; fp.numPasses = numPasses; fp.passBegin = passBegin; fp.channels = channels;
+    fp.rngSeed = rp.rngSeed; fp.timeStart = rp.timeStart; fp.timeEnd = rp.timeEnd;
+    fp.imageWidth = rp.imageWidth; fp.imageHeight = rp.imageHeight;
+    return fp;
+}
+static FeatureSums featureSums(const slrhip_ctx* ctx) { return FeatureSums{ctx->featGeometric.ptr, ctx->featShading.ptr, ctx->featTangent.ptr, ctx->featIds.ptr}; }
+
+int slrhip_render_features(slrhip_ctx* ctx, uint32_t channels, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_features: null context");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_render_features: call slrhip_render_begin first");
+    if (channels == 0 || (channels & ~SLRHIP_FEATURE_ALL)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_features: no or unknown channel bits");
+    if ((uint64_t)sppBegin + sppCount > 0xFFFFFFFFull) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_features: pass range beyond 2^32");
+    if (sppCount == 0) return SLRHIP_OK;
+    const RenderParams& rp = ctx->params;
+    // one channel set between two slrhip_render_begin calls: every channel then sums over the same passes (sum / COVERAGE is a mean)
+    if (ctx->featChannels && channels != ctx->featChannels)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_features: the channel set differs from that of the first feature call since slrhip_render_begin");
+    const bool first = ctx->featChannels == 0;
+    ctx->featChannels = channels;
+    if (rp.numPixels == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (first) {
+        // the first feature call since render_begin: the sums (cleared in stream order) and a record window whose size depends on
+        // the shard and the channel set alone, so that no later call allocates whatever its pass count
+        const size_t pixels = rp.numPixels;
+        const bool wantB2 = (channels & (kFeatureVectors & ~SLRHIP_FEATURE_GEOMETRIC_NORMAL)) != 0;
+        const uint64_t perPass = (uint64_t)pixels * (sizeof(float4) + (wantB2 ? sizeof(float) : 0));
+        ctx->featWindow = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>({kFeatureRecordBytes / perPass, 0x7FFFFFFFull / pixels, 64u}));
+        HIP_TRY(ctx->featGeometric.alloc(pixels)); HIP_TRY(ctx->featShading.alloc(pixels)); HIP_TRY(ctx->featTangent.alloc(pixels));
+        HIP_TRY(ctx->featIds.alloc(pixels)); HIP_TRY(ctx->featError.alloc(1));
+        HIP_TRY(ctx->featRecords.alloc(pixels * ctx->featWindow));
+        if (wantB2) HIP_TRY(ctx->featB2.alloc(pixels * ctx->featWindow));
+        HIP_TRY(hipMemsetAsync(ctx->featGeometric.ptr, 0, pixels * sizeof(float4), s));
+        HIP_TRY(hipMemsetAsync(ctx->featShading.ptr, 0, pixels * sizeof(float4), s));
+        HIP_TRY(hipMemsetAsync(ctx->featTangent.ptr, 0, pixels * sizeof(float4), s));
+        HIP_TRY(hipMemsetAsync(ctx->featIds.ptr, 0xFF, pixels * sizeof(uint4), s));
+        HIP_TRY(hipMemsetAsync(ctx->featError.ptr, 0, sizeof(uint32_t), s));
+        ctx->featReady = true;
+    }
+    const FeatureSums sums = featureSums(ctx);
+    for (uint32_t done = 0; done < sppCount; done += ctx->featWindow) {
+        const uint32_t n = std::min(ctx->featWindow, sppCount - done);
+        // the pixels keep the ids of the highest pass rendered so far
+        const uint64_t end = (uint64_t)sppBegin + done + n;
+        const uint32_t idsPass = end >= ctx->featPassEnd ? n - 1u : 0xFFFFFFFFu;
+        ctx->featPassEnd = std::max(ctx->featPassEnd, end);
+        launchFeatures(ctx->scene, featureParams(ctx, channels, sppBegin + done, n), sums, idsPass, ctx->numCUs, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_features(slrhip_ctx* ctx, uint32_t channel, void* deviceDst, size_t numElements, void* streamPtr) {
+    if (!ctx || !deviceDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_features: null argument");
+    if ((uintptr_t)deviceDst & 3u) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_features: misaligned pointer (4 bytes)");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_resolve_features: call slrhip_render_begin first");
+    if (channel == 0 || (channel & (channel - 1u)) || (channel & ~SLRHIP_FEATURE_ALL))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_features: `channel` must be one SLRHIP_FEATURE_* bit");
+    if (!(ctx->featChannels & channel))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_features: no slrhip_render_features call since slrhip_render_begin asked for this channel");
+    const RenderParams& rp = ctx->params;
+    const size_t k = (channel & (SLRHIP_FEATURE_DISTANCE | SLRHIP_FEATURE_COVERAGE)) ? 1u : 3u;
+    const size_t need = (size_t)rp.imageWidth * rp.imageHeight * k;
+    if (numElements < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_features: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    HIP_TRY(hipMemsetAsync(deviceDst, channel == SLRHIP_FEATURE_IDS ? 0xFF : 0, need * sizeof(uint32_t), s));
+    if (rp.numPixels) launchFeatureResolve(featureParams(ctx, channel, 0, 0), featureSums(ctx), channel, deviceDst, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_features(slrhip_ctx* ctx, uint32_t channel, void* hostDst, size_t numElements) {
+    if (!ctx || !hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_features: null argument");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_read_features: call slrhip_render_begin first");
+    const size_t need = (size_t)ctx->params.imageWidth * ctx->params.imageHeight * 3u;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->resolveScratch.alloc(need));
+    HIP_TRY(hipDeviceSynchronize());                   // feature passes queued on any stream of the caller's
+    int rc = slrhip_resolve_features(ctx, channel, ctx->resolveScratch.ptr, numElements, nullptr);
+    if (rc != SLRHIP_OK) return rc;
+    uint32_t bits = 0;
+    if ((rc = slrhip_features_status(ctx, &bits, nullptr)) != SLRHIP_OK) return rc;
+    if (bits) return fail(SLRHIP_ERR_HIP, "slrhip_read_features: the feature error word is set (a traversal gave up): " + std::to_string(bits));
+    const size_t k = (channel & (SLRHIP_FEATURE_DISTANCE | SLRHIP_FEATURE_COVERAGE)) ? 1u : 3u;
+    HIP_TRY(hipMemcpy(hostDst, ctx->resolveScratch.ptr, need / 3u * k * sizeof(float), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+int slrhip_camera_rays(slrhip_ctx* ctx, uint32_t pass, slrhip_ray* rays, uint32_t* pixelXY, uint32_t capacity, uint32_t* count, void* streamPtr) {
+    if (!ctx || !count) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_camera_rays: null context or count");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_camera_rays: call slrhip_render_begin first");
+    const RenderParams& rp = ctx->params;
+    *count = rp.numPixels;
+    if (rp.numPixels == 0 || (!rays && !pixelXY && capacity == 0)) return SLRHIP_OK;          // the count alone
+    if (!rays) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_camera_rays: null ray pointer");
+    if (((uintptr_t)rays & 15u) || ((uintptr_t)pixelXY & 3u)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_camera_rays: misaligned pointer (rays: 16 bytes; pixel_xy: 4)");
+    if (capacity < rp.numPixels)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_camera_rays: capacity " + std::to_string(capacity) + " is smaller than the shard's " + std::to_string(rp.numPixels) + " pixels");
+    HIP_TRY(hipSetDevice(ctx->device));
+    launchCameraRays(ctx->scene, featureParams(ctx, 0, pass, 1), reinterpret_cast<float4*>(rays), pixelXY, (hipStream_t)streamPtr);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream) {
+    if (!ctx || !bits) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_features_status: null argument");
+    *bits = 0;
+    if (!ctx->haveRender || !ctx->featReady) return SLRHIP_OK;          // no feature pass can have run
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(bits, ctx->featError.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return SLRHIP_OK;
 }

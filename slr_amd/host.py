@@ -5,6 +5,8 @@ Reads a scene in the reference's scene language (slr_amd/scene_language.py), ren
 behind what PathTracingRenderer::render leaves behind (PathTracingRenderer.cpp:83-94): "%03u.bmp" after 1, 2, 4, ...
 samples with scale brightness / samples, and one stdout line "%u samples: %s, %g[s]" per image, at most 16 images.
 A scene that asks for another renderer ("BPT", ...) is rendered with the path tracer and a note on stderr.
+`--features DIR` (or a scene whose renderer is "debug") also writes the first-hit feature buffers: the normal images of the
+reference's DebugRenderer and features.npz with the raw per-pixel sums.
 """
 import argparse
 import ctypes as C
@@ -16,6 +18,40 @@ import numpy as np
 
 from . import abi, binding, scene_language
 
+# setRenderer("debug", (outputs = (...))) names (libSLRSceneGraph/API.cpp:1037-1059) -> channel bits
+DEBUG_OUTPUTS = {"geometric normal": abi.FEATURE_GEOMETRIC_NORMAL, "shading normal": abi.FEATURE_SHADING_NORMAL,
+                 "shading tangent": abi.FEATURE_SHADING_TANGENT, "distance": abi.FEATURE_DISTANCE}
+
+
+def encode_normals(sums, coverage):
+    """DebugRenderer's image of a vector channel (DebugRenderer.cpp:162-185): (uint8)clamp((0.5 n + 0.5) * 255, 0, 255) of the
+    per-pixel mean over the hits (0 where nothing was hit), as the [h, w, 3] BGR bottom-up pixels a BMP holds."""
+    cov = np.asarray(coverage, np.float32)[:, :, None]
+    mean = np.where(cov > 0, np.asarray(sums, np.float32) / np.maximum(cov, np.float32(1)), np.float32(0)).astype(np.float32)
+    rgb = np.clip((np.float32(0.5) * mean + np.float32(0.5)) * np.float32(255), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(rgb[::-1, :, ::-1])
+
+
+def save_bmp(path, bgr_bottom_up):
+    """[h, w, 3] uint8 BGR bottom-up pixels through slrhip_save_bmp (rows padded as it expects them)."""
+    h, w, _ = bgr_bottom_up.shape
+    rows = np.zeros((h, 3 * w + w % 4), np.uint8)
+    rows[:, :3 * w] = bgr_bottom_up.reshape(h, 3 * w)
+    lib = binding.load_library()
+    binding._check(lib, lib.slrhip_save_bmp(path.encode(), rows.ctypes.data, w, h), "slrhip_save_bmp")
+
+
+def write_features(ctx, spp, out_dir, channels):
+    """The feature buffers of `spp` passes next to the beauty frame: geometric_normal.bmp, shading_normal.bmp, shading_tangent.bmp
+    (DebugRenderer's file names, DebugRenderer.cpp:112-127) for the vector channels asked for, and features.npz with the raw sums."""
+    ctx.render_features(channels | abi.FEATURE_COVERAGE, spp)
+    raw = {abi.FEATURE_CHANNELS[c][0]: ctx.features(c) for c in abi.FEATURE_CHANNELS if c & (channels | abi.FEATURE_COVERAGE)}
+    for c in (abi.FEATURE_GEOMETRIC_NORMAL, abi.FEATURE_SHADING_NORMAL, abi.FEATURE_SHADING_TANGENT):
+        name = abi.FEATURE_CHANNELS[c][0]
+        if name in raw:
+            save_bmp(os.path.join(out_dir, name + ".bmp"), encode_normals(raw[name], raw["coverage"]))
+    np.savez(os.path.join(out_dir, "features.npz"), **raw)
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m slr_amd.host")
@@ -24,6 +60,8 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=0, help="override the script's sample count")
     ap.add_argument("--out", default=".")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--features", metavar="DIR", default=None,
+                    help="also write the first-hit feature buffers (normal BMPs as the reference's DebugRenderer names them, features.npz) to DIR")
     args = ap.parse_args(argv)
 
     try:
@@ -31,7 +69,14 @@ def main(argv=None):
     except scene_language.SceneLanguageError as e:
         print("failed to read the scene: %s" % e, file=sys.stderr)
         return -1                                                            # main.cpp:39-42
-    if renderer["method"] != "PT":
+    feature_dir, feature_channels = args.features, abi.FEATURE_ALL
+    if renderer["method"] == "debug":
+        # the beauty frame is rendered as before; the debug renderer's outputs are written next to it
+        feature_dir = feature_dir or args.out
+        feature_channels = 0
+        for name in renderer.get("outputs") or DEBUG_OUTPUTS:
+            feature_channels |= DEBUG_OUTPUTS[name]
+    elif renderer["method"] != "PT":
         print("note: the scene asks for %r; only the unidirectional path tracer is built, rendering with it" % renderer["method"], file=sys.stderr)
     spp = args.samples or int(renderer["samples"])
     st = abi.RenderSettings(int(settings["width"]), int(settings["height"]), float(settings["timeStart"]), float(settings["timeEnd"]),
@@ -59,6 +104,9 @@ def main(argv=None):
             print("%u samples: %s, %g[s]" % (export, name, time.time() - start), flush=True)
             img += 1
             export += export
+    if feature_dir is not None:
+        os.makedirs(feature_dir, exist_ok=True)
+        write_features(ctx, spp, feature_dir, feature_channels)
     ctx.close()
     return 0
 

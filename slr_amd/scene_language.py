@@ -596,10 +596,19 @@ class Interpreter:
     def _set_renderer(self, a):
         method = a["method"]        # recorded as written; only "PT" (the unidirectional path tracer) exists in this build,
         samples = 8                 # so a caller that renders a "BPT" scene does so with PT and should say so
+        outputs = None              # "debug" (DebugRenderer, API.cpp:1037-1059): outputs = ("geometric normal", "shading normal", ...)
         for k, v in a["config"].items:
             if k == "samples":
                 samples = int(v)
+            elif k == "outputs" and method == "debug":
+                outputs = [str(x) for x in (v.unnamed() if isinstance(v, Tuple) else [v])]
+                known = ("geometric normal", "shading normal", "shading tangent", "distance")
+                for name in outputs:
+                    if name not in known:
+                        raise SceneLanguageError("setRenderer(\"debug\"): unknown output %r" % name)
         self.renderer = {"method": method, "samples": samples}
+        if method == "debug":
+            self.renderer["outputs"] = outputs
 
     def _create_emitter(self, a):
         if a["type"] != "diffuse":
