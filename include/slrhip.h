@@ -555,6 +555,91 @@ int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
 
+/* ---- per-pixel noise statistics and rendering to a noise target ------------------------------------------------------------
+ * How noisy is the frame, and when is it good enough?  The reference leaves that to a human looking at the BMPs it writes after
+ * 1, 2, 4, ... passes (PathTracingRenderer.cpp:83-94).  With statistics on, the pass that adds a window's samples to the sensor
+ * (ImageSensor::add, in pass order) also keeps, per pixel of the shard, the running moments of the samples' LUMINANCE: one
+ * 16-byte record {mean, M2, n, max}, updated per sample with float32 Welford steps in pass order,
+ *     n += 1;  d = Y - mean;  mean = mean + d / (float)n;  M2 = M2 + d * (Y - mean);  max = fmaxf(max, Y);
+ * (IEEE division; a non-finite sample is not filtered and propagates into the mean).  Like the frame, the records depend on the
+ * (pixel, pass) samples alone: not on the slot count, the shard split, the result windows, how the passes are cut into
+ * slrhip_render calls (ascending) or scheduling — not even in the last bit.  A render that does not ask for statistics launches
+ * the kernels it launched before and produces the same bits; with statistics on, the frame, the counters and the error word
+ * are unchanged in every bit.  Not built: per-pixel adaptive sampling (pixels with different pass counts would change the work
+ * queues); every pixel always gets the same passes.
+ *
+ * The luminance of a sample = of its result-window entry, weight x C as ImageSensor::add receives it (un-normalised: not
+ * divided by the pass count, no brightness, no sensitivity, no clamp), with the constants of slrhip_tonemap_bgr8:
+ *   3 components:  Y = (float)(0.222485 * r + 0.716905 * g + 0.060610 * b)     (double literals, float operands; saveImage's Y)
+ *   16 components: p_q = ((w[4q] v[4q] + w[4q+1] v[4q+1]) + w[4q+2] v[4q+2]) + w[4q+3] v[4q+3] for q = 0..3 in float32, with w =
+ *                  DiscretizedSpectrum::ybar (16 strata); Y = ((p_0 + p_1) + (p_2 + p_3)) / integralCMF.
+ * Pure function; the kernels evaluate the same expression.  Other component counts return NaN.                              */
+float slrhip_sample_luminance(int32_t components, const float* values);
+
+/* Channels of slrhip_resolve_statistics / slrhip_read_statistics (ONE bit per call), each [height][width] float32:          */
+#define SLRHIP_STATISTICS_MEAN             1u   /* mean of the pixel's sample luminances                                     */
+#define SLRHIP_STATISTICS_VARIANCE         2u   /* sample variance M2 / (n - 1); 0 while n < 2                                */
+#define SLRHIP_STATISTICS_VARIANCE_OF_MEAN 4u   /* M2 / ((n - 1) n), the divisor a float32 product; 0 while n < 2            */
+#define SLRHIP_STATISTICS_COUNT            8u   /* n, as float                                                               */
+#define SLRHIP_STATISTICS_MAX             16u   /* largest sample luminance (0 before the first sample)                      */
+#define SLRHIP_STATISTICS_ALL             31u
+
+/* Switches statistics on for the render that slrhip_render_begin just began: call it after slrhip_render_begin and before that
+ * render's first slrhip_render.  Later: SLRHIP_ERR_INVALID_ARGUMENT (the render goes on, its frame untouched); before
+ * slrhip_render_begin: SLRHIP_ERR_NO_SCENE.  Allocates the records (16 B per pixel of the shard) and the summary's partial sums;
+ * they are kept for later renders and freed with the context.  A failed allocation (SLRHIP_ERR_HIP) leaves statistics off and the
+ * render usable.  The records are cleared in stream order by the first statistics-aware call that follows (render, resolve,
+ * summary), on that call's stream: keep one render's calls on one stream, or synchronise between them.  Every
+ * slrhip_render_begin switches statistics off again.                                                                        */
+int slrhip_statistics_begin(slrhip_ctx* ctx);
+
+/* One channel into DEVICE memory as [height][width] float32 (num_floats: room at device_dst, at least width x height), zeros
+ * outside the shard, so that the channels of shards add up to the whole frame's.  Stream-ordered, non-blocking, allocates
+ * nothing.  SLRHIP_ERR_INVALID_ARGUMENT when statistics are off, when `channel` is not exactly one SLRHIP_STATISTICS_* bit, or
+ * when the destination is null, misaligned (4 bytes) or too small; SLRHIP_ERR_NO_SCENE before slrhip_render_begin.            */
+int slrhip_resolve_statistics(slrhip_ctx* ctx, uint32_t channel, float* device_dst, size_t num_floats, void* stream);
+/* The same into HOST memory (synchronises the device).                                                                      */
+int slrhip_read_statistics(slrhip_ctx* ctx, uint32_t channel, float* host_dst, size_t num_floats);
+
+/* Totals over the pixels of the shard.  The three sums are taken in double over the float32 channel values, in a fixed order
+ * (a two-stage reduction without floating-point atomics whose grid depends on the pixel count alone): two calls on the same
+ * state return the same bits.  All fields ADD over shards except max_sample (take the larger).  (A struct tag, not a typedef:
+ * the function below has the same name.)                                                                                     */
+struct slrhip_statistics_summary {
+    uint64_t pixels;                  /* pixels of the shard                                          */
+    uint64_t samples;                 /* sum of COUNT: pixels x passes folded so far                  */
+    double sum_mean;                  /* sum of MEAN                                                  */
+    double sum_mean_sq;               /* sum of MEAN^2 (the square taken in double)                   */
+    double sum_variance_of_mean;      /* sum of VARIANCE_OF_MEAN                                      */
+    float max_sample;                 /* largest MAX                                                  */
+    uint32_t reserved;
+};                                    /* 48 bytes */
+/* Fills *host_out (HOST memory) in order on `stream`; waits for that stream only, not for the device.  Allocates nothing.
+ * SLRHIP_ERR_INVALID_ARGUMENT when statistics are off; SLRHIP_ERR_NO_SCENE before slrhip_render_begin.                       */
+int slrhip_statistics_summary(slrhip_ctx* ctx, struct slrhip_statistics_summary* host_out, void* stream);
+
+/* Rendering to a noise target.  metric, evaluated on the host in double from the summary:                                  */
+#define SLRHIP_NOISE_RMSE     0u   /* sqrt(sum_variance_of_mean / pixels): the estimated RMS error of the per-pixel mean luminance */
+#define SLRHIP_NOISE_RELATIVE 1u   /* that divided by the frame's mean luminance sum_mean / pixels; infinity when that is 0 */
+typedef struct slrhip_noise_target {
+    uint32_t metric;                  /* SLRHIP_NOISE_*                                                */
+    float target;                     /* stop once metric <= target (0: never; INFINITY: after the first block with 2 passes) */
+    uint32_t spp_step;                /* passes per block: the stop check runs after each block        */
+    uint32_t spp_max;                 /* at most this many passes; the last block is cut to fit        */
+} slrhip_noise_target;
+/* Renders passes [spp_begin, spp_begin + *spp_done) in blocks of spp_step passes through slrhip_render (same stream ordering,
+ * blocks the host).  After each block it takes the summary and stops at the first block after which every pixel holds at least 2
+ * samples and metric <= target, or at spp_max passes.  Every pixel gets the same passes, so the frame is BIT-IDENTICAL to one
+ * slrhip_render(ctx, spp_begin, *spp_done, stream).  *spp_done (HOST) is the number of passes rendered by this call, also when
+ * it fails part-way; *last (HOST, may be NULL) the summary of the last stop check.  The records continue across calls, like
+ * the frame: a second call goes on from where the first stopped (give it spp_begin + *spp_done).
+ * Needs slrhip_statistics_begin (else SLRHIP_ERR_INVALID_ARGUMENT); spp_step == 0, spp_max == 0, an unknown metric, a NaN
+ * target or a pass range beyond 2^32: SLRHIP_ERR_INVALID_ARGUMENT; before slrhip_render_begin: SLRHIP_ERR_NO_SCENE.
+ * Per context: a multi-rank host renders fixed blocks with slrhip_render on every rank, adds the ranks' summaries (the sums add)
+ * and evaluates the metric itself, so that all ranks stop at the same pass.                                                 */
+int slrhip_render_until(slrhip_ctx* ctx, uint32_t spp_begin, const slrhip_noise_target* target, uint32_t* spp_done,
+                        struct slrhip_statistics_summary* last, void* stream);
+
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */
 enum { SLRHIP_SPECTRUMTYPE_REFLECTANCE = 0, SLRHIP_SPECTRUMTYPE_ILLUMINANT = 1, SLRHIP_SPECTRUMTYPE_IOR = 2 };

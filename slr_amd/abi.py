@@ -45,6 +45,13 @@ FEATURE_ALL = 63
 FEATURE_CHANNELS = {FEATURE_GEOMETRIC_NORMAL: ("geometric_normal", 3, np.float32), FEATURE_SHADING_NORMAL: ("shading_normal", 3, np.float32),
                     FEATURE_SHADING_TANGENT: ("shading_tangent", 3, np.float32), FEATURE_DISTANCE: ("distance", 1, np.float32),
                     FEATURE_COVERAGE: ("coverage", 1, np.float32), FEATURE_IDS: ("ids", 3, np.uint32)}
+# per-pixel noise statistics (slrhip_statistics_begin): channel bits -> file / npz name; the metrics of slrhip_render_until
+STATISTICS_MEAN, STATISTICS_VARIANCE, STATISTICS_VARIANCE_OF_MEAN, STATISTICS_COUNT, STATISTICS_MAX = 1, 2, 4, 8, 16
+STATISTICS_ALL = 31
+STATISTICS_CHANNELS = {STATISTICS_MEAN: "mean", STATISTICS_VARIANCE: "variance", STATISTICS_VARIANCE_OF_MEAN: "variance_of_mean",
+                       STATISTICS_COUNT: "count", STATISTICS_MAX: "max"}
+NOISE_RMSE, NOISE_RELATIVE = 0, 1
+NOISE_METRICS = {"rmse": NOISE_RMSE, "relative": NOISE_RELATIVE}
 
 
 def texture_ref(t):
@@ -113,6 +120,27 @@ class Counters(C.Structure):
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint64 * 3), ("milliseconds", C.c_double * 3), ("rays", C.c_uint64 * 2),
                 ("nodes", C.c_uint64 * 2), ("triangles", C.c_uint64 * 2), ("slot_visits", C.c_uint64)]
+
+
+class StatisticsSummary(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("samples", C.c_uint64), ("sum_mean", C.c_double), ("sum_mean_sq", C.c_double),
+                ("sum_variance_of_mean", C.c_double), ("max_sample", C.c_float), ("reserved", C.c_uint32)]
+
+
+class NoiseTarget(C.Structure):
+    _fields_ = [("metric", C.c_uint32), ("target", C.c_float), ("spp_step", C.c_uint32), ("spp_max", C.c_uint32)]
+
+
+def noise_metric(summary, metric=NOISE_RMSE):
+    """The stop check of slrhip_render_until on a statistics summary (a dict of Context.statistics_summary, or the sum of
+    several shards' dicts): NOISE_RMSE = sqrt(sum_variance_of_mean / pixels), NOISE_RELATIVE = that over the mean luminance."""
+    if summary["pixels"] == 0:
+        return 0.0
+    rmse = float(np.sqrt(np.float64(summary["sum_variance_of_mean"]) / np.float64(summary["pixels"])))
+    if metric == NOISE_RMSE:
+        return rmse
+    mean = float(np.float64(summary["sum_mean"]) / np.float64(summary["pixels"]))
+    return float("inf") if mean == 0.0 else rmse / mean
 
 
 FLAG_TIME_KERNELS, FLAG_COUNT_TRAVERSAL, FLAG_BVH_DEVICE_BUILD, FLAG_TEST_DEVICE_ERROR, FLAG_BVH_SPATIAL_SPLITS, FLAG_TAIL_KERNEL = 1, 2, 4, 16, 64, 128

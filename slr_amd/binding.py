@@ -15,6 +15,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_resolve_framebuffer", "slrhip_reduce_framebuffer", "slrhip_read_framebuffer", "slrhip_synchronize", "slrhip_get_counters",
            "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_intersect_rays", "slrhip_test_visibility",
            "slrhip_query_status", "slrhip_render_features", "slrhip_resolve_features", "slrhip_read_features", "slrhip_camera_rays", "slrhip_features_status",
+           "slrhip_statistics_begin", "slrhip_resolve_statistics", "slrhip_read_statistics", "slrhip_statistics_summary", "slrhip_render_until", "slrhip_sample_luminance",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -66,6 +67,18 @@ def load_library():
                            ("slrhip_features_status", [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
+    # (and one from before the noise statistics lacks these six)
+    for name, argtypes in (("slrhip_statistics_begin", [C.c_void_p]),
+                           ("slrhip_resolve_statistics", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_read_statistics", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_statistics_summary", [C.c_void_p, C.POINTER(abi.StatisticsSummary), C.c_void_p]),
+                           ("slrhip_render_until", [C.c_void_p, C.c_uint32, C.POINTER(abi.NoiseTarget), C.POINTER(C.c_uint32),
+                                                    C.POINTER(abi.StatisticsSummary), C.c_void_p]),
+                           ("slrhip_sample_luminance", [C.c_int32, C.c_void_p])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
+        lib.slrhip_sample_luminance.restype = C.c_float
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -313,6 +326,44 @@ class Context:
                 if p.value:
                     hip.hipFree(p)
         return rows, xy
+
+    # ---- per-pixel noise statistics and rendering to a noise target (slrhip_statistics_begin ... slrhip_render_until) ----
+    def statistics_begin(self):
+        """Switches the noise statistics on for the render that render_begin just began (before its first render())."""
+        _check(self.lib, self.lib.slrhip_statistics_begin(self.handle), "slrhip_statistics_begin")
+
+    def statistics_into(self, channel, device_ptr, num_floats, stream=None):
+        """One abi.STATISTICS_* channel into device memory at `device_ptr` ([height, width] float32), ordered on `stream`."""
+        _check(self.lib, self.lib.slrhip_resolve_statistics(self.handle, channel, device_ptr, num_floats, self._stream_handle(stream)),
+               "slrhip_resolve_statistics")
+
+    def statistics(self, channel):
+        """One abi.STATISTICS_* channel as a numpy array [height, width] float32, zeros outside the shard.  Synchronises."""
+        h, w = self.settings.image_height, self.settings.image_width
+        out = np.empty((h, w), np.float32)
+        _check(self.lib, self.lib.slrhip_read_statistics(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_statistics")
+        return out
+
+    @staticmethod
+    def _summary_dict(s):
+        return {name: getattr(s, name) for name, _ in abi.StatisticsSummary._fields_ if name != "reserved"}
+
+    def statistics_summary(self, stream=None):
+        """The shard's totals (slrhip_statistics_summary) as a dict; waits for `stream` only.  Dicts of shards add field by
+        field, except max_sample (take the larger); abi.noise_metric evaluates the stop check on one."""
+        s = abi.StatisticsSummary()
+        _check(self.lib, self.lib.slrhip_statistics_summary(self.handle, C.byref(s), self._stream_handle(stream)), "slrhip_statistics_summary")
+        return self._summary_dict(s)
+
+    def render_until(self, metric, target, step, spp_max, spp_begin=0, stream=None):
+        """Renders blocks of `step` passes from `spp_begin` until abi.noise_metric(summary, metric) <= target (and every pixel has
+        2 samples) or `spp_max` passes are done (slrhip_render_until): (spp_done, summary of the last stop check).  The frame
+        is bit-identical to render(spp_begin, spp_done).  Needs statistics_begin()."""
+        t = abi.NoiseTarget(metric, target, step, spp_max)
+        done, last = C.c_uint32(0), abi.StatisticsSummary()
+        _check(self.lib, self.lib.slrhip_render_until(self.handle, spp_begin, C.byref(t), C.byref(done), C.byref(last), self._stream_handle(stream)),
+               "slrhip_render_until")
+        return done.value, self._summary_dict(last)
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

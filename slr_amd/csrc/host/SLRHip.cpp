@@ -209,6 +209,7 @@ void PathTracingRenderer::render(const Scene& scene, const RenderSettings& setti
     st.rng_seed = settings.getInt(RenderSettingItem::RNGSeed);
     slrhip_shard whole = {0, 1};
     if ((rc = slrhip_render_begin(ctx, &st, whole))) die("slrhip_render_begin", rc);
+    if (m_hasNoiseTarget && (rc = slrhip_statistics_begin(ctx))) die("slrhip_statistics_begin", rc);
 
     // sensitivity of PerspectiveCamera.cpp:23 (ImageSensor::saveImage multiplies the scale by it, ImageSensor.cpp:143-147)
     const slrhip_camera& cam = scene.camera();
@@ -228,8 +229,22 @@ void PathTracingRenderer::render(const Scene& scene, const RenderSettings& setti
     uint32_t done = 0;
     while (done < m_samplesPerPixel) {
         const uint32_t upTo = exportPass <= m_samplesPerPixel ? exportPass : m_samplesPerPixel;
-        if ((rc = slrhip_render(ctx, done, upTo - done, nullptr))) die("slrhip_render", rc);
+        bool reached = false;
+        if (m_hasNoiseTarget) {
+            // one block up to the next export: slrhip_render_until renders it and takes the stop check
+            slrhip_noise_target t = m_noiseTarget;
+            t.spp_step = t.spp_max = upTo - done;
+            uint32_t n = 0;
+            struct slrhip_statistics_summary sum;
+            if ((rc = slrhip_render_until(ctx, done, &t, &n, &sum, nullptr))) die("slrhip_render_until", rc);
+            const double rmse = sum.pixels ? std::sqrt(sum.sum_variance_of_mean / (double)sum.pixels) : 0.0;
+            const double mean = sum.pixels ? sum.sum_mean / (double)sum.pixels : 0.0;
+            m_noiseReached = t.metric == SLRHIP_NOISE_RMSE ? rmse : (mean == 0.0 ? (double)INFINITY : rmse / mean);
+            reached = sum.samples >= 2 * sum.pixels && m_noiseReached <= (double)t.target;
+        }
+        else if ((rc = slrhip_render(ctx, done, upTo - done, nullptr))) die("slrhip_render", rc);
         done = upTo;
+        m_samplesReached = done;
         if (done == exportPass) {
             if ((rc = slrhip_read_framebuffer(ctx, fb.data(), numFloats))) die("slrhip_read_framebuffer", rc);
             char filename[256];
@@ -243,6 +258,10 @@ void PathTracingRenderer::render(const Scene& scene, const RenderSettings& setti
             ++imgIdx;
             if (imgIdx == endIdx) break;
             exportPass += exportPass;
+        }
+        if (reached) {
+            std::printf("noise target %g reached: %g after %u samples\n", (double)m_noiseTarget.target, m_noiseReached, done);
+            break;
         }
     }
     slrhip_destroy(ctx);

@@ -104,10 +104,21 @@ class PathTracingRenderer : public Renderer {
     int m_device;
     std::string m_outputDir;
     int m_mode;
+    bool m_hasNoiseTarget = false;
+    slrhip_noise_target m_noiseTarget = {SLRHIP_NOISE_RMSE, 0.0f, 16, 0};
+    mutable uint32_t m_samplesReached = 0;
+    mutable double m_noiseReached = 0.0;
 public:
     // mode: SLRHIP_MODE_RGB or SLRHIP_MODE_SPECTRAL — the reference's compile-time Use_Spectral_Representation switch
     explicit PathTracingRenderer(uint32_t spp, int device = 0, const std::string& outputDir = ".", int mode = SLRHIP_MODE_RGB)
         : m_samplesPerPixel(spp), m_device(device), m_outputDir(outputDir), m_mode(mode) {}
+    // Optional: render to a noise level instead of a sample count (slrhip_render_until).  The images are still written after 1, 2,
+    // 4, ... passes, but the pass loop ends at the first export at which the metric (SLRHIP_NOISE_*) of the frame is at most
+    // `target` — or at spp, the sample limit.  Every pixel gets the same passes.  The reference has no counterpart.
+    void setNoiseTarget(uint32_t metric, float target) { m_hasNoiseTarget = true; m_noiseTarget.metric = metric; m_noiseTarget.target = target; }
+    // after render(): the passes rendered, and the metric's last value (0 without a noise target)
+    uint32_t samplesReached() const { return m_samplesReached; }
+    double noiseReached() const { return m_noiseReached; }
     void render(const Scene& scene, const RenderSettings& settings) const override;
 };
 

@@ -9,6 +9,7 @@
 
 #include "../../include/slrhip.h"
 #include "cmf16_table.h"
+#include "pt_luminance.h"
 #include "cmf_2deg_table.h"
 
 namespace {
@@ -249,6 +250,16 @@ int32_t slrhip_sample_seed(int32_t rngSeed, uint32_t px, uint32_t py, uint32_t p
     h = fmix32(h ^ (py * 0x85EBCA77u + 0x165667B1u));
     h = fmix32(h ^ (px * 0xC2B2AE3Du + 0x27D4EB2Fu));
     return (int32_t)h;
+}
+
+// The luminance of one sample, as the fold kernel takes it for the noise statistics (pt_luminance.h: the same functions).
+float slrhip_sample_luminance(int32_t components, const float* v) {
+    if (!v) return NAN;
+    if (components == 3) return slrhip::sampleLuminanceRGB(v[0], v[1], v[2]);
+    if (components != 16) return NAN;
+    float p[4];
+    for (uint32_t q = 0; q < 4; ++q) p[q] = slrhip::sampleLuminancePlane(q, v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    return slrhip::sampleLuminanceOfPlanes(p[0] + p[1], p[2] + p[3]);
 }
 
 int slrhip_tonemap_bgr8(const float* fb, int32_t width, int32_t height, int32_t components, float scale, uint8_t* dst,

@@ -239,7 +239,8 @@ __device__ __forceinline__ bool tailModeBegins(const PathBuffers& pb, uint32_t l
 
 void launchResetSlots(const PathBuffers& pb, const RenderParams& rp, bool clearSensor, hipStream_t stream);
 // ImageSensor::add for the window's passes, in pass order: the result window folded into the per-pixel Kahan sums
-void launchFold(const PathBuffers& pb, const RenderParams& rp, hipStream_t stream);
+// statRecords != nullptr (slrhip_statistics_begin): the instantiation that also updates the per-pixel noise records
+void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, hipStream_t stream);
 // one wavefront iteration = launchShade(parity) then launchTraceWs(parity)
 void launchShade(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);
 void launchCountSamples(const PathBuffers& pb, const RenderParams& rp, hipStream_t stream);
@@ -284,5 +285,23 @@ struct FeatureSums {
 void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream);
 void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays, uint32_t* pixelXY, hipStream_t stream);
 void launchFeatureResolve(const FeatureParams& fp, const FeatureSums& sums, uint32_t channel, void* dst, hipStream_t stream);
+
+
+// Per-pixel noise statistics (slrhip_statistics_begin; pt_stats.hip).  One record per pixel of the shard, updated by k_fold in
+// pass order: {mean, M2, n (uint32 bits), max} of the samples' luminance (float32 Welford).
+static const uint32_t kStatsBlock = 256;                   // threads per block of the summary's first stage
+static const uint32_t kStatsPixelsPerThread = 16;          // a block reduces kStatsBlock x kStatsPixelsPerThread consecutive pixels
+struct StatsTotals {                                       // slrhip_statistics_summary's layout (checked in slrhip_api.hip)
+    uint64_t pixels, samples;
+    double sumMean, sumMeanSq, sumVarianceOfMean;
+    float maxSample;
+    uint32_t pad;
+};
+inline uint32_t statsSummaryBlocks(uint32_t numPixels) { return (numPixels + kStatsBlock * kStatsPixelsPerThread - 1) / (kStatsBlock * kStatsPixelsPerThread); }
+// one SLRHIP_STATISTICS_* channel as [height][width] floats (dst cleared by the caller: pixels outside the shard stay 0)
+void launchStatsResolve(const float4* records, const uint32_t* pixelXY, uint32_t numPixels, uint32_t imageWidth, uint32_t channel, float* dst,
+                        hipStream_t stream);
+// the shard's totals, in double, in a fixed order: partials[statsSummaryBlocks(numPixels)], then *out (both DEVICE memory)
+void launchStatsSummary(const float4* records, uint32_t numPixels, StatsTotals* partials, StatsTotals* out, hipStream_t stream);
 
 } // namespace slrhip

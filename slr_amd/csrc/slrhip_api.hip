@@ -12,6 +12,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -162,6 +163,11 @@ struct slrhip_ctx {
     uint32_t featChannels = 0;                    // the channel set of the feature calls since render_begin (0: none yet)
     uint32_t featWindow = 0;                      // passes per launch (the record window)
     uint64_t featPassEnd = 0;                     // 1 + the highest pass rendered since render_begin (whose ids the pixels hold)
+    // per-pixel noise statistics (slrhip_statistics_begin): allocated by the first enabling call, kept for later renders
+    DevArray<float4> statRecords;                 // {mean, M2, n, max} per pixel of the shard, updated by k_fold
+    DevArray<StatsTotals> statPartials, statTotals;      // the summary's first-stage partials and its result
+    bool statsOn = false;                         // this render folds with the statistics instantiation of k_fold
+    bool statsClear = false;                      // the records still hold an earlier render's: cleared in stream order before their first use
     PathBuffers buffers;
     uint64_t iterations = 0;
     bool firstRenderCall = true;
@@ -523,12 +529,23 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
     }
     ctx->iterations += it;
     launchCountSamples(ctx->buffers, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
-    launchFold(ctx->buffers, rp, s);               // sensor->add, in pass order
+    launchFold(ctx->buffers, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, s);       // sensor->add, in pass order (+ the noise records)
     HIP_TRY(hipGetLastError());
     const int rc = checkWindow(ctx, s);
     if (rc == SLRHIP_OK && iterLogPath) writeIterationLog(iterLogPath, rp, iterLog);
     return rc;
 }
+
+// The noise records of an earlier render are cleared before their first use in this one, in order on the stream of that use.
+static int clearStatistics(slrhip_ctx* ctx, hipStream_t stream) {
+    if (!ctx->statsOn || !ctx->statsClear) return SLRHIP_OK;
+    HIP_TRY(hipMemsetAsync(ctx->statRecords.ptr, 0, std::max<size_t>(ctx->params.numPixels, 1u) * sizeof(float4), stream));
+    ctx->statsClear = false;
+    return SLRHIP_OK;
+}
+
+static_assert(sizeof(StatsTotals) == sizeof(struct slrhip_statistics_summary) && offsetof(StatsTotals, sumVarianceOfMean) == offsetof(struct slrhip_statistics_summary, sum_variance_of_mean) &&
+              offsetof(StatsTotals, maxSample) == offsetof(struct slrhip_statistics_summary, max_sample), "StatsTotals is slrhip_statistics_summary's layout");
 
 extern "C" {
 
@@ -637,6 +654,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->iterations = 0;
     ctx->firstRenderCall = true;
     ctx->featReady = false; ctx->featChannels = 0; ctx->featPassEnd = 0;      // the feature accumulation restarts (its arrays are kept for reuse)
+    ctx->statsOn = false; ctx->statsClear = true;                             // statistics are per render (slrhip_statistics_begin); the records are kept, stale
     ctx->haveRender = true;
     return SLRHIP_OK;
 }
@@ -648,6 +666,7 @@ int slrhip_render(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, void* s
     hipStream_t stream = (hipStream_t)streamPtr;
     const RenderParams& rp = ctx->params;
     if (rp.numSlots == 0) { ctx->firstRenderCall = false; return SLRHIP_OK; }
+    if (const int rc = clearStatistics(ctx, stream)) return rc;       // ordered before the fold: renderWindow's own stream waits for `stream`
     // the result window's budget (render_plan.cpp, planWindows): 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides
     uint64_t budget = 16ull << 30;
     if (const char* e = getenv("SLRHIP_RESULT_WINDOW_MB")) { const long mb = atol(e); if (mb > 0) budget = (uint64_t)mb << 20; }
@@ -959,6 +978,107 @@ int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(bits, ctx->featError.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return SLRHIP_OK;
+}
+
+// ---- per-pixel noise statistics (slrhip_statistics_begin / slrhip_resolve_statistics / slrhip_statistics_summary / slrhip_render_until) ----
+int slrhip_statistics_begin(slrhip_ctx* ctx) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_statistics_begin: null context");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_statistics_begin: call slrhip_render_begin first");
+    if (!ctx->firstRenderCall) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_statistics_begin: this render has begun (call it before the first slrhip_render after slrhip_render_begin)");
+    if (ctx->statsOn) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t pixels = ctx->params.numPixels;
+    hipError_t e = ctx->statRecords.alloc(pixels);
+    if (e == hipSuccess) e = ctx->statPartials.alloc(statsSummaryBlocks(pixels));
+    if (e == hipSuccess) e = ctx->statTotals.alloc(1);
+    if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_statistics_begin: allocating the records: ") + hipGetErrorString(e));
+    ctx->statsOn = true; ctx->statsClear = true;
+    return SLRHIP_OK;
+}
+
+static int checkStatistics(slrhip_ctx* ctx, const char* what) {
+    const std::string w(what);
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": null context");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, w + ": call slrhip_render_begin first");
+    if (!ctx->statsOn) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": statistics are off (slrhip_statistics_begin after slrhip_render_begin switches them on)");
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_statistics(slrhip_ctx* ctx, uint32_t channel, float* deviceDst, size_t numFloats, void* streamPtr) {
+    if (const int rc = checkStatistics(ctx, "slrhip_resolve_statistics")) return rc;
+    if (channel == 0 || (channel & (channel - 1u)) || (channel & ~SLRHIP_STATISTICS_ALL))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_statistics: `channel` must be one SLRHIP_STATISTICS_* bit");
+    if (!deviceDst || ((uintptr_t)deviceDst & 3u)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_statistics: null or misaligned destination (4 bytes)");
+    const RenderParams& rp = ctx->params;
+    const size_t need = (size_t)rp.imageWidth * rp.imageHeight;
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_statistics: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (const int rc = clearStatistics(ctx, s)) return rc;
+    HIP_TRY(hipMemsetAsync(deviceDst, 0, need * sizeof(float), s));
+    launchStatsResolve(ctx->statRecords.ptr, ctx->pixelXY.ptr, rp.numPixels, rp.imageWidth, channel, deviceDst, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_statistics(slrhip_ctx* ctx, uint32_t channel, float* hostDst, size_t numFloats) {
+    if (const int rc = checkStatistics(ctx, "slrhip_read_statistics")) return rc;
+    if (!hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_statistics: null destination");
+    const size_t need = (size_t)ctx->params.imageWidth * ctx->params.imageHeight;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->resolveScratch.alloc(need));
+    HIP_TRY(hipDeviceSynchronize());                   // renders queued on any stream of the caller's
+    if (const int rc = slrhip_resolve_statistics(ctx, channel, ctx->resolveScratch.ptr, numFloats, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hostDst, ctx->resolveScratch.ptr, need * sizeof(float), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+int slrhip_statistics_summary(slrhip_ctx* ctx, struct slrhip_statistics_summary* hostOut, void* streamPtr) {
+    if (const int rc = checkStatistics(ctx, "slrhip_statistics_summary")) return rc;
+    if (!hostOut) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_statistics_summary: null destination");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (const int rc = clearStatistics(ctx, s)) return rc;
+    launchStatsSummary(ctx->statRecords.ptr, ctx->params.numPixels, ctx->statPartials.ptr, ctx->statTotals.ptr, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hostOut, ctx->statTotals.ptr, sizeof(*hostOut), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    hostOut->reserved = 0;
+    return SLRHIP_OK;
+}
+
+// The stop check of slrhip_render_until: the metric of a summary, in double.
+static double noiseMetric(const struct slrhip_statistics_summary& t, uint32_t metric) {
+    if (t.pixels == 0) return 0.0;                     // an empty shard has no noise
+    const double rmse = std::sqrt(t.sum_variance_of_mean / (double)t.pixels);
+    if (metric == SLRHIP_NOISE_RMSE) return rmse;
+    const double mean = t.sum_mean / (double)t.pixels;
+    return mean == 0.0 ? INFINITY : rmse / mean;
+}
+
+int slrhip_render_until(slrhip_ctx* ctx, uint32_t sppBegin, const slrhip_noise_target* target, uint32_t* sppDone, struct slrhip_statistics_summary* last,
+                        void* stream) {
+    if (sppDone) *sppDone = 0;
+    if (const int rc = checkStatistics(ctx, "slrhip_render_until")) return rc;
+    if (!target || !sppDone) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_until: null argument");
+    if (target->spp_step == 0 || target->spp_max == 0) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_until: spp_step and spp_max must be positive");
+    if (target->metric != SLRHIP_NOISE_RMSE && target->metric != SLRHIP_NOISE_RELATIVE) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_until: unknown metric");
+    if (std::isnan(target->target)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_until: the target is NaN");
+    if ((uint64_t)sppBegin + target->spp_max > 0xFFFFFFFFull) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_until: pass range beyond 2^32");
+    struct slrhip_statistics_summary totals;
+    std::memset(&totals, 0, sizeof(totals));
+    for (uint32_t done = 0; done < target->spp_max;) {
+        const uint32_t n = std::min(target->spp_step, target->spp_max - done);
+        if (const int rc = slrhip_render(ctx, sppBegin + done, n, stream)) return rc;
+        done += n;
+        *sppDone = done;
+        if (const int rc = slrhip_statistics_summary(ctx, &totals, stream)) return rc;
+        if (last) *last = totals;
+        // "at least 2 passes": the variance of one sample is not defined (the channels are 0 then, which would read as "no noise")
+        if (totals.samples >= 2 * totals.pixels && noiseMetric(totals, target->metric) <= (double)target->target) break;
+    }
     return SLRHIP_OK;
 }
 

@@ -7,6 +7,10 @@ samples with scale brightness / samples, and one stdout line "%u samples: %s, %g
 A scene that asks for another renderer ("BPT", ...) is rendered with the path tracer and a note on stderr.
 `--features DIR` (or a scene whose renderer is "debug") also writes the first-hit feature buffers: the normal images of the
 reference's DebugRenderer and features.npz with the raw per-pixel sums.
+`--noise-target X` renders to a noise level instead of a sample count: blocks of `--noise-step` passes until the estimated error
+of the frame (`--noise-metric rmse`: RMS of the per-pixel standard error of the mean luminance; `relative`: that over the mean
+luminance) is at most X or `--max-spp` passes are done; prints the passes reached and the final estimate, writes one image, and
+with `--noise-map FILE.npy` the per-pixel variance of the mean.  Every pixel gets the same passes (no per-pixel adaptive sampling).
 """
 import argparse
 import ctypes as C
@@ -53,7 +57,27 @@ def write_features(ctx, spp, out_dir, channels):
     np.savez(os.path.join(out_dir, "features.npz"), **raw)
 
 
-def main(argv=None):
+def render_to_noise_target(ctx, st, args, spp, sensitivity):
+    """--noise-target: Context.render_until in place of the 1, 2, 4, ... loop; one image ("000.bmp") of the passes reached."""
+    start = time.time()
+    ctx.statistics_begin()
+    metric = abi.NOISE_METRICS[args.noise_metric]
+    done, summary = ctx.render_until(metric, args.noise_target, args.noise_step, args.max_spp or spp)
+    w, h = st.image_width, st.image_height
+    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
+    fb = ctx.read_framebuffer()
+    scale = float(np.float32(np.float32(st.brightness) / np.float32(done)) * np.float32(sensitivity))
+    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
+    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(os.path.join(args.out, "000.bmp").encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    print("%u samples: 000.bmp, %g[s]" % (done, time.time() - start), flush=True)
+    print("noise target %g (%s): reached %g after %u samples%s" % (args.noise_target, args.noise_metric, abi.noise_metric(summary, metric), done,
+                                                                  "" if abi.noise_metric(summary, metric) <= args.noise_target else " (sample limit)"), flush=True)
+    if args.noise_map:
+        np.save(args.noise_map, ctx.statistics(abi.STATISTICS_VARIANCE_OF_MEAN))
+    return done
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m slr_amd.host")
     ap.add_argument("scene")
     ap.add_argument("--spectral", action="store_true", help="16 wavelength samples per path (the reference's default build)")
@@ -62,7 +86,23 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--features", metavar="DIR", default=None,
                     help="also write the first-hit feature buffers (normal BMPs as the reference's DebugRenderer names them, features.npz) to DIR")
+    ap.add_argument("--noise-target", type=float, default=None, metavar="X",
+                    help="render until the frame's estimated noise is at most X instead of a fixed sample count")
+    ap.add_argument("--noise-metric", choices=sorted(abi.NOISE_METRICS), default="rmse",
+                    help="rmse: RMS over the pixels of the standard error of the mean luminance; relative: that over the mean luminance")
+    ap.add_argument("--noise-step", type=int, default=16, metavar="N", help="passes between two stop checks")
+    ap.add_argument("--max-spp", type=int, default=0, metavar="N", help="sample limit of --noise-target (default: the sample count)")
+    ap.add_argument("--noise-map", default=None, metavar="FILE.npy", help="with --noise-target: write the per-pixel variance of the mean")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.noise_target is None and (args.noise_map or args.max_spp):
+        ap.error("--noise-map and --max-spp go with --noise-target")
+    if args.noise_target is not None and (args.noise_step < 1 or args.max_spp < 0 or args.noise_target != args.noise_target):
+        ap.error("--noise-step must be positive, --max-spp non-negative and --noise-target a number")
 
     try:
         scene, settings, renderer = scene_language.load_scene(args.scene)
@@ -91,6 +131,8 @@ def main(argv=None):
     lib = ctx.lib
     start = time.time()
     done, export, img = 0, 1, 0
+    if args.noise_target is not None:
+        done = spp = render_to_noise_target(ctx, st, args, spp, sensitivity)
     while done < spp and img < 16:
         upto = min(export, spp)
         ctx.render(done, upto - done)
