@@ -565,8 +565,8 @@ int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y,
  * (pixel, pass) samples alone: not on the slot count, the shard split, the result windows, how the passes are cut into
  * slrhip_render calls (ascending) or scheduling — not even in the last bit.  A render that does not ask for statistics launches
  * the kernels it launched before and produces the same bits; with statistics on, the frame, the counters and the error word
- * are unchanged in every bit.  Not built: per-pixel adaptive sampling (pixels with different pass counts would change the work
- * queues); every pixel always gets the same passes.
+ * are unchanged in every bit.  slrhip_render and slrhip_render_until give every pixel the same passes; per-pixel adaptive sampling
+ * on top of the records is slrhip_render_adaptive, below.
  *
  * The luminance of a sample = of its result-window entry, weight x C as ImageSensor::add receives it (un-normalised: not
  * divided by the pass count, no brightness, no sensitivity, no clamp), with the constants of slrhip_tonemap_bgr8:
@@ -639,6 +639,65 @@ typedef struct slrhip_noise_target {
  * and evaluates the metric itself, so that all ranks stop at the same pass.                                                 */
 int slrhip_render_until(slrhip_ctx* ctx, uint32_t spp_begin, const slrhip_noise_target* target, uint32_t* spp_done,
                         struct slrhip_statistics_summary* last, void* stream);
+
+/* ---- adaptive sampling: retire converged pixels, render only the rest --------------------------------------------------------
+ * slrhip_render_until stops the whole frame; here every pixel stops on its own.  The call renders blocks of passes — the first of
+ * spp_min passes, every later one of spp_step, the last cut to fit spp_max — through the window loop of slrhip_render (same
+ * ordering on `stream`, same host blocking, same device error word).  After EACH block, the last included, the check below runs on
+ * the noise records of the pixels that are still active, and a pixel that passes it RETIRES: it gets no further pass from any
+ * adaptive call until the next slrhip_render_begin, which makes every pixel active again.  The call ends when no pixel is active
+ * or spp_max passes have been handed out.  Every still-active pixel has received the same passes, so a block is an ordinary render
+ * window over a shorter, compacted pixel list (ascending order of the shard's pixel list, compacted on the device without atomics:
+ * the list, too, is reproducible); the records of retired pixels stay as they are.
+ *
+ * The check, on a pixel's record {mean, M2, n, max}, in float32, every operation IEEE-rounded on its own (no fused multiply-add):
+ *     vom = M2 / ((float)(n - 1) * (float)n)        the expression of the VARIANCE_OF_MEAN channel
+ *     m   = fmaxf(mean, floor)
+ *     a   = threshold * m
+ *     the pixel retires if  n >= 2  &&  vom <= a * a
+ * i.e. when the standard error of the pixel's mean luminance is at most `threshold` times that mean, or times `floor` for a pixel
+ * darker than that.  A NaN record never retires: a NaN M2 makes vom NaN and the comparison false; a NaN mean is tested
+ * explicitly (fmaxf(NaN, floor) is floor, so the rule alone would not see it).  threshold = 0 retires exactly the pixels whose
+ * samples so far all had the same luminance.  threshold = INFINITY retires every pixel at the first check IF floor > 0.  With
+ * floor = 0 a pixel whose mean is 0 (black so far) gives a = INFINITY * 0 = NaN and NEVER retires at an infinite threshold.
+ *
+ * Invariants.  The rule reads one pixel's own samples only, so the frame, the noise records and the per-pixel counts depend on
+ * (seed, target) alone: not — in any bit — on the slot count, the shard split, the result-window size or scheduling.  A
+ * multi-rank host needs no exchange to stay consistent.  Cutting a call in two: EVERY call begins with a block of spp_min passes,
+ * so two calls reproduce one only if the first ends at a block boundary of the single call and the second is given the single
+ * call's spp_step as its spp_min (and spp_max = the passes that are left); any other cut moves the checks and is another target.
+ * slrhip_render and slrhip_render_until keep rendering ALL pixels of the shard, retired or not, unchanged in every bit; a
+ * context that never calls slrhip_render_adaptive launches the kernels it launched before.
+ * Cost: the 16 B per pixel of the records plus two pairs of list buffers of 8 B per pixel, allocated at the first adaptive call,
+ * kept for later renders and freed with the context; per block one check (three small launches over the active list) and one
+ * 4-byte read-back.  The slot count stays the shard's: with few active pixels most slots idle at once and the tail kernel takes
+ * over early.                                                                                                                */
+typedef struct slrhip_adaptive_target {
+    float    threshold;   /* t >= 0: relative standard error of the pixel's mean luminance at which it retires */
+    float    floor;       /* f >= 0: luminance below which the error is taken relative to f, not to the mean */
+    uint32_t spp_min;     /* >= 2: passes every pixel gets before the first check */
+    uint32_t spp_step;    /* >= 1: passes per block after that; a check follows every block */
+    uint32_t spp_max;     /* >= spp_min: no pixel gets more passes than this from this call */
+} slrhip_adaptive_target;
+/* Passes [spp_begin, spp_begin + *spp_done) for the pixels that stay active longest.  *spp_done (HOST): the passes the
+ * longest-lived pixel got from this call; *samples_done (HOST, may be NULL): the (pixel, pass) samples it rendered (what
+ * slrhip_counters::samples rose by).  Both are written on a failure part-way through as well.  A second call continues with the
+ * surviving pixels: give it spp_begin + *spp_done, as with slrhip_render_until; with no pixel active it returns SLRHIP_OK and
+ * *spp_done = 0, as does a call on an empty shard.
+ * Needs slrhip_statistics_begin for the current render (else SLRHIP_ERR_INVALID_ARGUMENT).  SLRHIP_ERR_INVALID_ARGUMENT also for a
+ * null argument, a NaN or negative threshold or floor, spp_min < 2, spp_step == 0, spp_max < spp_min, or a pass range beyond 2^32;
+ * a refused call renders nothing and leaves the frame untouched.  Before slrhip_render_begin: SLRHIP_ERR_NO_SCENE.            */
+int slrhip_render_adaptive(slrhip_ctx* ctx, uint32_t spp_begin, const slrhip_adaptive_target* target, uint32_t* spp_done,
+                           uint64_t* samples_done, void* stream);
+/* The frame as per-pixel MEANS, for pixels with unequal counts: [height][width][components], sum[c] / (float)n (IEEE division) with
+ * n of the pixel's noise record, 0 where n == 0, zeros outside the shard.  slrhip_resolve_framebuffer is unchanged: the frame
+ * stays the un-normalised sum.  Needs statistics on (else SLRHIP_ERR_INVALID_ARGUMENT); pointer, alignment and size rules are those of
+ * slrhip_resolve_framebuffer (DEVICE memory, stream-ordered, non-blocking) / slrhip_read_framebuffer (HOST memory, synchronises). */
+int slrhip_resolve_framebuffer_mean(slrhip_ctx* ctx, float* device_dst, size_t num_floats, void* stream);
+int slrhip_read_framebuffer_mean(slrhip_ctx* ctx, float* host_dst, size_t num_floats);
+/* *host_count (HOST) = pixels of the shard not yet retired: all of them after slrhip_render_begin.  The count is known on the
+ * host since the last check (slrhip_render_adaptive blocks), so nothing is queued on `stream`.                                */
+int slrhip_adaptive_active(slrhip_ctx* ctx, uint32_t* host_count, void* stream);   /* pixels of the shard not yet retired */
 
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */

@@ -42,6 +42,12 @@ int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shard_index
                              uint32_t num_passes, uint64_t budget_bytes, uint32_t* plan, uint32_t* windows, uint32_t max_windows,
                              uint32_t* num_windows, uint32_t* pixels, uint32_t max_pixels);
 
+/* The blocks of a slrhip_render_adaptive call (slr_amd/csrc/render_plan.h, planAdaptiveBlocks), evaluated on the HOST with the
+ * function the call asks for its next block: blocks[k] = passes of block k for the first `max_blocks` blocks, *num_blocks = their number (0 for a
+ * triple the entry point refuses).  No GPU is touched.                                                                          */
+int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t spp_max, uint32_t* blocks, uint32_t max_blocks,
+                                 uint32_t* num_blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ class NoiseTarget(C.Structure):
     _fields_ = [("metric", C.c_uint32), ("target", C.c_float), ("spp_step", C.c_uint32), ("spp_max", C.c_uint32)]
 
 
+class AdaptiveTarget(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("spp_min", C.c_uint32), ("spp_step", C.c_uint32), ("spp_max", C.c_uint32)]
+
+
 def noise_metric(summary, metric=NOISE_RMSE):
     """The stop check of slrhip_render_until on a statistics summary (a dict of Context.statistics_summary, or the sum of
     several shards' dicts): NOISE_RMSE = sqrt(sum_variance_of_mean / pixels), NOISE_RELATIVE = that over the mean luminance."""

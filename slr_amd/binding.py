@@ -16,6 +16,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_components", "slrhip_get_profile", "slrhip_trace_rays", "slrhip_intersect_rays", "slrhip_test_visibility",
            "slrhip_query_status", "slrhip_render_features", "slrhip_resolve_features", "slrhip_read_features", "slrhip_camera_rays", "slrhip_features_status",
            "slrhip_statistics_begin", "slrhip_resolve_statistics", "slrhip_read_statistics", "slrhip_statistics_summary", "slrhip_render_until", "slrhip_sample_luminance",
+           "slrhip_render_adaptive", "slrhip_resolve_framebuffer_mean", "slrhip_read_framebuffer_mean", "slrhip_adaptive_active", "slrhip_debug_adaptive_blocks",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -75,6 +76,15 @@ def load_library():
                            ("slrhip_render_until", [C.c_void_p, C.c_uint32, C.POINTER(abi.NoiseTarget), C.POINTER(C.c_uint32),
                                                     C.POINTER(abi.StatisticsSummary), C.c_void_p]),
                            ("slrhip_sample_luminance", [C.c_int32, C.c_void_p])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before adaptive sampling lacks these five)
+    for name, argtypes in (("slrhip_render_adaptive", [C.c_void_p, C.c_uint32, C.POINTER(abi.AdaptiveTarget), C.POINTER(C.c_uint32),
+                                                       C.POINTER(C.c_uint64), C.c_void_p]),
+                           ("slrhip_resolve_framebuffer_mean", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_read_framebuffer_mean", [C.c_void_p, C.c_void_p, C.c_size_t]),
+                           ("slrhip_adaptive_active", [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+                           ("slrhip_debug_adaptive_blocks", [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
@@ -364,6 +374,37 @@ class Context:
         _check(self.lib, self.lib.slrhip_render_until(self.handle, spp_begin, C.byref(t), C.byref(done), C.byref(last), self._stream_handle(stream)),
                "slrhip_render_until")
         return done.value, self._summary_dict(last)
+
+    # ---- adaptive sampling (slrhip_render_adaptive / slrhip_read_framebuffer_mean / slrhip_adaptive_active) ----
+    def render_adaptive(self, spp_begin, threshold, floor, spp_min, spp_step, spp_max, stream=None):
+        """Renders blocks of passes from `spp_begin` (spp_min, then spp_step each, cut to spp_max) and retires, after each block,
+        the pixels whose relative standard error of the mean luminance is at most `threshold` (relative to `floor` for darker
+        pixels); later blocks render only the rest (slrhip_render_adaptive): (spp_done of the longest-lived pixel, samples
+        rendered).  Needs statistics_begin(); the per-pixel counts are statistics(abi.STATISTICS_COUNT)."""
+        t = abi.AdaptiveTarget(threshold, floor, spp_min, spp_step, spp_max)
+        done, samples = C.c_uint32(0), C.c_uint64(0)
+        _check(self.lib, self.lib.slrhip_render_adaptive(self.handle, spp_begin, C.byref(t), C.byref(done), C.byref(samples), self._stream_handle(stream)),
+               "slrhip_render_adaptive")
+        return done.value, samples.value
+
+    def mean_into(self, device_ptr, num_floats, stream=None):
+        """The mean frame into device memory at `device_ptr` (slrhip_resolve_framebuffer_mean), ordered on `stream`."""
+        _check(self.lib, self.lib.slrhip_resolve_framebuffer_mean(self.handle, device_ptr, num_floats, self._stream_handle(stream)),
+               "slrhip_resolve_framebuffer_mean")
+
+    def read_framebuffer_mean(self):
+        """The frame as per-pixel means [height, width, components]: sum / count with the count of the pixel's noise record, 0
+        where no sample was rendered and outside the shard.  Needs statistics_begin(); synchronises."""
+        h, w = self.settings.image_height, self.settings.image_width
+        fb = np.zeros((h, w, self.components), np.float32)
+        _check(self.lib, self.lib.slrhip_read_framebuffer_mean(self.handle, fb.ctypes.data, fb.size), "slrhip_read_framebuffer_mean")
+        return fb
+
+    def adaptive_active(self, stream=None):
+        """Pixels of the shard that have not retired since render_begin (slrhip_adaptive_active)."""
+        count = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_adaptive_active(self.handle, C.byref(count), self._stream_handle(stream)), "slrhip_adaptive_active")
+        return count.value
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

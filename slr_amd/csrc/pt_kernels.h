@@ -304,4 +304,30 @@ void launchStatsResolve(const float4* records, const uint32_t* pixelXY, uint32_t
 // the shard's totals, in double, in a fixed order: partials[statsSummaryBlocks(numPixels)], then *out (both DEVICE memory)
 void launchStatsSummary(const float4* records, uint32_t numPixels, StatsTotals* partials, StatsTotals* out, hipStream_t stream);
 
+// Adaptive sampling (slrhip_render_adaptive; pt_adaptive.hip).  The pixels that have not retired are a compact list in ascending
+// shard-pixel order: activeXY (x | y << 16: what a window over the list hands the kernels as PathBuffers::pixelXY) and activeIndex
+// (compact index -> pixel of the shard: where the indexed fold adds).  After a block of passes the check reads the noise records
+// of the previous list's pixels and writes the next list: per-workgroup counts (wave ballots), an exclusive scan of the counts,
+// a scatter — a stable compaction without atomics, so the order (neighbouring pixels in neighbouring runs: WorkItem above) and the
+// run are reproducible.  Two list buffers alternate; the work is proportional to the previous list's length.
+static const uint32_t kAdaptiveBlock = 256;                // entries of the previous list per workgroup
+inline uint32_t adaptiveSelectBlocks(uint32_t count) { return (count + kAdaptiveBlock - 1) / kAdaptiveBlock; }
+struct AdaptiveSelect {
+    const float4* records;        // the noise records, per pixel of the shard
+    const uint32_t* shardXY;      // the shard's pixel list (slrhip_render_begin)
+    const uint32_t* prevIndex;    // the previous list; nullptr = every pixel of the shard (before the first check)
+    uint32_t prevCount;
+    uint32_t* nextXY;             // the next list: at least prevCount entries each
+    uint32_t* nextIndex;
+    uint32_t* blockOffsets;       // adaptiveSelectBlocks(prevCount) words: the counts, then their exclusive scan
+    uint32_t* countWord;          // the next list's length
+    float threshold, floor;       // slrhip_adaptive_target
+};
+void launchAdaptiveSelect(const AdaptiveSelect& a, hipStream_t stream);
+// launchFold (with statistics) for a window over a compact list: rp.numPixels = the list's length, pb.fbSum / fbComp and
+// statRecords are the shard's, compact pixel i adds into pixel indexMap[i]
+void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const uint32_t* indexMap, hipStream_t stream);
+// the frame as per-pixel means: sum / (float)n with n of the pixel's record, 0 where n == 0 (dst cleared by the caller)
+void launchResolveMean(const PathBuffers& pb, const RenderParams& rp, const float4* records, float* dst, hipStream_t stream);
+
 } // namespace slrhip

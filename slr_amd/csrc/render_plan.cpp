@@ -128,4 +128,15 @@ uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail
     return std::min(bound, numSlots / divisor);
 }
 
+uint32_t adaptiveBlock(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t done) {
+    if (sppMin < 2 || sppStep == 0 || sppMax < sppMin || done >= sppMax) return 0u;
+    return done == 0 ? sppMin : std::min(sppStep, sppMax - done);
+}
+
+std::vector<uint32_t> planAdaptiveBlocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax) {
+    std::vector<uint32_t> blocks;
+    for (uint32_t done = 0, n; (n = adaptiveBlock(sppMin, sppStep, sppMax, done)) != 0; done += n) blocks.push_back(n);
+    return blocks;
+}
+
 } // namespace slrhip

@@ -53,4 +53,12 @@ WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthO
 // build does not count traversal steps; never more than numSlots / `divisor` (SLR_TAIL_DIVISOR of slrhip_api.hip).
 uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail, bool available);
 
+// The blocks of a slrhip_render_adaptive call, as pass counts: sppMin (>= 2), then sppStep (>= 1) as often as it fits, the last one
+// cut so that the sum is sppMax (>= sppMin).  A retirement check follows every block; the windows of a block come from
+// planWindows / planWindow with the active pixel count.  adaptiveBlock: the block that follows `done` passes of the call (0: the
+// call is complete, or the triple is one the entry point refuses) — what the render loop asks for, block by block;
+// planAdaptiveBlocks: the whole list from the same function (one entry per block: for the tests and tools, not for 2^32 passes).
+uint32_t adaptiveBlock(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t done);
+std::vector<uint32_t> planAdaptiveBlocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax);
+
 } // namespace slrhip

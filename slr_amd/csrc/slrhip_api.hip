@@ -168,6 +168,11 @@ struct slrhip_ctx {
     DevArray<StatsTotals> statPartials, statTotals;      // the summary's first-stage partials and its result
     bool statsOn = false;                         // this render folds with the statistics instantiation of k_fold
     bool statsClear = false;                      // the records still hold an earlier render's: cleared in stream order before their first use
+    // adaptive sampling (slrhip_render_adaptive): the list buffers are allocated by the first adaptive call and kept for later renders
+    DevArray<uint32_t> adaptXY[2], adaptIndex[2]; // the active list (pt_kernels.h AdaptiveSelect), two pairs that alternate
+    DevArray<uint32_t> adaptOffsets, adaptCount;  // the select's workgroup offsets; the new list's length (read back once per block)
+    uint32_t activePixels = 0;                    // pixels of the shard not yet retired since render_begin
+    int activeList = -1;                          // the pair that holds them; -1: every pixel of the shard (no check has run yet)
     PathBuffers buffers;
     uint64_t iterations = 0;
     bool firstRenderCall = true;
@@ -356,25 +361,25 @@ static hipError_t readStatus(slrhip_ctx* ctx, uint32_t* words, uint32_t count, h
 // The window is complete only if the queues handed out exactly one sample per pixel and pass: the device's own count
 // (k_count_samples over the queues' cursors) against the host's arithmetic.  A lost or repeated sample would leave a stale
 // or overwritten entry in the result window — never silent.
-static int checkWindow(slrhip_ctx* ctx, hipStream_t s) {
+static int checkWindow(slrhip_ctx* ctx, uint32_t workItems, hipStream_t s) {
     uint32_t words[kStatusWords] = {};
     HIP_TRY(readStatus(ctx, words, kStatusWords, s));
     if (words[S_ERROR]) return deviceError(words[S_ERROR]);
-    if (words[S_WINDOW_SAMPLES] != ctx->params.workItems)
+    if (words[S_WINDOW_SAMPLES] != workItems)
         return fail(SLRHIP_ERR_HIP, "slrhip_render: the work queues handed out " + std::to_string(words[S_WINDOW_SAMPLES]) + " samples for a window of " +
-                                        std::to_string(ctx->params.workItems) + " (internal error)");
+                                        std::to_string(workItems) + " (internal error)");
     return SLRHIP_OK;
 }
 
 // Tail mode seen in the status words: list the live slots, finish them, read the words again (live slots must be 0 then).
 // `status` are the loop's words (S_LIVE .. S_TAIL_MODE), updated here.
-static int runTail(slrhip_ctx* ctx, uint32_t* status, hipStream_t s, bool timed) {
+static int runTail(slrhip_ctx* ctx, const PathBuffers& pb, const RenderParams& rp, uint32_t* status, hipStream_t s, bool timed) {
     struct Timer {
         hipEvent_t t0 = nullptr, t1 = nullptr;
         ~Timer() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
     } timer;
     if (timed) { HIP_TRY(hipEventCreate(&timer.t0)); HIP_TRY(hipEventCreate(&timer.t1)); HIP_TRY(hipEventRecord(timer.t0, s)); }
-    launchTail(ctx->scene, ctx->buffers, ctx->params, status[S_LIVE], ctx->numCUs, s);
+    launchTail(ctx->scene, pb, rp, status[S_LIVE], ctx->numCUs, s);
     if (timed) HIP_TRY(hipEventRecord(timer.t1, s));
     HIP_TRY(hipGetLastError());
     const uint32_t liveBefore = status[S_LIVE];
@@ -405,16 +410,16 @@ const int kCheckEvery = 16;
 const int kEventsPerIteration = 3;    // SLRHIP_FLAG_TIME_KERNELS: before shade, after shade, after trace
 
 // One block of kCheckEvery iterations as plain launches on `s`, with the context's timing events around each kernel if `timed`.
-static hipError_t launchBlock(slrhip_ctx* ctx, uint32_t traceBlocks, bool timed, hipStream_t s) {
+static hipError_t launchBlock(slrhip_ctx* ctx, const PathBuffers& pb, const RenderParams& rp, uint32_t traceBlocks, bool timed, hipStream_t s) {
     const bool count = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
     hipError_t e = hipSuccess;
     for (int k = 0; k < kCheckEvery; ++k) {
         const uint32_t parity = (uint32_t)(k & 1);
         hipEvent_t* ev = timed ? &ctx->events[(size_t)k * kEventsPerIteration] : nullptr;
         if (ev && e == hipSuccess) e = hipEventRecord(ev[0], s);
-        launchShade(ctx->scene, ctx->buffers, ctx->params, parity, s);
+        launchShade(ctx->scene, pb, rp, parity, s);
         if (ev && e == hipSuccess) e = hipEventRecord(ev[1], s);
-        launchTraceWs(ctx->scene, ctx->buffers, ctx->params, parity, traceBlocks, count, s);
+        launchTraceWs(ctx->scene, pb, rp, parity, traceBlocks, count, s);
         if (ev && e == hipSuccess) e = hipEventRecord(ev[2], s);
     }
     return e;
@@ -454,16 +459,28 @@ struct BlockGraph {
     ~BlockGraph() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
 };
 
+// The pixels of a window of slrhip_render_adaptive: a compact list (pt_kernels.h AdaptiveSelect) instead of the shard's.
+struct ActiveWindow {
+    const uint32_t* xy;           // compact index -> x | y << 16
+    const uint32_t* index;        // compact index -> pixel of the shard
+    uint32_t count;
+};
+
 // One window of passes [sppBegin, sppBegin + sppCount): every sample of the window rendered into the result window, then folded
-// into the sensor in pass order.  slrhip_render sizes the windows.
-static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, hipStream_t stream) {
-    RenderParams& rp = ctx->params;
+// into the sensor in pass order.  slrhip_render sizes the windows.  The window runs on its OWN copy of the render parameters and
+// the buffer table: ctx->params and ctx->buffers stay the shard's (the resolves, the statistics, the feature passes and
+// slrhip_camera_rays read them).  `active` (slrhip_render_adaptive): the window is over that list — its length as the pixel count, its
+// xy as the pixel list, its index as the map of the fold; the slots, the queues' owners and the tail bound stay the shard's.
+static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, hipStream_t stream, const ActiveWindow* active = nullptr) {
+    RenderParams rp = ctx->params;
+    PathBuffers pb = ctx->buffers;
+    if (active) { rp.numPixels = active->count; pb.pixelXY = active->xy; }
     const WindowPlan window = planWindow(rp.numPixels, sppCount, runLengthOverride());
     rp.sppBegin = sppBegin; rp.sppCount = sppCount;
     rp.workItems = window.workItems; rp.runLength = window.runLength; rp.numRuns = window.numRuns;
     // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
     // it is asked for zero passes
-    launchResetSlots(ctx->buffers, rp, ctx->firstRenderCall, stream);
+    launchResetSlots(pb, rp, ctx->firstRenderCall, stream);
     ctx->firstRenderCall = false;
     if (sppCount == 0) return SLRHIP_OK;
     // persistent traversal workgroups of the wave-specialised kernel (pt_trace_ws.hip): a fixed number per CU
@@ -501,7 +518,7 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
         HIP_TRY(hipEventRecord(ctx->userReady, stream));          // the reset kernel above and whatever the caller queued before
         HIP_TRY(hipStreamWaitEvent(s, ctx->userReady, 0));
         HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        (void)launchBlock(ctx, traceBlocks, false, s);
+        (void)launchBlock(ctx, pb, rp, traceBlocks, false, s);
         hipError_t ce = hipStreamEndCapture(s, &block.graph);
         if (ce == hipSuccess) ce = hipGraphInstantiate(&block.exec, block.graph, nullptr, nullptr, 0);
         if (ce != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: hipGraph capture failed: ") + hipGetErrorString(ce));
@@ -511,7 +528,7 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
     uint64_t it = 0;
     uint32_t status[S_TAIL_MODE + 1] = {rp.numSlots, 0u, 0u, 0u};
     while (status[S_LIVE] > 0) {
-        hipError_t e = block.exec ? hipGraphLaunch(block.exec, s) : launchBlock(ctx, traceBlocks, timeKernels, s);
+        hipError_t e = block.exec ? hipGraphLaunch(block.exec, s) : launchBlock(ctx, pb, rp, traceBlocks, timeKernels, s);
         if (e == hipSuccess && !block.exec) e = hipGetLastError();          // a failed launch surfaces here, not at the end of the render
         if (e == hipSuccess) e = readStatus(ctx, status, S_TAIL_MODE + 1, s);
         if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: ") + hipGetErrorString(e));
@@ -522,16 +539,17 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
             if (rc != SLRHIP_OK) return rc;
         }
         if (status[S_TAIL_MODE] && status[S_LIVE]) {
-            const int rc = runTail(ctx, status, s, timeKernels);
+            const int rc = runTail(ctx, pb, rp, status, s, timeKernels);
             if (rc != SLRHIP_OK) return rc;
         }
         if (it > maxIterations) return fail(SLRHIP_ERR_HIP, "slrhip_render: iteration bound exceeded (internal error)");
     }
     ctx->iterations += it;
-    launchCountSamples(ctx->buffers, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
-    launchFold(ctx->buffers, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, s);       // sensor->add, in pass order (+ the noise records)
+    launchCountSamples(pb, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
+    if (active) launchFoldIndexed(pb, rp, ctx->statRecords.ptr, active->index, s);       // the same, scattered to the list's pixels of the shard
+    else launchFold(pb, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, s);       // sensor->add, in pass order (+ the noise records)
     HIP_TRY(hipGetLastError());
-    const int rc = checkWindow(ctx, s);
+    const int rc = checkWindow(ctx, rp.workItems, s);
     if (rc == SLRHIP_OK && iterLogPath) writeIterationLog(iterLogPath, rp, iterLog);
     return rc;
 }
@@ -542,6 +560,13 @@ static int clearStatistics(slrhip_ctx* ctx, hipStream_t stream) {
     HIP_TRY(hipMemsetAsync(ctx->statRecords.ptr, 0, std::max<size_t>(ctx->params.numPixels, 1u) * sizeof(float4), stream));
     ctx->statsClear = false;
     return SLRHIP_OK;
+}
+
+// the result window's budget (render_plan.cpp, planWindows): 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides
+static uint64_t resultWindowBudget() {
+    uint64_t budget = 16ull << 30;
+    if (const char* e = getenv("SLRHIP_RESULT_WINDOW_MB")) { const long mb = atol(e); if (mb > 0) budget = (uint64_t)mb << 20; }
+    return budget;
 }
 
 static_assert(sizeof(StatsTotals) == sizeof(struct slrhip_statistics_summary) && offsetof(StatsTotals, sumVarianceOfMean) == offsetof(struct slrhip_statistics_summary, sum_variance_of_mean) &&
@@ -655,6 +680,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->firstRenderCall = true;
     ctx->featReady = false; ctx->featChannels = 0; ctx->featPassEnd = 0;      // the feature accumulation restarts (its arrays are kept for reuse)
     ctx->statsOn = false; ctx->statsClear = true;                             // statistics are per render (slrhip_statistics_begin); the records are kept, stale
+    ctx->activePixels = plan.numPixels; ctx->activeList = -1;                 // every pixel is active again (slrhip_render_adaptive)
     ctx->haveRender = true;
     return SLRHIP_OK;
 }
@@ -667,10 +693,7 @@ int slrhip_render(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, void* s
     const RenderParams& rp = ctx->params;
     if (rp.numSlots == 0) { ctx->firstRenderCall = false; return SLRHIP_OK; }
     if (const int rc = clearStatistics(ctx, stream)) return rc;       // ordered before the fold: renderWindow's own stream waits for `stream`
-    // the result window's budget (render_plan.cpp, planWindows): 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides
-    uint64_t budget = 16ull << 30;
-    if (const char* e = getenv("SLRHIP_RESULT_WINDOW_MB")) { const long mb = atol(e); if (mb > 0) budget = (uint64_t)mb << 20; }
-    const uint32_t window = planWindows(rp.numPixels, rp.spectral != 0, sppCount, budget);
+    const uint32_t window = planWindows(rp.numPixels, rp.spectral != 0, sppCount, resultWindowBudget());
     HIP_TRY(ctx->results.alloc((size_t)window * rp.numPixels * (rp.spectral ? 4u : 1u)));
     ctx->buffers.results = ctx->results.ptr;
     if (sppCount == 0) return renderWindow(ctx, sppBegin, 0, stream);
@@ -1079,6 +1102,121 @@ int slrhip_render_until(slrhip_ctx* ctx, uint32_t sppBegin, const slrhip_noise_t
         // "at least 2 passes": the variance of one sample is not defined (the channels are 0 then, which would read as "no noise")
         if (totals.samples >= 2 * totals.pixels && noiseMetric(totals, target->metric) <= (double)target->target) break;
     }
+    return SLRHIP_OK;
+}
+
+// ---- adaptive sampling (slrhip_render_adaptive / slrhip_resolve_framebuffer_mean / slrhip_adaptive_active) ----
+// The retirement check after a block: the next active list from the current one (pt_adaptive.hip), its length read back.
+static int adaptiveSelect(slrhip_ctx* ctx, const slrhip_adaptive_target& target, hipStream_t stream) {
+    const int next = ctx->activeList < 0 ? 0 : ctx->activeList ^ 1;
+    AdaptiveSelect a{};
+    a.records = ctx->statRecords.ptr; a.shardXY = ctx->pixelXY.ptr;
+    a.prevIndex = ctx->activeList < 0 ? nullptr : ctx->adaptIndex[ctx->activeList].ptr; a.prevCount = ctx->activePixels;
+    a.nextXY = ctx->adaptXY[next].ptr; a.nextIndex = ctx->adaptIndex[next].ptr;
+    a.blockOffsets = ctx->adaptOffsets.ptr; a.countWord = ctx->adaptCount.ptr;
+    a.threshold = target.threshold; a.floor = target.floor;
+    launchAdaptiveSelect(a, stream);
+    HIP_TRY(hipGetLastError());
+    uint32_t count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, ctx->adaptCount.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (count > ctx->activePixels) return fail(SLRHIP_ERR_HIP, "slrhip_render_adaptive: the active list grew from " + std::to_string(ctx->activePixels) + " to " + std::to_string(count) + " pixels (internal error)");
+    ctx->activePixels = count; ctx->activeList = next;
+    return SLRHIP_OK;
+}
+
+int slrhip_render_adaptive(slrhip_ctx* ctx, uint32_t sppBegin, const slrhip_adaptive_target* target, uint32_t* sppDone, uint64_t* samplesDone,
+                           void* streamPtr) {
+    if (sppDone) *sppDone = 0;
+    if (samplesDone) *samplesDone = 0;
+    if (const int rc = checkStatistics(ctx, "slrhip_render_adaptive")) return rc;
+    if (!target || !sppDone) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_adaptive: null argument");
+    if (!(target->threshold >= 0.0f) || !(target->floor >= 0.0f)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_adaptive: threshold and floor must be >= 0 (and not NaN)");
+    if (target->spp_min < 2 || target->spp_step == 0 || target->spp_max < target->spp_min)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_adaptive: need spp_min >= 2, spp_step >= 1 and spp_max >= spp_min");
+    if ((uint64_t)sppBegin + target->spp_max > 0xFFFFFFFFull) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_adaptive: pass range beyond 2^32");
+    const RenderParams& shard = ctx->params;
+    if (shard.numSlots == 0 || ctx->activePixels == 0) return SLRHIP_OK;        // an empty shard, or every pixel has retired
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 2; ++k) {
+            if (e == hipSuccess) e = ctx->adaptXY[k].alloc(shard.numPixels);
+            if (e == hipSuccess) e = ctx->adaptIndex[k].alloc(shard.numPixels);
+        }
+        if (e == hipSuccess) e = ctx->adaptOffsets.alloc(adaptiveSelectBlocks(shard.numPixels));
+        if (e == hipSuccess) e = ctx->adaptCount.alloc(1);
+        if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render_adaptive: allocating the active lists: ") + hipGetErrorString(e));
+    }
+    if (const int rc = clearStatistics(ctx, stream)) return rc;
+    const uint64_t budget = resultWindowBudget();
+    uint32_t done = 0;
+    while (ctx->activePixels > 0) {
+        const uint32_t block = adaptiveBlock(target->spp_min, target->spp_step, target->spp_max, done);
+        if (block == 0) break;                                                   // spp_max passes have been handed out
+        // the block as the windows of an ordinary call of `block` passes over the active pixels
+        ActiveWindow list{};
+        const bool compact = ctx->activeList >= 0;
+        if (compact) { list.xy = ctx->adaptXY[ctx->activeList].ptr; list.index = ctx->adaptIndex[ctx->activeList].ptr; list.count = ctx->activePixels; }
+        const uint32_t window = planWindows(ctx->activePixels, shard.spectral != 0, block, budget);
+        HIP_TRY(ctx->results.alloc((size_t)window * ctx->activePixels * (shard.spectral ? 4u : 1u)));
+        ctx->buffers.results = ctx->results.ptr;
+        for (uint32_t w = 0; w < block; w += window) {
+            const uint32_t passes = std::min(window, block - w);
+            if (const int rc = renderWindow(ctx, sppBegin + done + w, passes, stream, compact ? &list : nullptr)) return rc;
+            if (samplesDone) *samplesDone += (uint64_t)ctx->activePixels * passes;
+        }
+        done += block;
+        *sppDone = done;
+        if (const int rc = adaptiveSelect(ctx, *target, stream)) return rc;
+    }
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_framebuffer_mean(slrhip_ctx* ctx, float* deviceDst, size_t numFloats, void* streamPtr) {
+    if (const int rc = checkStatistics(ctx, "slrhip_resolve_framebuffer_mean")) return rc;
+    if (!deviceDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_framebuffer_mean: null argument");
+    const RenderParams& rp = ctx->params;
+    const size_t need = frameFloats(rp);
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_framebuffer_mean: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    if (const int rc = clearStatistics(ctx, stream)) return rc;
+    HIP_TRY(hipMemsetAsync(deviceDst, 0, need * sizeof(float), stream));
+    launchResolveMean(ctx->buffers, rp, ctx->statRecords.ptr, deviceDst, stream);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_framebuffer_mean(slrhip_ctx* ctx, float* hostDst, size_t numFloats) {
+    if (const int rc = checkStatistics(ctx, "slrhip_read_framebuffer_mean")) return rc;
+    if (!hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_framebuffer_mean: null argument");
+    const size_t need = frameFloats(ctx->params);
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_framebuffer_mean: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->resolveScratch.alloc(need));
+    HIP_TRY(hipDeviceSynchronize());                   // renders queued on any stream of the caller's
+    if (const int rc = slrhip_resolve_framebuffer_mean(ctx, ctx->resolveScratch.ptr, need, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hostDst, ctx->resolveScratch.ptr, need * sizeof(float), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+int slrhip_adaptive_active(slrhip_ctx* ctx, uint32_t* hostCount, void*) {
+    if (!ctx || !hostCount) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_adaptive_active: null argument");
+    *hostCount = 0;
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_adaptive_active: call slrhip_render_begin first");
+    *hostCount = ctx->activePixels;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the block lengths of a slrhip_render_adaptive call.
+int slrhip_debug_adaptive_blocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t* blocks, uint32_t maxBlocks, uint32_t* numBlocks) {
+    if (!numBlocks || (maxBlocks && !blocks)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_adaptive_blocks: null argument");
+    const std::vector<uint32_t> plan = planAdaptiveBlocks(sppMin, sppStep, sppMax);
+    *numBlocks = (uint32_t)plan.size();
+    for (uint32_t k = 0; k < std::min<uint32_t>(*numBlocks, maxBlocks); ++k) blocks[k] = plan[k];
     return SLRHIP_OK;
 }
 

@@ -10,7 +10,11 @@ reference's DebugRenderer and features.npz with the raw per-pixel sums.
 `--noise-target X` renders to a noise level instead of a sample count: blocks of `--noise-step` passes until the estimated error
 of the frame (`--noise-metric rmse`: RMS of the per-pixel standard error of the mean luminance; `relative`: that over the mean
 luminance) is at most X or `--max-spp` passes are done; prints the passes reached and the final estimate, writes one image, and
-with `--noise-map FILE.npy` the per-pixel variance of the mean.  Every pixel gets the same passes (no per-pixel adaptive sampling).
+with `--noise-map FILE.npy` the per-pixel variance of the mean.  Every pixel gets the same passes.
+`--adaptive T` stops every pixel on its own instead (Context.render_adaptive): `--spp-min` passes, then blocks of `--noise-step`
+up to `--max-spp`; after each block the pixels whose standard error of the mean luminance is at most T times that mean (times
+`--adaptive-floor` for darker pixels) retire.  The image is written from the mean frame; the samples rendered are printed against
+pixels x sample limit.
 """
 import argparse
 import ctypes as C
@@ -77,6 +81,28 @@ def render_to_noise_target(ctx, st, args, spp, sensitivity):
     return done
 
 
+def render_adaptively(ctx, st, args, spp, sensitivity):
+    """--adaptive: Context.render_adaptive in place of the 1, 2, 4, ... loop; one image ("000.bmp") from the MEAN frame (the pixels
+    hold different numbers of samples), scale brightness x sensitivity in place of brightness / samples x sensitivity."""
+    start = time.time()
+    ctx.statistics_begin()
+    spp_max = max(args.max_spp or spp, args.spp_min)
+    done, samples = ctx.render_adaptive(0, args.adaptive, args.adaptive_floor, args.spp_min, args.noise_step, spp_max)
+    w, h = st.image_width, st.image_height
+    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
+    fb = ctx.read_framebuffer_mean()
+    scale = float(np.float32(st.brightness) * np.float32(sensitivity))
+    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
+    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(os.path.join(args.out, "000.bmp").encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    print("%u samples: 000.bmp, %g[s]" % (done, time.time() - start), flush=True)
+    full = w * h * spp_max
+    print("adaptive %g (floor %g): %u of %u samples rendered (%.1f %%), %u of %u pixels still active after %u passes"
+          % (args.adaptive, args.adaptive_floor, samples, full, 100.0 * samples / full, ctx.adaptive_active(), w * h, done), flush=True)
+    if args.noise_map:
+        np.save(args.noise_map, ctx.statistics(abi.STATISTICS_VARIANCE_OF_MEAN))
+    return done
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m slr_amd.host")
     ap.add_argument("scene")
@@ -93,14 +119,21 @@ def build_parser():
     ap.add_argument("--noise-step", type=int, default=16, metavar="N", help="passes between two stop checks")
     ap.add_argument("--max-spp", type=int, default=0, metavar="N", help="sample limit of --noise-target (default: the sample count)")
     ap.add_argument("--noise-map", default=None, metavar="FILE.npy", help="with --noise-target: write the per-pixel variance of the mean")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="T",
+                    help="per-pixel adaptive sampling: a pixel retires once the standard error of its mean luminance is at most T x that mean")
+    ap.add_argument("--adaptive-floor", type=float, default=0.05, metavar="F", help="with --adaptive: pixels darker than F are judged relative to F")
+    ap.add_argument("--spp-min", type=int, default=16, metavar="N", help="with --adaptive: passes every pixel gets before the first check (>= 2)")
     return ap
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.noise_target is None and (args.noise_map or args.max_spp):
-        ap.error("--noise-map and --max-spp go with --noise-target")
+    if args.noise_target is None and args.adaptive is None and (args.noise_map or args.max_spp):
+        ap.error("--noise-map and --max-spp go with --noise-target or --adaptive")
+    if args.adaptive is not None and (args.noise_target is not None or not args.adaptive >= 0 or not args.adaptive_floor >= 0 or args.spp_min < 2
+                                      or args.noise_step < 1 or args.max_spp < 0):
+        ap.error("--adaptive takes no --noise-target; it and --adaptive-floor must be >= 0, --spp-min >= 2, --noise-step positive, --max-spp non-negative")
     if args.noise_target is not None and (args.noise_step < 1 or args.max_spp < 0 or args.noise_target != args.noise_target):
         ap.error("--noise-step must be positive, --max-spp non-negative and --noise-target a number")
 
@@ -133,6 +166,8 @@ def main(argv=None):
     done, export, img = 0, 1, 0
     if args.noise_target is not None:
         done = spp = render_to_noise_target(ctx, st, args, spp, sensitivity)
+    elif args.adaptive is not None:
+        done = spp = render_adaptively(ctx, st, args, spp, sensitivity)
     while done < spp and img < 16:
         upto = min(export, spp)
         ctx.render(done, upto - done)
