@@ -699,6 +699,73 @@ int slrhip_read_framebuffer_mean(slrhip_ctx* ctx, float* host_dst, size_t num_fl
  * host since the last check (slrhip_render_adaptive blocks), so nothing is queued on `stream`.                                */
 int slrhip_adaptive_active(slrhip_ctx* ctx, uint32_t* host_count, void* stream);   /* pixels of the shard not yet retired */
 
+/* ---- denoising: a variance-guided, edge-avoiding a-trous filter on device buffers --------------------------------------------
+ * The feature buffers, the noise records and the mean frame above are the inputs of a denoiser; this is the denoiser: the 5 x 5
+ * B3-spline a-trous wavelet filter with the edge-stopping weights of SVGF (normal, distance, luminance over the local standard
+ * deviation), `iterations` passes with the tap distance doubling.  It is a PURE FUNCTION OF THE CALLER'S DEVICE BUFFERS: it never
+ * reads the render state, needs no scene and no slrhip_render_begin; the context only names the device and owns the scratch.
+ *
+ * The definition.  Everything is float32, every operation IEEE-rounded on its own (no fused multiply-add), no transcendental
+ * function; sqrtf and division are the correctly rounded ones.  p, q are pixels, C = components.
+ *   Guides, once per call.  hit_p = coverage != NULL && coverage_p > 0.  For a hit pixel, with `normal` given:
+ *     len = sqrtf((Nx*Nx + Ny*Ny) + Nz*Nz);  n_p = N / len component-wise (by division) if len > 0, else (0, 0, 0);
+ *   with `distance` given: z_p = distance_p / coverage_p.
+ *   Luminance.  Y(c) = the expression of slrhip_sample_luminance on the pixel's C components.
+ *   Iterations.  Iteration i = 0 .. iterations - 1 has the step s = 2^i and the input (c, v), colour and variance:
+ *     c_0 = color;  v_0 = variance, or all zeros if variance is NULL.
+ *   Taps.  h = {1/16, 1/4, 3/8, 1/4, 1/16}, indexed by d + 2.  The taps of the centre p = (x, y) are q = (x + dx*s, y + dy*s);
+ *     dy is the OUTER loop from -2 to 2, dx the INNER loop from -2 to 2, and all sums below add in that order, starting from 0.0f.
+ *     A tap is skipped if it lies outside the image or if hit_q != hit_p.
+ *   Centre tap (dx = dy = 0): w = h[2]*h[2], unconditionally.
+ *   Other taps: w = ((h[dx+2]*h[dy+2]) * w_n) * w_z * w_l, evaluated left to right, with
+ *     w_n = 1 if normal is NULL or !hit_p; else t = fmaxf(0.0f, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z), then t = t*t repeated
+ *           normal_power_log2 times, and w_n = t;
+ *     w_z = 1 if distance is NULL, sigma_distance <= 0 or !hit_p; else d = (float)(s * max(|dx|, |dy|)),
+ *           x = fabsf(z_p - z_q) / ((sigma_distance * d) * z_p), t = fmaxf(0.0f, 1.0f - x), w_z = t*t;
+ *     w_l = 1 if variance is NULL or sigma_luminance <= 0; else x = fabsf(Y(c_p) - Y(c_q)) / (sigma_luminance * sd_p + 1e-20f),
+ *           t = fmaxf(0.0f, 1.0f - x), w_l = t*t;
+ *     sd_p = sqrtf(fmaxf(0.0f, vbar_p)), vbar_p = the 3 x 3 prefilter of this iteration's v at p: weights
+ *           g = {1/16, 1/8, 1/16; 1/8, 1/4, 1/8; 1/16, 1/8, 1/16} at offsets of ONE pixel for every s, in-image taps only, in row-major
+ *           order: vbar = (sum g v_q) / (sum g).
+ *     A tap whose weight w is 0 adds nothing to any sum (its colour is not read).
+ *   Output of the iteration: c'_p[k] = (sum w * c_q[k]) / W with W = sum w;  v'_p = (sum (w*w) * v_q) / (W*W).
+ *   The last iteration's c' goes to `output`, its v' to `output_variance`.
+ * Consequences.  fmaxf(0, NaN) is 0, so a tap with a NaN guide, a NaN luminance or a zero or NaN denominator gets weight 0.  With
+ * the luminance stop on, a non-finite pixel stays where it is: it is the centre of its own filter only, and W >= 9/64 always.  With
+ * the luminance stop off a NaN or an infinity SPREADS to every pixel whose taps reach it.  Pixels that miss everything (environment,
+ * background) are filtered among themselves, by luminance alone.  A pixel with v = 0 merges only with taps of exactly equal
+ * luminance.  Each pixel's sums are formed by one thread in the stated order: the result does not depend on scheduling.
+ *
+ * The call.  All pointers are DEVICE pointers, 4-byte aligned.  The inputs are the channels exactly as the resolve calls write them
+ * (SUMS for the features, means for the colour), so a multi-GPU host reduces the shards' five buffers and denoises on the root with
+ * no extra pass.  Ordered on `stream`, non-blocking, copies nothing to the host.  The scratch, slrhip_denoise_scratch_bytes bytes
+ * = width * height * (32 + 2 * (components == 3 ? 16 : 64)) (one 16-byte guide record and two 8-byte {Y, v} records per pixel, two
+ * colour planes of float4s), is allocated by the first call and by any call that needs more, kept, and freed with the context; a call
+ * that fits the scratch it finds allocates nothing.  The denoise calls of one context go on one stream, or the caller synchronises
+ * between them: they share the scratch.
+ * SLRHIP_ERR_INVALID_ARGUMENT, with nothing written: a null context or descriptor; a zero size or width * height >= 2^31; a null
+ * or misaligned color or output, another misaligned pointer; components other than 3 or 16; iterations outside 1 .. 8;
+ * normal_power_log2 > 7; a nonzero `reserved`; a NaN sigma; normal or distance without coverage; output or output_variance
+ * overlapping any input or each other (byte ranges).  A failed allocation: SLRHIP_ERR_OUT_OF_MEMORY, the context stays usable.   */
+typedef struct slrhip_denoise_desc {
+    uint32_t width, height;       /* >= 1 each; width * height < 2^31 */
+    uint32_t components;          /* 3 or 16 (the two modes; the luminance is defined for these) */
+    uint32_t iterations;          /* 1 .. 8: iteration i uses step 2^i */
+    const float* color;           /* [H][W][C] per-pixel MEANS (slrhip_resolve_framebuffer_mean, or sum / spp) */
+    const float* variance;        /* [H][W] variance of the mean luminance (SLRHIP_STATISTICS_VARIANCE_OF_MEAN), or NULL */
+    const float* normal;          /* [H][W][3] SUM of shading normals (SLRHIP_FEATURE_SHADING_NORMAL as resolved), or NULL */
+    const float* distance;        /* [H][W] SUM of distances (SLRHIP_FEATURE_DISTANCE as resolved), or NULL */
+    const float* coverage;        /* [H][W] SLRHIP_FEATURE_COVERAGE; required when normal or distance is given, else may be NULL */
+    float* output;                /* [H][W][C] */
+    float* output_variance;       /* [H][W] the filtered variance, or NULL */
+    float sigma_luminance;        /* > 0: luminance stop in standard deviations (SVGF uses 4); <= 0 or variance NULL: off */
+    float sigma_distance;         /* > 0: accepted relative change of distance per pixel of offset; <= 0 or distance NULL: off */
+    uint32_t normal_power_log2;   /* 0 .. 7: the normal weight is max(0, n.n')^(2^k), by k squarings (SVGF: 7) */
+    uint32_t reserved;            /* 0 */
+} slrhip_denoise_desc;
+int    slrhip_denoise(slrhip_ctx* ctx, const slrhip_denoise_desc* desc, void* stream);
+size_t slrhip_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t components);  /* pure; 0 for invalid arguments */
+
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */
 enum { SLRHIP_SPECTRUMTYPE_REFLECTANCE = 0, SLRHIP_SPECTRUMTYPE_ILLUMINANT = 1, SLRHIP_SPECTRUMTYPE_IOR = 2 };

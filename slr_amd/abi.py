@@ -135,6 +135,19 @@ class AdaptiveTarget(C.Structure):
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("spp_min", C.c_uint32), ("spp_step", C.c_uint32), ("spp_max", C.c_uint32)]
 
 
+class DenoiseDesc(C.Structure):
+    """slrhip_denoise_desc: every pointer is a DEVICE pointer (an integer address, or None)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_uint32), ("iterations", C.c_uint32),
+                ("color", C.c_void_p), ("variance", C.c_void_p), ("normal", C.c_void_p), ("distance", C.c_void_p), ("coverage", C.c_void_p),
+                ("output", C.c_void_p), ("output_variance", C.c_void_p),
+                ("sigma_luminance", C.c_float), ("sigma_distance", C.c_float), ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# Context.denoise's default sigma_distance: the accepted relative change of the camera distance per pixel of tap offset
+# (DESIGN.md records how it was picked on the Cornell scenes)
+DENOISE_SIGMA_DISTANCE = 0.1
+
+
 def noise_metric(summary, metric=NOISE_RMSE):
     """The stop check of slrhip_render_until on a statistics summary (a dict of Context.statistics_summary, or the sum of
     several shards' dicts): NOISE_RMSE = sqrt(sum_variance_of_mean / pixels), NOISE_RELATIVE = that over the mean luminance."""

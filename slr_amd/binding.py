@@ -17,6 +17,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_query_status", "slrhip_render_features", "slrhip_resolve_features", "slrhip_read_features", "slrhip_camera_rays", "slrhip_features_status",
            "slrhip_statistics_begin", "slrhip_resolve_statistics", "slrhip_read_statistics", "slrhip_statistics_summary", "slrhip_render_until", "slrhip_sample_luminance",
            "slrhip_render_adaptive", "slrhip_resolve_framebuffer_mean", "slrhip_read_framebuffer_mean", "slrhip_adaptive_active", "slrhip_debug_adaptive_blocks",
+           "slrhip_denoise", "slrhip_denoise_scratch_bytes",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -87,6 +88,11 @@ def load_library():
                            ("slrhip_debug_adaptive_blocks", [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
+    # (and one from before the denoiser lacks these two)
+    if path == LIB_PATH or hasattr(lib, "slrhip_denoise"):
+        lib.slrhip_denoise.argtypes = [C.c_void_p, C.POINTER(abi.DenoiseDesc), C.c_void_p]
+        lib.slrhip_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.slrhip_denoise_scratch_bytes.restype = C.c_size_t
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
@@ -140,6 +146,7 @@ class Context:
         _check(self.lib, self.lib.slrhip_create(C.byref(cfg), C.byref(self.handle)), "slrhip_create")
         self.components = self.lib.slrhip_components(self.handle)
         self.settings = None
+        self.shard = (0, 1)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -156,6 +163,7 @@ class Context:
     def render_begin(self, settings, shard=(0, 1)):
         _check(self.lib, self.lib.slrhip_render_begin(self.handle, C.byref(settings), abi.Shard(*shard)), "slrhip_render_begin")
         self.settings = settings          # a refused call leaves the previous render state, and its frame size, in place
+        self.shard = tuple(shard)
 
     def render(self, spp_begin, spp_count, stream=None):
         _check(self.lib, self.lib.slrhip_render(self.handle, spp_begin, spp_count, stream), "slrhip_render")
@@ -405,6 +413,94 @@ class Context:
         count = C.c_uint32(0)
         _check(self.lib, self.lib.slrhip_adaptive_active(self.handle, C.byref(count), self._stream_handle(stream)), "slrhip_adaptive_active")
         return count.value
+
+    # ---- denoising (slrhip_denoise): a pure function of device buffers ----
+    def denoise_into(self, width, height, components, iterations, color, output, variance=None, normal=None, distance=None, coverage=None,
+                     output_variance=None, sigma_luminance=4.0, sigma_distance=abi.DENOISE_SIGMA_DISTANCE, normal_power_log2=7, stream=None):
+        """The filter of include/slrhip.h over DEVICE pointers (integer addresses; None = not given): color [H][W][C] means,
+        variance [H][W], normal [H][W][3] and distance [H][W] sums, coverage [H][W] -> output [H][W][C] and, if given,
+        output_variance [H][W].  Ordered on `stream`, returns at once.  Needs no scene and no render_begin."""
+        d = abi.DenoiseDesc(width, height, components, iterations, color, variance, normal, distance, coverage, output, output_variance,
+                            sigma_luminance, sigma_distance, normal_power_log2, 0)
+        _check(self.lib, self.lib.slrhip_denoise(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_denoise")
+
+    def _denoise_staged(self, shape, fill, params, want_variance):
+        """hipMalloc the buffers of a denoise call, let `fill(name, device_ptr)` fill the inputs (a name it returns False for is
+        passed as NULL), run the filter on the null stream and copy the result back."""
+        h, w, comps = shape
+        sizes = {"color": h * w * comps, "variance": h * w, "normal": h * w * 3, "distance": h * w, "coverage": h * w}
+        hip = _hip_runtime()
+        ptrs = {}
+
+        def malloc(name, floats):
+            p = C.c_void_p()
+            _hip_check(hip.hipMalloc(C.byref(p), max(4 * floats, 16)), "hipMalloc")
+            ptrs[name] = p.value
+            return p.value
+        out, out_v = np.empty((h, w, comps), np.float32), np.empty((h, w), np.float32)
+        try:
+            given = {name: malloc(name, n) for name, n in sizes.items() if fill(name, None)}
+            for name, p in given.items():
+                fill(name, p)
+            self.denoise_into(w, h, comps, color=given["color"], output=malloc("output", out.size),
+                              output_variance=malloc("output_variance", out_v.size) if want_variance else None,
+                              **{k: given.get(k) for k in ("variance", "normal", "distance", "coverage")}, **params)
+            self.synchronize()
+            _hip_check(hip.hipMemcpy(out.ctypes.data, ptrs["output"], out.nbytes, 2), "hipMemcpy")
+            if want_variance:
+                _hip_check(hip.hipMemcpy(out_v.ctypes.data, ptrs["output_variance"], out_v.nbytes, 2), "hipMemcpy")
+        finally:
+            for p in ptrs.values():
+                hip.hipFree(p)
+        return (out, out_v) if want_variance else out
+
+    def denoise(self, color, variance=None, normal=None, distance=None, coverage=None, iterations=5, sigma_luminance=4.0,
+                sigma_distance=abi.DENOISE_SIGMA_DISTANCE, normal_power_log2=7, want_variance=False):
+        """The filter over HOST arrays: color [H, W, 3 or 16] per-pixel means, the guides as the read-outs give them (variance of the
+        mean luminance [H, W]; sums of shading normals [H, W, 3] and distances [H, W]; coverage [H, W]; None = not given).  The
+        arrays are copied to the device and the result back: the filtered frame, or (frame, filtered variance) with
+        want_variance.  Synchronises."""
+        host = {"color": color, "variance": variance, "normal": normal, "distance": distance, "coverage": coverage}
+        host = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in host.items() if v is not None}
+        if host["color"].ndim != 3:
+            raise ValueError("color: a [height, width, components] array expected")
+        h, w, _ = shape = host["color"].shape
+        for name, want in (("variance", (h, w)), ("normal", (h, w, 3)), ("distance", (h, w)), ("coverage", (h, w))):
+            if name in host and host[name].shape != want:
+                raise ValueError("%s: shape %r expected" % (name, want))
+        hip = _hip_runtime()
+
+        def fill(name, ptr):
+            if ptr is not None:
+                _hip_check(hip.hipMemcpy(ptr, host[name].ctypes.data, host[name].nbytes, 1), "hipMemcpy")
+            return name in host
+        params = dict(iterations=iterations, sigma_luminance=sigma_luminance, sigma_distance=sigma_distance, normal_power_log2=normal_power_log2)
+        return self._denoise_staged(shape, fill, params, want_variance)
+
+    def denoised(self, want_variance=False, **params):
+        """The current render's frame, denoised: after a render with statistics on and render_features(abi.FEATURE_SHADING_NORMAL |
+        abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE, ...).  The mean frame, the variance of the mean and the three guides are
+        resolved ON THE DEVICE and filtered there; only the result comes back.  **params: iterations, sigma_luminance,
+        sigma_distance, normal_power_log2 of denoise().  A whole-image shard only: the taps of a pixel reach into other shards'
+        tiles (a multi-GPU host reduces the five buffers onto one rank and denoises there)."""
+        if self.settings is None:
+            raise SlrHipError("denoised: call render_begin first")
+        if tuple(self.shard) != (0, 1):
+            raise SlrHipError("denoised: the context renders shard %r; the filter needs the whole image (reduce the buffers, then denoise)" % (self.shard,))
+        h, w = self.settings.image_height, self.settings.image_width
+        resolve = {"color": lambda p, n: self.mean_into(p, n),
+                   "variance": lambda p, n: self.statistics_into(abi.STATISTICS_VARIANCE_OF_MEAN, p, n),
+                   "normal": lambda p, n: self.features_into(abi.FEATURE_SHADING_NORMAL, p, n),
+                   "distance": lambda p, n: self.features_into(abi.FEATURE_DISTANCE, p, n),
+                   "coverage": lambda p, n: self.features_into(abi.FEATURE_COVERAGE, p, n)}
+        floats = {"color": h * w * self.components, "variance": h * w, "normal": h * w * 3, "distance": h * w, "coverage": h * w}
+
+        def fill(name, ptr):
+            if ptr is not None:
+                resolve[name](ptr, floats[name])
+            return True
+        params.setdefault("iterations", 5)
+        return self._denoise_staged((h, w, self.components), fill, params, want_variance)
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

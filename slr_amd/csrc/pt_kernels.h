@@ -330,4 +330,18 @@ void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* st
 // the frame as per-pixel means: sum / (float)n with n of the pixel's record, 0 where n == 0 (dst cleared by the caller)
 void launchResolveMean(const PathBuffers& pb, const RenderParams& rp, const float4* records, float* dst, hipStream_t stream);
 
+// The denoiser (slrhip_denoise; pt_denoise.hip): the filter of include/slrhip.h over the caller's buffers.  The scratch
+// (render_plan.h: denoiseScratchBytes) holds, per pixel, one guide record {n.x, n.y, n.z, z} (a miss: n.x = -INFINITY), two {Y, v}
+// records and two colour records (one float4 for 3 components, four for 16) that the iterations alternate between.
+struct DenoiseParams {
+    uint32_t width, height, components, iterations;
+    const float* color; const float* variance; const float* normal; const float* distance; const float* coverage;
+    float* output; float* outputVariance;
+    float sigmaLuminance, sigmaDistance;
+    uint32_t normalPowerLog2;
+    float4* guides; float2* yv[2]; float4* planes[2];      // the scratch, cut up by the caller
+};
+// one prepare launch and `iterations` filter launches on `stream`
+void launchDenoise(const DenoiseParams& dp, hipStream_t stream);
+
 } // namespace slrhip

@@ -139,4 +139,29 @@ std::vector<uint32_t> planAdaptiveBlocks(uint32_t sppMin, uint32_t sppStep, uint
     return blocks;
 }
 
+DenoiseScratch denoiseScratch(uint32_t width, uint32_t height, uint32_t components) {
+    DenoiseScratch s;
+    const uint64_t pixels = (uint64_t)width * height;
+    if (pixels == 0 || pixels >= (1ull << 31) || (components != 3 && components != 16)) return s;
+    const size_t plane = (size_t)pixels * (components == 3 ? 16u : 64u);
+    s.guides = 0;
+    s.planes[0] = (size_t)pixels * 16u;
+    s.planes[1] = s.planes[0] + plane;
+    s.yv[0] = s.planes[1] + plane;
+    s.yv[1] = s.yv[0] + (size_t)pixels * 8u;
+    s.bytes = s.yv[1] + (size_t)pixels * 8u;               // = pixels x (32 + 2 x (16 or 64)) <= 2^31 x 160
+    return s;
+}
+
+bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    if (aBytes == 0 || bBytes == 0) return false;
+    // a0 < b0 + bBytes && b0 < a0 + aBytes, written without a sum that could wrap
+    return a0 < b0 ? b0 - a0 < aBytes : a0 - b0 < bBytes;
+}
+
 } // namespace slrhip
+
+extern "C" size_t slrhip_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t components) {
+    return slrhip::denoiseScratch(width, height, components).bytes;
+}

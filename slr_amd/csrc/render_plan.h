@@ -61,4 +61,16 @@ uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail
 uint32_t adaptiveBlock(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t done);
 std::vector<uint32_t> planAdaptiveBlocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax);
 
+// The scratch of slrhip_denoise, in the order it is cut up: guide records (16 B per pixel), the two colour planes (16 B per pixel
+// for 3 components, 64 B for 16), the two {Y, v} planes (8 B per pixel): every offset is a multiple of the record that lives there.
+// bytes = 0 for a size the entry point refuses (a zero side, width * height >= 2^31, components other than 3 or 16).
+struct DenoiseScratch {
+    size_t guides = 0, planes[2] = {0, 0}, yv[2] = {0, 0};   // byte offsets
+    size_t bytes = 0;
+};
+DenoiseScratch denoiseScratch(uint32_t width, uint32_t height, uint32_t components);
+
+// Do the byte ranges [a, a + aBytes) and [b, b + bBytes) share a byte?  An empty range shares none.
+bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes);
+
 } // namespace slrhip

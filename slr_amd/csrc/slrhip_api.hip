@@ -173,6 +173,8 @@ struct slrhip_ctx {
     DevArray<uint32_t> adaptOffsets, adaptCount;  // the select's workgroup offsets; the new list's length (read back once per block)
     uint32_t activePixels = 0;                    // pixels of the shard not yet retired since render_begin
     int activeList = -1;                          // the pair that holds them; -1: every pixel of the shard (no check has run yet)
+    // the denoiser (slrhip_denoise): allocated by the first call and by any call that needs more, never by a render
+    DevArray<uint8_t> denoiseScratch;
     PathBuffers buffers;
     uint64_t iterations = 0;
     bool firstRenderCall = true;
@@ -1208,6 +1210,51 @@ int slrhip_adaptive_active(slrhip_ctx* ctx, uint32_t* hostCount, void*) {
     *hostCount = 0;
     if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_adaptive_active: call slrhip_render_begin first");
     *hostCount = ctx->activePixels;
+    return SLRHIP_OK;
+}
+
+// The denoiser: argument checks, the scratch, the launch list (pt_denoise.hip).  It reads nothing of the render state.
+int slrhip_denoise(slrhip_ctx* ctx, const slrhip_denoise_desc* d, void* streamPtr) {
+    const auto refuse = [](const char* what) { return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_denoise: ") + what); };
+    if (!ctx || !d) return refuse("null argument");
+    if (d->reserved != 0) return refuse("reserved must be 0");
+    if (d->components != 3 && d->components != 16) return refuse("components must be 3 or 16");
+    if (d->iterations < 1 || d->iterations > 8) return refuse("iterations must be 1 .. 8");
+    if (d->normal_power_log2 > 7) return refuse("normal_power_log2 must be 0 .. 7");
+    if (d->sigma_luminance != d->sigma_luminance || d->sigma_distance != d->sigma_distance) return refuse("a sigma is NaN");
+    const DenoiseScratch scratch = denoiseScratch(d->width, d->height, d->components);
+    if (scratch.bytes == 0) return refuse("width and height must be >= 1 and width * height < 2^31");
+    if (!d->color || !d->output) return refuse("null color or output");
+    const size_t pixels = (size_t)d->width * d->height, plane = pixels * sizeof(float), frame = plane * d->components;
+    struct Range { const void* p; size_t bytes; };
+    const Range inputs[5] = {{d->color, frame}, {d->variance, plane}, {d->normal, 3 * plane}, {d->distance, plane}, {d->coverage, plane}};
+    const Range outputs[2] = {{d->output, frame}, {d->output_variance, plane}};
+    for (const Range& r : inputs) if ((uintptr_t)r.p & 3u) return refuse("a misaligned pointer (4 bytes)");
+    for (const Range& r : outputs) if ((uintptr_t)r.p & 3u) return refuse("a misaligned pointer (4 bytes)");
+    if ((d->normal || d->distance) && !d->coverage) return refuse("normal and distance need coverage");
+    for (const Range& o : outputs)
+        for (const Range& in : inputs)
+            if (o.p && in.p && rangesOverlap(o.p, o.bytes, in.p, in.bytes)) return refuse("an output overlaps an input");
+    if (d->output_variance && rangesOverlap(d->output, frame, d->output_variance, plane)) return refuse("output and output_variance overlap");
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (const hipError_t e = ctx->denoiseScratch.alloc(scratch.bytes)) {
+        (void)hipGetLastError();                           // the context stays usable: the next call allocates again
+        return fail(SLRHIP_ERR_OUT_OF_MEMORY, std::string("slrhip_denoise: allocating the scratch: ") + hipGetErrorString(e));
+    }
+    uint8_t* base = ctx->denoiseScratch.ptr;
+    DenoiseParams dp{};
+    dp.width = d->width; dp.height = d->height; dp.components = d->components; dp.iterations = d->iterations;
+    dp.color = d->color; dp.variance = d->variance; dp.normal = d->normal; dp.distance = d->distance; dp.coverage = d->coverage;
+    dp.output = d->output; dp.outputVariance = d->output_variance;
+    dp.sigmaLuminance = d->sigma_luminance; dp.sigmaDistance = d->sigma_distance; dp.normalPowerLog2 = d->normal_power_log2;
+    dp.guides = reinterpret_cast<float4*>(base + scratch.guides);
+    for (int k = 0; k < 2; ++k) {
+        dp.planes[k] = reinterpret_cast<float4*>(base + scratch.planes[k]);
+        dp.yv[k] = reinterpret_cast<float2*>(base + scratch.yv[k]);
+    }
+    launchDenoise(dp, (hipStream_t)streamPtr);
+    HIP_TRY(hipGetLastError());
     return SLRHIP_OK;
 }
 

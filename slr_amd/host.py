@@ -15,6 +15,9 @@ with `--noise-map FILE.npy` the per-pixel variance of the mean.  Every pixel get
 up to `--max-spp`; after each block the pixels whose standard error of the mean luminance is at most T times that mean (times
 `--adaptive-floor` for darker pixels) retire.  The image is written from the mean frame; the samples rendered are printed against
 pixels x sample limit.
+`--denoise [ITERATIONS]` (default 5, 1 .. 8) also filters the final frame on the device (Context.denoised: the mean frame guided by
+the variance of the mean, the shading normals and the camera distance, which are rendered alongside) and writes
+"<name>_denoised.bmp" next to the last image.
 """
 import argparse
 import ctypes as C
@@ -103,6 +106,20 @@ def render_adaptively(ctx, st, args, spp, sensitivity):
     return done
 
 
+DENOISE_CHANNELS = abi.FEATURE_SHADING_NORMAL | abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE
+
+
+def write_denoised(ctx, st, iterations, sensitivity, path):
+    """--denoise: the filtered MEAN frame (scale brightness x sensitivity, as --adaptive writes its image) to `path`."""
+    w, h = st.image_width, st.image_height
+    fb = ctx.denoised(iterations=iterations)
+    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
+    scale = float(np.float32(st.brightness) * np.float32(sensitivity))
+    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
+    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(path.encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    print("denoised (%u iterations): %s" % (iterations, os.path.basename(path)), flush=True)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m slr_amd.host")
     ap.add_argument("scene")
@@ -123,6 +140,8 @@ def build_parser():
                     help="per-pixel adaptive sampling: a pixel retires once the standard error of its mean luminance is at most T x that mean")
     ap.add_argument("--adaptive-floor", type=float, default=0.05, metavar="F", help="with --adaptive: pixels darker than F are judged relative to F")
     ap.add_argument("--spp-min", type=int, default=16, metavar="N", help="with --adaptive: passes every pixel gets before the first check (>= 2)")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS",
+                    help="also write <name>_denoised.bmp: the final frame filtered on the device (a-trous iterations, 1 .. 8; default 5)")
     return ap
 
 
@@ -136,6 +155,9 @@ def main(argv=None):
         ap.error("--adaptive takes no --noise-target; it and --adaptive-floor must be >= 0, --spp-min >= 2, --noise-step positive, --max-spp non-negative")
     if args.noise_target is not None and (args.noise_step < 1 or args.max_spp < 0 or args.noise_target != args.noise_target):
         ap.error("--noise-step must be positive, --max-spp non-negative and --noise-target a number")
+
+    if args.denoise is not None and not 1 <= args.denoise <= 8:
+        ap.error("--denoise takes 1 .. 8 iterations")
 
     try:
         scene, settings, renderer = scene_language.load_scene(args.scene)
@@ -164,6 +186,9 @@ def main(argv=None):
     lib = ctx.lib
     start = time.time()
     done, export, img = 0, 1, 0
+    name = "000.bmp"
+    if args.denoise is not None and args.noise_target is None and args.adaptive is None:
+        ctx.statistics_begin()                                               # the filter's variance guide; the frame is unchanged in every bit
     if args.noise_target is not None:
         done = spp = render_to_noise_target(ctx, st, args, spp, sensitivity)
     elif args.adaptive is not None:
@@ -183,7 +208,12 @@ def main(argv=None):
             export += export
     if feature_dir is not None:
         os.makedirs(feature_dir, exist_ok=True)
-        write_features(ctx, spp, feature_dir, feature_channels)
+        # one channel set per render: with --denoise the guides ride with the channels asked for
+        write_features(ctx, spp, feature_dir, feature_channels | (DENOISE_CHANNELS if args.denoise is not None else 0))
+    elif args.denoise is not None:
+        ctx.render_features(DENOISE_CHANNELS, spp)
+    if args.denoise is not None:
+        write_denoised(ctx, st, args.denoise, sensitivity, os.path.join(args.out, os.path.splitext(name)[0] + "_denoised.bmp"))
     ctx.close()
     return 0
 
