@@ -766,6 +766,59 @@ typedef struct slrhip_denoise_desc {
 int    slrhip_denoise(slrhip_ctx* ctx, const slrhip_denoise_desc* desc, void* stream);
 size_t slrhip_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t components);  /* pure; 0 for invalid arguments */
 
+/* ---- image export on the device: linear floats -> 8-bit pixels ------------------------------------------------------------------
+ * The last step of render -> mean -> denoise -> image without a read-back of floats: the pixel pipeline of slrhip_tonemap_bgr8 below
+ * (ImageSensor::saveImage, ImageSensor.cpp:138-186) as a kernel over the caller's device buffers.  Like the denoiser it is a PURE
+ * FUNCTION OF THE CALLER'S DEVICE BUFFERS: it reads nothing of the render state, needs no scene and no slrhip_render_begin; the
+ * context only names the device.
+ *
+ * The definition, per pixel, C = components.  Every operation is float32 and IEEE-rounded on its own (no fused multiply-add),
+ * except the steps marked double, whose operands are converted to double, whose operations are IEEE double operations evaluated
+ * left to right, and whose result is rounded to float once.
+ *   C = 3:   RGB[k] = p[k] * scale.
+ *   C = 16:  X = Y = Z = 0.0f;  for b = 0 .. 15 in ascending order: v = p[b] * scale;  X += xbar[b] * v;  Y += ybar[b] * v;
+ *            Z += zbar[b] * v  (the three tables and integralCMF of DiscretizedSpectrum, 16 bins);  X /= integralCMF, Y, Z likewise;
+ *            double:  R = 3.2404542 * X - 1.5371385 * Y - 0.4985314 * Z;   G = -0.9692660 * X + 1.8760108 * Y + 0.0415560 * Z;
+ *                     B = 0.0556434 * X - 0.2040259 * Y + 1.0572252 * Z.
+ *   Clamp:   RGB[k] = RGB[k] < 0 ? 0 : RGB[k]  (a NaN stays).
+ *   Tone:    double:  Y = 0.222485 * R + 0.716905 * G + 0.060610 * B;
+ *            e = (float)exp((double)(-Y));   scaleY = Y != 0 ? (1.0f - e) / Y : 0.0f;   v[k] = fminf(scaleY * RGB[k], 1.0f).
+ *   Gamma:   g[k] = v[k] <= 0.0031308 (compared in double) ? (float)(12.92 * v[k]) : (float)(1.055 * pow((double)v[k], 1.0 / 2.4) - 0.055),
+ *            both in double.
+ *   Byte:    (uint8_t)(256 * fminf(g[k], 0.999f)), the product in float, truncated.
+ * exp and pow are the only library calls, and the only places where two implementations of this definition can differ in a last
+ * bit (slrhip_tonemap_bgr8 calls the host's expf and pow).  Consequence: an output byte can differ from slrhip_tonemap_bgr8's only
+ * where the un-truncated value 256 * fminf(g[k], 0.999f) lies within rounding distance of an integer.
+ * Non-finite and negative values come out as the host function gives them (fminf returns its other operand for a NaN): a pixel with
+ * a NaN in any component, or with +infinity in every component, is 255 in every channel; a channel that is +infinity next to finite
+ * ones is 255 and the finite ones are 0 (C = 3); a negative RGB channel is 0; an all-zero pixel is 0.
+ *
+ * Formats.  Both run the same arithmetic.
+ *   SLRHIP_IMAGE_BGR8_BMP  bottom-up rows (image row i is output row height - 1 - i) of 3 * width + width % 4 bytes, B G R per pixel,
+ *                          the padding bytes 0: byte for byte what slrhip_tonemap_bgr8 fills and slrhip_save_bmp takes.
+ *   SLRHIP_IMAGE_RGBA8     top-down rows of 4 * width bytes, R G B 255: a display surface, a uint8 tensor [H][W][4].
+ *
+ * The call.  Ordered on `stream`, non-blocking; it allocates nothing, copies nothing and does not synchronise, so it can be captured
+ * into a graph from the first call on.  It writes exactly slrhip_tonemap_bytes(width, height, format) bytes, padding included, and
+ * nothing beyond them.  Any `scale` is accepted, as slrhip_tonemap_bgr8 accepts it.
+ * SLRHIP_ERR_INVALID_ARGUMENT, with nothing written: a null context, descriptor, color or output; a misaligned pointer (4 bytes); a
+ * zero size or width * height >= 2^31; components other than 3 or 16; an unknown format; a nonzero `reserved`; output_bytes less
+ * than slrhip_tonemap_bytes; output overlapping color (byte ranges).                                                              */
+#define SLRHIP_IMAGE_BGR8_BMP 0u
+#define SLRHIP_IMAGE_RGBA8    1u
+typedef struct slrhip_tonemap_desc {
+    uint32_t width, height;       /* >= 1 each; width * height < 2^31 */
+    uint32_t components;          /* 3 or 16 */
+    uint32_t format;              /* SLRHIP_IMAGE_* */
+    const float* color;           /* DEVICE [H][W][C]; 4-byte aligned */
+    uint8_t* output;              /* DEVICE; 4-byte aligned */
+    size_t output_bytes;          /* room at output; at least slrhip_tonemap_bytes(width, height, format) */
+    float scale;                  /* as slrhip_tonemap_bgr8's: brightness / samples x sensitivity for a frame of sums */
+    uint32_t reserved;            /* 0 */
+} slrhip_tonemap_desc;
+int    slrhip_tonemap(slrhip_ctx* ctx, const slrhip_tonemap_desc* desc, void* stream);
+size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format);   /* pure; 0 for invalid arguments */
+
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */
 enum { SLRHIP_SPECTRUMTYPE_REFLECTANCE = 0, SLRHIP_SPECTRUMTYPE_ILLUMINANT = 1, SLRHIP_SPECTRUMTYPE_IOR = 2 };

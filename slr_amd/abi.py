@@ -143,6 +143,17 @@ class DenoiseDesc(C.Structure):
                 ("sigma_luminance", C.c_float), ("sigma_distance", C.c_float), ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# slrhip_tonemap's image formats (SLRHIP_IMAGE_*)
+IMAGE_BGR8_BMP = 0      # bottom-up rows of 3 * w + w % 4 bytes, B G R, padding 0: what slrhip_tonemap_bgr8 fills and slrhip_save_bmp takes
+IMAGE_RGBA8 = 1         # top-down rows of 4 * w bytes, R G B 255
+
+
+class TonemapDesc(C.Structure):
+    """slrhip_tonemap_desc: color and output are DEVICE pointers (integer addresses)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_uint32), ("format", C.c_uint32),
+                ("color", C.c_void_p), ("output", C.c_void_p), ("output_bytes", C.c_size_t), ("scale", C.c_float), ("reserved", C.c_uint32)]
+
+
 # Context.denoise's default sigma_distance: the accepted relative change of the camera distance per pixel of tap offset
 # (DESIGN.md records how it was picked on the Cornell scenes)
 DENOISE_SIGMA_DISTANCE = 0.1

@@ -17,7 +17,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_query_status", "slrhip_render_features", "slrhip_resolve_features", "slrhip_read_features", "slrhip_camera_rays", "slrhip_features_status",
            "slrhip_statistics_begin", "slrhip_resolve_statistics", "slrhip_read_statistics", "slrhip_statistics_summary", "slrhip_render_until", "slrhip_sample_luminance",
            "slrhip_render_adaptive", "slrhip_resolve_framebuffer_mean", "slrhip_read_framebuffer_mean", "slrhip_adaptive_active", "slrhip_debug_adaptive_blocks",
-           "slrhip_denoise", "slrhip_denoise_scratch_bytes",
+           "slrhip_denoise", "slrhip_denoise_scratch_bytes", "slrhip_tonemap", "slrhip_tonemap_bytes",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -93,6 +93,11 @@ def load_library():
         lib.slrhip_denoise.argtypes = [C.c_void_p, C.POINTER(abi.DenoiseDesc), C.c_void_p]
         lib.slrhip_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         lib.slrhip_denoise_scratch_bytes.restype = C.c_size_t
+    # (and one from before the device image export lacks these two)
+    if path == LIB_PATH or hasattr(lib, "slrhip_tonemap"):
+        lib.slrhip_tonemap.argtypes = [C.c_void_p, C.POINTER(abi.TonemapDesc), C.c_void_p]
+        lib.slrhip_tonemap_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.slrhip_tonemap_bytes.restype = C.c_size_t
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
@@ -424,9 +429,10 @@ class Context:
                             sigma_luminance, sigma_distance, normal_power_log2, 0)
         _check(self.lib, self.lib.slrhip_denoise(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_denoise")
 
-    def _denoise_staged(self, shape, fill, params, want_variance):
+    def _denoise_staged(self, shape, fill, params, want_variance, image=None):
         """hipMalloc the buffers of a denoise call, let `fill(name, device_ptr)` fill the inputs (a name it returns False for is
-        passed as NULL), run the filter on the null stream and copy the result back."""
+        passed as NULL), run the filter on the null stream and copy the result back; with image = (scale, format) the result stays
+        on the device, is tone-mapped there (slrhip_tonemap) and only the 8-bit image comes back."""
         h, w, comps = shape
         sizes = {"color": h * w * comps, "variance": h * w, "normal": h * w * 3, "distance": h * w, "coverage": h * w}
         hip = _hip_runtime()
@@ -445,6 +451,8 @@ class Context:
             self.denoise_into(w, h, comps, color=given["color"], output=malloc("output", out.size),
                               output_variance=malloc("output_variance", out_v.size) if want_variance else None,
                               **{k: given.get(k) for k in ("variance", "normal", "distance", "coverage")}, **params)
+            if image is not None:
+                return self._tonemap_staged(ptrs["output"], w, h, comps, *image)
             self.synchronize()
             _hip_check(hip.hipMemcpy(out.ctypes.data, ptrs["output"], out.nbytes, 2), "hipMemcpy")
             if want_variance:
@@ -477,12 +485,13 @@ class Context:
         params = dict(iterations=iterations, sigma_luminance=sigma_luminance, sigma_distance=sigma_distance, normal_power_log2=normal_power_log2)
         return self._denoise_staged(shape, fill, params, want_variance)
 
-    def denoised(self, want_variance=False, **params):
+    def denoised(self, want_variance=False, image=None, **params):
         """The current render's frame, denoised: after a render with statistics on and render_features(abi.FEATURE_SHADING_NORMAL |
         abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE, ...).  The mean frame, the variance of the mean and the three guides are
         resolved ON THE DEVICE and filtered there; only the result comes back.  **params: iterations, sigma_luminance,
         sigma_distance, normal_power_log2 of denoise().  A whole-image shard only: the taps of a pixel reach into other shards'
-        tiles (a multi-GPU host reduces the five buffers onto one rank and denoises there)."""
+        tiles (a multi-GPU host reduces the five buffers onto one rank and denoises there).  image = (scale, abi.IMAGE_*): the
+        filtered frame is tone-mapped on the device as well and the 8-bit image (as frame_image returns it) comes back in its place."""
         if self.settings is None:
             raise SlrHipError("denoised: call render_begin first")
         if tuple(self.shard) != (0, 1):
@@ -500,7 +509,68 @@ class Context:
                 resolve[name](ptr, floats[name])
             return True
         params.setdefault("iterations", 5)
-        return self._denoise_staged((h, w, self.components), fill, params, want_variance)
+        return self._denoise_staged((h, w, self.components), fill, params, want_variance, image)
+
+    # ---- image export on the device (slrhip_tonemap): a pure function of device buffers ----
+    def tonemap_into(self, width, height, components, color_ptr, output_ptr, output_bytes, scale, format, stream=None):
+        """The image export of include/slrhip.h over DEVICE pointers (integer addresses): color [H][W][C] floats times `scale` ->
+        the 8-bit image in `format` (abi.IMAGE_BGR8_BMP, abi.IMAGE_RGBA8) at output, which has room for output_bytes.  Ordered on
+        `stream`, returns at once.  Needs no scene and no render_begin."""
+        d = abi.TonemapDesc(width, height, components, format, color_ptr, output_ptr, output_bytes, scale, 0)
+        _check(self.lib, self.lib.slrhip_tonemap(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_tonemap")
+
+    def tonemap(self, color, scale, format=abi.IMAGE_RGBA8):
+        """The image of a torch CUDA tensor [H, W, 3 or 16] float32 (contiguous), passed without a copy and tone-mapped in order on
+        torch.cuda.current_stream(): a uint8 device tensor, [H, W, 4] for abi.IMAGE_RGBA8, the flat padded bottom-up rows
+        (slrhip_save_bmp's input) for abi.IMAGE_BGR8_BMP.  Returns at once.  Needs libslrhip.so bound to torch's HIP runtime: import
+        torch before the first Context."""
+        import torch
+        if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3 and color.is_contiguous()):
+            raise ValueError("color: a contiguous [height, width, components] float32 CUDA tensor expected")
+        if color.device.index != self.device:
+            raise SlrHipError("tonemap: the tensor is on device %r, the context on device %d" % (color.device.index, self.device))
+        h, w, comps = color.shape
+        size = self.lib.slrhip_tonemap_bytes(w, h, format)
+        if size == 0:
+            raise ValueError("tonemap: a non-empty image of less than 2^31 pixels and a format of abi.IMAGE_* expected")
+        s = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            out = torch.empty((size,), dtype=torch.uint8, device=color.device)
+            self.tonemap_into(w, h, comps, color.data_ptr(), out.data_ptr(), size, scale, format, s)
+        return out.view(h, w, 4) if format == abi.IMAGE_RGBA8 else out
+
+    def _tonemap_staged(self, color_ptr, width, height, components, scale, format):
+        """The image of the device floats at color_ptr as a numpy uint8 array: hipMalloc the image, tone-map on the null stream,
+        copy the 8-bit rows back."""
+        hip = _hip_runtime()
+        out = np.empty(self.lib.slrhip_tonemap_bytes(width, height, format), np.uint8)
+        p = C.c_void_p()
+        _hip_check(hip.hipMalloc(C.byref(p), max(out.nbytes, 16)), "hipMalloc")
+        try:
+            self.tonemap_into(width, height, components, color_ptr, p.value, out.nbytes, scale, format)
+            self.synchronize()
+            _hip_check(hip.hipMemcpy(out.ctypes.data, p.value, out.nbytes, 2), "hipMemcpy")
+        finally:
+            hip.hipFree(p)
+        return out.reshape(height, width, 4) if format == abi.IMAGE_RGBA8 else out
+
+    def frame_image(self, scale, mean=False, format=abi.IMAGE_BGR8_BMP):
+        """The current render's frame as an 8-bit image, tone-mapped ON THE DEVICE: the frame of sums (or, with mean, of per-pixel
+        means: needs statistics_begin()) is resolved into device memory and only the image comes back: a numpy uint8 array, the flat
+        padded rows slrhip_save_bmp takes, or [H, W, 4] for abi.IMAGE_RGBA8.  Byte for byte what slrhip_tonemap_bgr8 makes of
+        read_framebuffer() / read_framebuffer_mean(), up to the last bit of exp and pow (include/slrhip.h).  Synchronises."""
+        if self.settings is None:
+            raise SlrHipError("frame_image: call render_begin first")
+        h, w = self.settings.image_height, self.settings.image_width
+        floats = h * w * self.components
+        hip = _hip_runtime()
+        p = C.c_void_p()
+        _hip_check(hip.hipMalloc(C.byref(p), 4 * floats), "hipMalloc")
+        try:
+            (self.mean_into if mean else self.resolve_into)(p.value, floats)
+            return self._tonemap_staged(p.value, w, h, self.components, scale, format)
+        finally:
+            hip.hipFree(p)
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

@@ -10,17 +10,19 @@
 #include "../../include/slrhip.h"
 #include "cmf16_table.h"
 #include "pt_luminance.h"
+#include "pt_tonemap.h"
 #include "cmf_2deg_table.h"
 
 namespace {
 
 inline uint32_t fmix32(uint32_t h) { h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16; return h; }
 
-// sRGB_gamma, BasicTypes/Spectrum.cpp:15-21 (float instantiation; literals are double)
-inline float sRGBGamma(float value) {
-    if (value <= 0.0031308) return (float)(12.92 * value);
-    return (float)(1.055 * std::pow((double)value, 1.0 / 2.4) - 0.055);
-}
+// The two library calls of the image export (pt_tonemap.h) as ImageSensor::saveImage makes them: std::exp on a float (expf),
+// std::pow in double.
+struct HostTonemapMath {
+    static float expNeg(float Y) { return std::exp(-Y); }
+    static double gammaPow(float value) { return std::pow((double)value, 1.0 / 2.4); }
+};
 
 // sRGB_degamma, BasicTypes/Spectrum.cpp:24-30 (float instantiation; literals are double)
 inline float sRGBDegamma(float value) {
@@ -272,33 +274,9 @@ int slrhip_tonemap_bgr8(const float* fb, int32_t width, int32_t height, int32_t 
     for (int32_t i = 0; i < height; ++i) {
         for (int32_t j = 0; j < width; ++j) {
             const float* p = fb + ((size_t)i * width + j) * components;
-            float RGB[3];
-            if (components == 3) {
-                RGB[0] = p[0] * scale; RGB[1] = p[1] * scale; RGB[2] = p[2] * scale;       // pixel(j, i) * scale
-            }
-            else {
-                // DiscretizedSpectrum::getRGB, BasicTypes/SpectrumTypes.h:702-721: 16 storage bins -> XYZ -> sRGB
-                float XYZ[3] = {0, 0, 0};
-                for (int b = 0; b < 16; ++b) {
-                    const float v = p[b] * scale;                                          // pixel(j, i) * scale
-                    XYZ[0] += kCmfX16[b] * v;
-                    XYZ[1] += kCmfY16[b] * v;
-                    XYZ[2] += kCmfZ16[b] * v;
-                }
-                XYZ[0] /= kIntegralCmf16; XYZ[1] /= kIntegralCmf16; XYZ[2] /= kIntegralCmf16;
-                // XYZ_to_sRGB, BasicTypes/Spectrum.h:60-64 (double literals, float operands and results)
-                RGB[0] = (float)(3.2404542 * XYZ[0] - 1.5371385 * XYZ[1] - 0.4985314 * XYZ[2]);
-                RGB[1] = (float)(-0.9692660 * XYZ[0] + 1.8760108 * XYZ[1] + 0.0415560 * XYZ[2]);
-                RGB[2] = (float)(0.0556434 * XYZ[0] - 0.2040259 * XYZ[1] + 1.0572252 * XYZ[2]);
-            }
-            for (int k = 0; k < 3; ++k) RGB[k] = RGB[k] < 0.0f ? 0.0f : RGB[k];
-            float Y = (float)(0.222485 * RGB[0] + 0.716905 * RGB[1] + 0.060610 * RGB[2]);
-            float scaleY = Y != 0 ? (1.0f - std::exp(-Y)) / Y : 0.0f;
-            for (int k = 0; k < 3; ++k) RGB[k] = std::fmin(scaleY * RGB[k], 1.0f);
             uint8_t* o = dst + (size_t)(height - i - 1) * byteWidth + 3 * (size_t)j;
-            o[2] = (uint8_t)(256 * std::fmin(sRGBGamma(RGB[0]), 0.999f));
-            o[1] = (uint8_t)(256 * std::fmin(sRGBGamma(RGB[1]), 0.999f));
-            o[0] = (uint8_t)(256 * std::fmin(sRGBGamma(RGB[2]), 0.999f));
+            if (components == 3) slrhip::tonemapPixel<3, HostTonemapMath>(p, scale, o);
+            else slrhip::tonemapPixel<16, HostTonemapMath>(p, scale, o);
         }
     }
     return SLRHIP_OK;

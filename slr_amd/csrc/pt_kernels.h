@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/slrhip.h"
 #include "device_types.h"
 
 namespace slrhip {
@@ -343,5 +344,8 @@ struct DenoiseParams {
 };
 // one prepare launch and `iterations` filter launches on `stream`
 void launchDenoise(const DenoiseParams& dp, hipStream_t stream);
+
+// The image export (slrhip_tonemap; pt_tonemap.hip): one launch on `stream`; the descriptor has passed tonemapRefusal (render_plan.h).
+void launchTonemap(const slrhip_tonemap_desc& d, hipStream_t stream);
 
 } // namespace slrhip

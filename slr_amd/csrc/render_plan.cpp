@@ -160,7 +160,34 @@ bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes) {
     return a0 < b0 ? b0 - a0 < aBytes : a0 - b0 < bBytes;
 }
 
+size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format) {
+    const uint64_t pixels = (uint64_t)width * height;
+    if (pixels == 0 || pixels >= (1ull << 31)) return 0;
+    // 3 * width + width % 4 <= 4 * width: at most 2^33 bytes
+    if (format == SLRHIP_IMAGE_BGR8_BMP) return (size_t)(3ull * width + width % 4u) * height;
+    if (format == SLRHIP_IMAGE_RGBA8) return (size_t)pixels * 4u;
+    return 0;
+}
+
+const char* tonemapRefusal(const slrhip_tonemap_desc& d) {
+    if (d.reserved != 0) return "reserved must be 0";
+    if (d.components != 3 && d.components != 16) return "components must be 3 or 16";
+    if (d.format != SLRHIP_IMAGE_BGR8_BMP && d.format != SLRHIP_IMAGE_RGBA8) return "unknown format";
+    const size_t bytes = tonemapBytes(d.width, d.height, d.format);
+    if (bytes == 0) return "width and height must be >= 1 and width * height < 2^31";
+    if (!d.color || !d.output) return "null color or output";
+    if (((uintptr_t)d.color | (uintptr_t)d.output) & 3u) return "a misaligned pointer (4 bytes)";
+    if (d.output_bytes < bytes) return "output_bytes is less than slrhip_tonemap_bytes";
+    const size_t frame = (size_t)d.width * d.height * d.components * sizeof(float);
+    if (rangesOverlap(d.output, bytes, d.color, frame)) return "output overlaps color";
+    return nullptr;
+}
+
 } // namespace slrhip
+
+extern "C" size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format) {
+    return slrhip::tonemapBytes(width, height, format);
+}
 
 extern "C" size_t slrhip_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t components) {
     return slrhip::denoiseScratch(width, height, components).bytes;

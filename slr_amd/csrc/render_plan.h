@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/slrhip.h"
+
 namespace slrhip {
 
 const uint32_t kDefaultRunLength = 64;         // SLRHIP_RUN_LENGTH: passes of a pixel a wave takes in a row (pt_kernels.h WorkItem; measured: DESIGN.md)
@@ -72,5 +74,11 @@ DenoiseScratch denoiseScratch(uint32_t width, uint32_t height, uint32_t componen
 
 // Do the byte ranges [a, a + aBytes) and [b, b + bBytes) share a byte?  An empty range shares none.
 bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes);
+
+// The image slrhip_tonemap writes (= slrhip_tonemap_bytes): rows of 3 * width + width % 4 bytes (SLRHIP_IMAGE_BGR8_BMP) or of
+// 4 * width bytes (SLRHIP_IMAGE_RGBA8).  0 for what the entry point refuses: a zero side, width * height >= 2^31, an unknown format.
+size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format);
+// The argument checks of slrhip_tonemap on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
+const char* tonemapRefusal(const slrhip_tonemap_desc& d);
 
 } // namespace slrhip

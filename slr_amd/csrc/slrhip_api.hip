@@ -1258,6 +1258,16 @@ int slrhip_denoise(slrhip_ctx* ctx, const slrhip_denoise_desc* d, void* streamPt
     return SLRHIP_OK;
 }
 
+// The image export: the argument checks (render_plan.cpp), one launch (pt_tonemap.hip).  It reads nothing of the render state.
+int slrhip_tonemap(slrhip_ctx* ctx, const slrhip_tonemap_desc* d, void* streamPtr) {
+    if (!ctx || !d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_tonemap: null argument");
+    if (const char* what = tonemapRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_tonemap: ") + what);
+    HIP_TRY(hipSetDevice(ctx->device));
+    launchTonemap(*d, (hipStream_t)streamPtr);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
 // Diagnostic (include/slrhip_debug.h): the block lengths of a slrhip_render_adaptive call.
 int slrhip_debug_adaptive_blocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t* blocks, uint32_t maxBlocks, uint32_t* numBlocks) {
     if (!numBlocks || (maxBlocks && !blocks)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_adaptive_blocks: null argument");

@@ -18,6 +18,9 @@ pixels x sample limit.
 `--denoise [ITERATIONS]` (default 5, 1 .. 8) also filters the final frame on the device (Context.denoised: the mean frame guided by
 the variance of the mean, the shading normals and the camera distance, which are rendered alongside) and writes
 "<name>_denoised.bmp" next to the last image.
+`--device-tonemap` tone-maps every BMP above on the device (Context.frame_image, slrhip_tonemap): the frame is resolved into device
+memory (or is the denoiser's output there) and only the 8-bit rows are copied back, in place of a read-back of the floats and the
+host loop of slrhip_tonemap_bgr8.
 """
 import argparse
 import ctypes as C
@@ -64,18 +67,28 @@ def write_features(ctx, spp, out_dir, channels):
     np.savez(os.path.join(out_dir, "features.npz"), **raw)
 
 
+def write_image(ctx, st, scale, path, source, device_tonemap, **denoise):
+    """frame -> BMP file.  source: "sum" (the frame of sums), "mean" (of per-pixel means) or "denoised" (Context.denoised(**denoise)).
+    The floats are read back and tone-mapped by slrhip_tonemap_bgr8, or with device_tonemap (--device-tonemap) tone-mapped where they
+    are and only the image is read back."""
+    w, h = st.image_width, st.image_height
+    if device_tonemap:
+        bmp = ctx.denoised(image=(scale, abi.IMAGE_BGR8_BMP), **denoise) if source == "denoised" else ctx.frame_image(scale, mean=source == "mean")
+    else:
+        fb = ctx.denoised(**denoise) if source == "denoised" else ctx.read_framebuffer_mean() if source == "mean" else ctx.read_framebuffer()
+        bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
+        binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
+    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(path.encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+
+
 def render_to_noise_target(ctx, st, args, spp, sensitivity):
     """--noise-target: Context.render_until in place of the 1, 2, 4, ... loop; one image ("000.bmp") of the passes reached."""
     start = time.time()
     ctx.statistics_begin()
     metric = abi.NOISE_METRICS[args.noise_metric]
     done, summary = ctx.render_until(metric, args.noise_target, args.noise_step, args.max_spp or spp)
-    w, h = st.image_width, st.image_height
-    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
-    fb = ctx.read_framebuffer()
     scale = float(np.float32(np.float32(st.brightness) / np.float32(done)) * np.float32(sensitivity))
-    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
-    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(os.path.join(args.out, "000.bmp").encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    write_image(ctx, st, scale, os.path.join(args.out, "000.bmp"), "sum", args.device_tonemap)
     print("%u samples: 000.bmp, %g[s]" % (done, time.time() - start), flush=True)
     print("noise target %g (%s): reached %g after %u samples%s" % (args.noise_target, args.noise_metric, abi.noise_metric(summary, metric), done,
                                                                   "" if abi.noise_metric(summary, metric) <= args.noise_target else " (sample limit)"), flush=True)
@@ -92,11 +105,8 @@ def render_adaptively(ctx, st, args, spp, sensitivity):
     spp_max = max(args.max_spp or spp, args.spp_min)
     done, samples = ctx.render_adaptive(0, args.adaptive, args.adaptive_floor, args.spp_min, args.noise_step, spp_max)
     w, h = st.image_width, st.image_height
-    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
-    fb = ctx.read_framebuffer_mean()
     scale = float(np.float32(st.brightness) * np.float32(sensitivity))
-    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
-    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(os.path.join(args.out, "000.bmp").encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    write_image(ctx, st, scale, os.path.join(args.out, "000.bmp"), "mean", args.device_tonemap)
     print("%u samples: 000.bmp, %g[s]" % (done, time.time() - start), flush=True)
     full = w * h * spp_max
     print("adaptive %g (floor %g): %u of %u samples rendered (%.1f %%), %u of %u pixels still active after %u passes"
@@ -109,14 +119,10 @@ def render_adaptively(ctx, st, args, spp, sensitivity):
 DENOISE_CHANNELS = abi.FEATURE_SHADING_NORMAL | abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE
 
 
-def write_denoised(ctx, st, iterations, sensitivity, path):
+def write_denoised(ctx, st, iterations, sensitivity, path, device_tonemap=False):
     """--denoise: the filtered MEAN frame (scale brightness x sensitivity, as --adaptive writes its image) to `path`."""
-    w, h = st.image_width, st.image_height
-    fb = ctx.denoised(iterations=iterations)
-    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
     scale = float(np.float32(st.brightness) * np.float32(sensitivity))
-    binding._check(ctx.lib, ctx.lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
-    binding._check(ctx.lib, ctx.lib.slrhip_save_bmp(path.encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+    write_image(ctx, st, scale, path, "denoised", device_tonemap, iterations=iterations)
     print("denoised (%u iterations): %s" % (iterations, os.path.basename(path)), flush=True)
 
 
@@ -142,6 +148,8 @@ def build_parser():
     ap.add_argument("--spp-min", type=int, default=16, metavar="N", help="with --adaptive: passes every pixel gets before the first check (>= 2)")
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS",
                     help="also write <name>_denoised.bmp: the final frame filtered on the device (a-trous iterations, 1 .. 8; default 5)")
+    ap.add_argument("--device-tonemap", action="store_true",
+                    help="tone-map every BMP on the device and read back only the 8-bit image, not the float frame")
     return ap
 
 
@@ -181,9 +189,6 @@ def main(argv=None):
     ctx.render_begin(st)
     cam = scene.camera
     sensitivity = cam.sensitivity if cam.sensitivity > 0 else float(np.float32(1.0 / (np.pi * float(np.float32(cam.lens_radius)) ** 2))) if cam.lens_radius > 0 else 1.0
-    w, h = st.image_width, st.image_height
-    bmp = np.zeros((3 * w + w % 4) * h, np.uint8)
-    lib = ctx.lib
     start = time.time()
     done, export, img = 0, 1, 0
     name = "000.bmp"
@@ -198,11 +203,9 @@ def main(argv=None):
         ctx.render(done, upto - done)
         done = upto
         if done == export:
-            fb = ctx.read_framebuffer()
             name = "%03u.bmp" % img
             scale = float(np.float32(np.float32(st.brightness) / np.float32(done)) * np.float32(sensitivity))
-            binding._check(lib, lib.slrhip_tonemap_bgr8(fb.ctypes.data, w, h, ctx.components, C.c_float(scale), bmp.ctypes.data, bmp.size), "slrhip_tonemap_bgr8")
-            binding._check(lib, lib.slrhip_save_bmp(os.path.join(args.out, name).encode(), bmp.ctypes.data, w, h), "slrhip_save_bmp")
+            write_image(ctx, st, scale, os.path.join(args.out, name), "sum", args.device_tonemap)
             print("%u samples: %s, %g[s]" % (export, name, time.time() - start), flush=True)
             img += 1
             export += export
@@ -213,7 +216,7 @@ def main(argv=None):
     elif args.denoise is not None:
         ctx.render_features(DENOISE_CHANNELS, spp)
     if args.denoise is not None:
-        write_denoised(ctx, st, args.denoise, sensitivity, os.path.join(args.out, os.path.splitext(name)[0] + "_denoised.bmp"))
+        write_denoised(ctx, st, args.denoise, sensitivity, os.path.join(args.out, os.path.splitext(name)[0] + "_denoised.bmp"), args.device_tonemap)
     ctx.close()
     return 0
 
