@@ -552,6 +552,58 @@ int slrhip_camera_rays(slrhip_ctx* ctx, uint32_t pass, slrhip_ray* rays, uint32_
  * traced), read in order on `stream` and written to HOST memory *bits.  Waits for that stream only.                          */
 int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
 
+/* ---- albedo: the first-hit base colour, accumulated like the feature channels ---------------------------------------------------
+ * What a denoiser divides the frame by (slrhip_modulate below): per sample, the reference's BSDF::getBaseColor(DirectionType::All)
+ * (Core/directional_distribution_functions.h:293-297) at the camera ray's first hit.  Its own calls, not a channel bit of
+ * slrhip_render_features: the buffer has `components` floats per pixel and differs between the RGB and the spectral mode.
+ *
+ * The definition, per (pixel, pass) of the shard.
+ *   Ray:      the camera ray slrhip_render and slrhip_render_features trace for that (pixel, pass): same seed, same draws.
+ *   Hit:      the closest hit of the aggregate, with the alpha test the render applies.  A miss (the environment sphere is a miss)
+ *             has the value 1.0 in every component: radiance that reaches the camera unscattered is divided by one.
+ *   Material: the hit triangle's material record; each spectrum slot that names a texture is replaced by the texture's value at the
+ *             hit's texture coordinate, interpolated from the ORIGINAL barycentrics (TriangleMesh.cpp:160-161), as the render does.
+ *   Spectra:  RGB mode: the three record values.  Spectral mode: component i is the spectrum's value at lambda_i of
+ *             WavelengthSamples::createWithEqualOffsets(offset, .) (lambda_i = 360 + 470 (i + offset) / 16), offset = the sample's
+ *             wavelength-offset draw (the fourth draw of the camera sample); component i is indexed by i, not binned as the sensor bins.
+ *   Colour:   by material type, every operation float32 and rounded on its own:
+ *               MATTE (Lambert and Oren-Nayar)  R                                    basic_BSDFs.cpp:55, OrenNayerBRDF.cpp:71
+ *               METAL                           coeffR                               basic_BSDFs.cpp:89
+ *               GLASS                           coeff                                basic_BSDFs.cpp:167
+ *               MICROFACET_METAL                FresnelConductor(eta, k).evaluate(1.0f) (the render's Fresnel function at cosine 1)
+ *                                                                                    MicrofacetBSDF.cpp:108
+ *               MICROFACET_GLASS                1 in every component                 MicrofacetBSDF.cpp:313
+ *               WARD                            R                                    ModifiedWardDurBRDF.cpp:84
+ *               ASHIKHMIN                       Rs + (1 - Rs) * Rd, in that order    AshikhminShirleyBRDF.cpp:167
+ *               MULTI                           the lobes in order (nested groups flattened in order), each with the `scale * spectrum`
+ *                                               its getBSDF receives; the first lobe whose colour has a non-zero component wins; zeros if
+ *                                               there is none.  An inverted lobe has its base's colour.  MultiBSDF.cpp:210-218
+ *             An emitting triangle is treated like any other: its BSDF's base colour.
+ *   Sum:      plain float32 sums in pass order, one lane per pixel, like the feature channels.  sum / passes is the mean albedo, also of
+ *             a partially covered pixel (a miss counts as one), so no coverage buffer is needed.
+ *
+ * The contract mirrors the feature calls.  Cleared by slrhip_render_begin; independent of the shard split, of how ascending passes are
+ * cut into calls, of the tree kind and of scheduling.  Stream-ordered and NON-BLOCKING.  The first albedo call after a
+ * slrhip_render_begin allocates (the sums: components x 4 B per pixel; the record window, which is the feature pass's: 16 B per
+ * (pixel, pass), 20 B for a scene with textures, at most 64 passes) and is not capturable; later calls allocate nothing, copy
+ * nothing, do not synchronise and may be captured.  The record window is shared with the feature pass: the albedo and feature calls of
+ * one context go on ONE stream (or the caller synchronises between them), and the first feature call and the first albedo call after
+ * a slrhip_render_begin may each allocate — and either may MOVE the shared record window when it needs more room than the other
+ * sized it for.  A graph that holds feature or albedo calls of a context that uses both must therefore be captured after BOTH
+ * first calls of that slrhip_render_begin: a call captured earlier holds the window's old address.  Feature calls, albedo calls and slrhip_render calls interleave freely: none changes a bit of
+ * another's result, of the counters or of the error words.  A traversal that gives up sets the FEATURE error word
+ * (slrhip_features_status); slrhip_read_albedo fails on it as slrhip_read_features does.
+ * Errors: SLRHIP_ERR_NO_SCENE before slrhip_render_begin; SLRHIP_ERR_INVALID_ARGUMENT for a null context, a pass range beyond 2^32, a
+ * null or misaligned (4 bytes) destination or too little room; spp_count == 0 does nothing.                                       */
+int slrhip_render_albedo(slrhip_ctx* ctx, uint32_t spp_begin, uint32_t spp_count, void* stream);
+/* The SUMS into DEVICE memory as [height][width][components] float32, zeros outside the shard, so that shards add like the frame;
+ * num_floats: room at device_dst, at least width x height x components.  *passes (HOST memory, may be NULL; written at the call): the
+ * number of passes accumulated since slrhip_render_begin, the divisor of the mean.  Stream-ordered, non-blocking, allocates nothing;
+ * before the first albedo call the sums are zeros and *passes is 0.                                                                */
+int slrhip_resolve_albedo(slrhip_ctx* ctx, float* device_dst, size_t num_floats, uint32_t* passes, void* stream);
+/* The same into HOST memory: resolves, waits for the device, and fails with SLRHIP_ERR_HIP if the feature error word is set.       */
+int slrhip_read_albedo(slrhip_ctx* ctx, float* host_dst, size_t num_floats, uint32_t* passes);
+
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
 
@@ -818,6 +870,44 @@ typedef struct slrhip_tonemap_desc {
 } slrhip_tonemap_desc;
 int    slrhip_tonemap(slrhip_ctx* ctx, const slrhip_tonemap_desc* desc, void* stream);
 size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format);   /* pure; 0 for invalid arguments */
+
+/* ---- albedo demodulation: divide a frame by the albedo, multiply it back -------------------------------------------------------------
+ * The denoiser's luminance stop cannot tell a texture edge from noise.  The cure: divide the frame by the first-hit albedo
+ * (slrhip_resolve_albedo), filter the smooth irradiance (slrhip_denoise), multiply back.  Like the denoiser and the image export this is a
+ * PURE FUNCTION OF THE CALLER'S DEVICE BUFFERS: it reads nothing of the render state, needs no scene and no slrhip_render_begin; the
+ * context only names the device.
+ *
+ * The definition, per pixel, C = components.  Everything is float32, every operation IEEE-rounded on its own (no fused multiply-add).
+ *   a[k] = fmaxf(albedo[k] / (float)albedo_passes, floor)        (fmaxf returns its other operand for a NaN: a NaN albedo becomes floor)
+ *   ya   = Y(a), the expression of slrhip_sample_luminance on the C values a[k]
+ *   SLRHIP_MODULATE_DIVIDE:    output[k] = color[k] / a[k];   output_variance = variance / (ya * ya)
+ *   SLRHIP_MODULATE_MULTIPLY:  output[k] = color[k] * a[k];   output_variance = variance * (ya * ya)
+ * `variance` is the variance of a luminance (SLRHIP_STATISTICS_VARIANCE_OF_MEAN, slrhip_denoise's output_variance): it is scaled by
+ * the square of the albedo's luminance, which is exact for a grey albedo.
+ *
+ * The call.  All pointers are DEVICE pointers, 4-byte aligned.  Ordered on `stream`, non-blocking; it allocates nothing, copies nothing
+ * and does not synchronise, so it can be captured into a graph from the first call on.  `output` may be exactly `color`, and
+ * `output_variance` exactly `variance` (in place); any other overlap of an output with a buffer of the call is refused.
+ * SLRHIP_ERR_INVALID_ARGUMENT, with nothing written: a null context or descriptor; a zero size or width * height >= 2^31; components
+ * other than 3 or 16; an unknown op; albedo_passes == 0; a floor that is not finite or <= 0; a nonzero `reserved`; a null color,
+ * albedo or output; a misaligned pointer; output_variance without variance; an output that overlaps another buffer (byte ranges) other
+ * than being exactly equal to its own input.                                                                                       */
+#define SLRHIP_MODULATE_DIVIDE   0u
+#define SLRHIP_MODULATE_MULTIPLY 1u
+typedef struct slrhip_modulate_desc {
+    uint32_t width, height;       /* >= 1 each; width * height < 2^31 */
+    uint32_t components;          /* 3 or 16 */
+    uint32_t op;                  /* SLRHIP_MODULATE_* */
+    const float* color;           /* [H][W][C] */
+    const float* variance;        /* [H][W] variance of the mean luminance, or NULL */
+    const float* albedo;          /* [H][W][C] SUMS as slrhip_resolve_albedo writes them */
+    float* output;                /* [H][W][C]; may be exactly `color` */
+    float* output_variance;       /* [H][W] or NULL; may be exactly `variance` */
+    uint32_t albedo_passes;       /* >= 1: the divisor of the albedo sums (slrhip_resolve_albedo's *passes) */
+    float floor;                  /* > 0, finite: the smallest albedo a pixel is divided by */
+    uint32_t reserved;            /* 0 */
+} slrhip_modulate_desc;
+int slrhip_modulate(slrhip_ctx* ctx, const slrhip_modulate_desc* desc, void* stream);
 
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */

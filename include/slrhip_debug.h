@@ -48,6 +48,11 @@ int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shard_index
 int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t spp_max, uint32_t* blocks, uint32_t max_blocks,
                                  uint32_t* num_blocks);
 
+/* The argument checks of slrhip_modulate on a descriptor (slr_amd/csrc/render_plan.h, modulateRefusal), evaluated on the HOST with the
+ * function the entry point calls: SLRHIP_OK if the call would go ahead, else SLRHIP_ERR_INVALID_ARGUMENT with the reason in
+ * slrhip_last_error_string.  The pointers are only compared, never followed.  No GPU is touched.                                  */
+int slrhip_debug_modulate_check(const slrhip_modulate_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,19 @@ class TonemapDesc(C.Structure):
                 ("color", C.c_void_p), ("output", C.c_void_p), ("output_bytes", C.c_size_t), ("scale", C.c_float), ("reserved", C.c_uint32)]
 
 
+# slrhip_modulate's operations (SLRHIP_MODULATE_*)
+MODULATE_DIVIDE, MODULATE_MULTIPLY = 0, 1
+# Context.modulate's default floor: the smallest mean albedo a pixel is divided by (a black texel, a NaN)
+MODULATE_FLOOR = 1e-3
+
+
+class ModulateDesc(C.Structure):
+    """slrhip_modulate_desc: every pointer is a DEVICE pointer (an integer address, or None)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_uint32), ("op", C.c_uint32),
+                ("color", C.c_void_p), ("variance", C.c_void_p), ("albedo", C.c_void_p), ("output", C.c_void_p), ("output_variance", C.c_void_p),
+                ("albedo_passes", C.c_uint32), ("floor", C.c_float), ("reserved", C.c_uint32)]
+
+
 # Context.denoise's default sigma_distance: the accepted relative change of the camera distance per pixel of tap offset
 # (DESIGN.md records how it was picked on the Cornell scenes)
 DENOISE_SIGMA_DISTANCE = 0.1

@@ -18,6 +18,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_statistics_begin", "slrhip_resolve_statistics", "slrhip_read_statistics", "slrhip_statistics_summary", "slrhip_render_until", "slrhip_sample_luminance",
            "slrhip_render_adaptive", "slrhip_resolve_framebuffer_mean", "slrhip_read_framebuffer_mean", "slrhip_adaptive_active", "slrhip_debug_adaptive_blocks",
            "slrhip_denoise", "slrhip_denoise_scratch_bytes", "slrhip_tonemap", "slrhip_tonemap_bytes",
+           "slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate", "slrhip_debug_modulate_check",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -98,6 +99,14 @@ def load_library():
         lib.slrhip_tonemap.argtypes = [C.c_void_p, C.POINTER(abi.TonemapDesc), C.c_void_p]
         lib.slrhip_tonemap_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         lib.slrhip_tonemap_bytes.restype = C.c_size_t
+    # (and one from before the albedo buffer lacks these five)
+    for name, argtypes in (("slrhip_render_albedo", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_resolve_albedo", [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p]),
+                           ("slrhip_read_albedo", [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+                           ("slrhip_modulate", [C.c_void_p, C.POINTER(abi.ModulateDesc), C.c_void_p]),
+                           ("slrhip_debug_modulate_check", [C.POINTER(abi.ModulateDesc)])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
@@ -318,6 +327,74 @@ class Context:
         _check(self.lib, self.lib.slrhip_read_features(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_features")
         return out if k == 3 else out[:, :, 0]
 
+    # ---- the albedo buffer (slrhip_render_albedo / slrhip_resolve_albedo / slrhip_read_albedo) ----
+    def render_albedo(self, spp, spp_begin=0, stream=None):
+        """Albedo passes [spp_begin, spp_begin + spp) of every pixel of the shard (slrhip_render_albedo): the base colour of the
+        camera ray's first hit, a miss counting as one.  Ordered on `stream`, returns at once."""
+        _check(self.lib, self.lib.slrhip_render_albedo(self.handle, spp_begin, spp, self._stream_handle(stream)), "slrhip_render_albedo")
+
+    def albedo_into(self, device_ptr, num_floats, stream=None):
+        """The albedo SUMS into device memory at `device_ptr` ([height, width, components] float32; slrhip_resolve_albedo), ordered
+        on `stream`; returns the number of passes accumulated since render_begin (the divisor of the mean)."""
+        passes = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_resolve_albedo(self.handle, device_ptr, num_floats, C.byref(passes), self._stream_handle(stream)),
+               "slrhip_resolve_albedo")
+        return passes.value
+
+    def albedo(self):
+        """(sums [height, width, components] float32, passes): the per-pixel albedo sums in pass order, zeros outside the shard, and the
+        passes accumulated; sums / passes is the mean albedo.  Synchronises, and raises if the feature error word is set."""
+        h, w = self.settings.image_height, self.settings.image_width
+        out = np.empty((h, w, self.components), np.float32)
+        passes = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_read_albedo(self.handle, out.ctypes.data, out.size, C.byref(passes)), "slrhip_read_albedo")
+        return out, passes.value
+
+    # ---- albedo demodulation (slrhip_modulate): a pure function of device buffers ----
+    def modulate_into(self, width, height, components, op, color, albedo, albedo_passes, output, variance=None, output_variance=None,
+                      floor=abi.MODULATE_FLOOR, stream=None):
+        """slrhip_modulate over DEVICE pointers (integer addresses; None = not given): color [H][W][C] divided by (abi.MODULATE_DIVIDE)
+        or multiplied with (abi.MODULATE_MULTIPLY) max(albedo / albedo_passes, floor) -> output, which may be `color` itself; the
+        variance of the luminance [H][W] is scaled by the square of the albedo's luminance.  Ordered on `stream`, returns at once."""
+        d = abi.ModulateDesc(width, height, components, op, color, variance, albedo, output, output_variance, albedo_passes, floor, 0)
+        _check(self.lib, self.lib.slrhip_modulate(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_modulate")
+
+    def modulate(self, color, albedo, passes, op, variance=None, floor=abi.MODULATE_FLOOR):
+        """slrhip_modulate over HOST arrays: color and albedo sums [H, W, 3 or 16], variance [H, W] or None.  The arrays are copied to
+        the device and the result back: the frame, or (frame, variance) when a variance is given.  Synchronises."""
+        color, albedo = np.ascontiguousarray(color, np.float32), np.ascontiguousarray(albedo, np.float32)
+        if color.ndim != 3 or albedo.shape != color.shape:
+            raise ValueError("color and albedo: two [height, width, components] arrays of one shape expected")
+        h, w, comps = color.shape
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, np.float32)
+            if variance.shape != (h, w):
+                raise ValueError("variance: shape %r expected" % ((h, w),))
+        hip = _hip_runtime()
+        ptrs = []
+
+        def put(a):
+            p = C.c_void_p()
+            _hip_check(hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
+            ptrs.append(p.value)
+            _hip_check(hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
+            return p.value
+        try:
+            pc, pa = put(color), put(albedo)
+            pv = put(variance) if variance is not None else None
+            self.modulate_into(w, h, comps, op, pc, pa, passes, pc, pv, pv, floor)      # in place
+            self.synchronize()
+            out = np.empty_like(color)
+            _hip_check(hip.hipMemcpy(out.ctypes.data, pc, out.nbytes, 2), "hipMemcpy")
+            if variance is None:
+                return out
+            out_v = np.empty_like(variance)
+            _hip_check(hip.hipMemcpy(out_v.ctypes.data, pv, out_v.nbytes, 2), "hipMemcpy")
+            return out, out_v
+        finally:
+            for p in ptrs:
+                hip.hipFree(p)
+
     def camera_rays(self, pass_, device=False, stream=None):
         """The camera rays of sample `pass_` of every pixel of the shard (slrhip_camera_rays): (rows, pixel_xy), rows [n, 8] float32
         in the format intersect_rays takes, pixel_xy [n] = x | y << 16.  Numpy arrays by default (the call synchronises);
@@ -429,10 +506,12 @@ class Context:
                             sigma_luminance, sigma_distance, normal_power_log2, 0)
         _check(self.lib, self.lib.slrhip_denoise(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_denoise")
 
-    def _denoise_staged(self, shape, fill, params, want_variance, image=None):
+    def _denoise_staged(self, shape, fill, params, want_variance, image=None, demodulate=None):
         """hipMalloc the buffers of a denoise call, let `fill(name, device_ptr)` fill the inputs (a name it returns False for is
         passed as NULL), run the filter on the null stream and copy the result back; with image = (scale, format) the result stays
-        on the device, is tone-mapped there (slrhip_tonemap) and only the 8-bit image comes back."""
+        on the device, is tone-mapped there (slrhip_tonemap) and only the 8-bit image comes back.  demodulate = floor: the albedo is
+        resolved on the device as well (albedo_into), colour and variance are divided by it before the filter and its outputs
+        multiplied with it afterwards (slrhip_modulate, in place)."""
         h, w, comps = shape
         sizes = {"color": h * w * comps, "variance": h * w, "normal": h * w * 3, "distance": h * w, "coverage": h * w}
         hip = _hip_runtime()
@@ -448,9 +527,19 @@ class Context:
             given = {name: malloc(name, n) for name, n in sizes.items() if fill(name, None)}
             for name, p in given.items():
                 fill(name, p)
+            if demodulate is not None:
+                if want_variance and "variance" not in given:
+                    raise ValueError("demodulate with want_variance needs a variance input: the filtered variance could not be multiplied back")
+                albedo = malloc("albedo", out.size)
+                passes = self.albedo_into(albedo, out.size)
+                self.modulate_into(w, h, comps, abi.MODULATE_DIVIDE, given["color"], albedo, passes, given["color"], given.get("variance"),
+                                   given.get("variance"), demodulate)
             self.denoise_into(w, h, comps, color=given["color"], output=malloc("output", out.size),
                               output_variance=malloc("output_variance", out_v.size) if want_variance else None,
                               **{k: given.get(k) for k in ("variance", "normal", "distance", "coverage")}, **params)
+            if demodulate is not None:
+                pv = ptrs.get("output_variance") if given.get("variance") else None
+                self.modulate_into(w, h, comps, abi.MODULATE_MULTIPLY, ptrs["output"], albedo, passes, ptrs["output"], pv, pv, demodulate)
             if image is not None:
                 return self._tonemap_staged(ptrs["output"], w, h, comps, *image)
             self.synchronize()
@@ -485,13 +574,15 @@ class Context:
         params = dict(iterations=iterations, sigma_luminance=sigma_luminance, sigma_distance=sigma_distance, normal_power_log2=normal_power_log2)
         return self._denoise_staged(shape, fill, params, want_variance)
 
-    def denoised(self, want_variance=False, image=None, **params):
+    def denoised(self, want_variance=False, image=None, demodulate=False, floor=abi.MODULATE_FLOOR, **params):
         """The current render's frame, denoised: after a render with statistics on and render_features(abi.FEATURE_SHADING_NORMAL |
         abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE, ...).  The mean frame, the variance of the mean and the three guides are
         resolved ON THE DEVICE and filtered there; only the result comes back.  **params: iterations, sigma_luminance,
         sigma_distance, normal_power_log2 of denoise().  A whole-image shard only: the taps of a pixel reach into other shards'
         tiles (a multi-GPU host reduces the five buffers onto one rank and denoises there).  image = (scale, abi.IMAGE_*): the
-        filtered frame is tone-mapped on the device as well and the 8-bit image (as frame_image returns it) comes back in its place."""
+        filtered frame is tone-mapped on the device as well and the 8-bit image (as frame_image returns it) comes back in its place.
+        demodulate=True (after render_albedo): the frame and its variance are divided by the mean first-hit albedo (never less than
+        `floor`) before the filter and the results multiplied back, so that texture detail the guides do not see passes the filter."""
         if self.settings is None:
             raise SlrHipError("denoised: call render_begin first")
         if tuple(self.shard) != (0, 1):
@@ -509,7 +600,7 @@ class Context:
                 resolve[name](ptr, floats[name])
             return True
         params.setdefault("iterations", 5)
-        return self._denoise_staged((h, w, self.components), fill, params, want_variance, image)
+        return self._denoise_staged((h, w, self.components), fill, params, want_variance, image, floor if demodulate else None)
 
     # ---- image export on the device (slrhip_tonemap): a pure function of device buffers ----
     def tonemap_into(self, width, height, components, color_ptr, output_ptr, output_bytes, scale, format, stream=None):

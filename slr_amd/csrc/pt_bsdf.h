@@ -677,4 +677,26 @@ SLR_DEV S bsdfEvaluate(const Mat<S>& m, uint32_t type, V3 dirOut, V3 gNorm, V3 d
     return bsdfEvaluateOnly<S, MF>(m, type, dirOut, gNorm, dir, wl);
 }
 
+// BSDF::getBaseColor(DirectionType::All) of a single lobe (Core/directional_distribution_functions.h:293-297: `matches` is true
+// for every lobe with All, on either side, so an InverseBSDF has its base's colour, basic_BSDFs.cpp:205-207).  m: the record with
+// its textures and its `scale` applied.  The albedo of slrhip_render_albedo; bsdfBaseColorMulti (pt_bsdf_multi.h) folds a MultiBSDF.
+template <class S>
+SLR_DEV S bsdfBaseColor(const Mat<S>& m) {
+    switch (m.type) {
+    case SLRHIP_MATERIAL_MATTE:                  // LambertianBRDF basic_BSDFs.cpp:55, OrenNayerBRDF.cpp:71: m_R
+    case SLRHIP_MATERIAL_METAL:                  // SpecularBRDF basic_BSDFs.cpp:89: m_coeffR
+    case SLRHIP_MATERIAL_GLASS:                  // SpecularBSDF basic_BSDFs.cpp:167: m_coeff
+    case SLRHIP_MATERIAL_WARD:                   // ModifiedWardDurBRDF.cpp:84: m_R
+        return m.a;
+    case SLRHIP_MATERIAL_MICROFACET_METAL:       // MicrofacetBSDF.cpp:108: m_F.evaluate(1.0f)
+        return fresnelConductor(m.b, m.c, 1.0f);
+    case SLRHIP_MATERIAL_MICROFACET_GLASS:       // MicrofacetBSDF.cpp:313: One
+        return S(1.0f);
+    case SLRHIP_MATERIAL_ASHIKHMIN:              // AshikhminShirleyBRDF.cpp:167: m_Rs + (One - m_Rs) * m_Rd
+        return m.a + (S(1.0f) - m.a) * m.b;
+    default:
+        return S();
+    }
+}
+
 } // namespace slrhip

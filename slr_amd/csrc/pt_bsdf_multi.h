@@ -113,6 +113,22 @@ SLR_DEV void applyScale(Mat<S>& c, float scale) {
     }
 }
 
+// MultiBSDF::getBaseColorInternal (MultiBSDF.cpp:210-218) with flags = All: the components in order, the first whose base colour
+// has a non-zero component; zeros if there is none.  A nested MultiBSDF answers the same way, so over the flattened tree it is the
+// first such LEAF in buildMultiTree's order.  `load(i)`: material record i with its textures applied, as for MultiBSDF below.
+template <class S, class Load>
+SLR_DEV S bsdfBaseColorMulti(const MultiTree& tr, const Load& load) {
+    S color;
+#pragma unroll 1
+    for (uint32_t i = 0; i < tr.numLeaves; ++i) {
+        Mat<S> c = load(sel4(tr.leafMat, i));
+        applyScale(c, sel4(tr.leafScale, i));
+        color = bsdfBaseColor(c);
+        if (!color.isZero()) break;              // hasNonZero
+    }
+    return color;
+}
+
 // weightInternal of each lobe under BSDF::weight (DDF.h:280-289; non-adjoint: no correction)
 template <class S>
 SLR_DEV float bsdfWeight(const Mat<S>& m, uint32_t type, uint32_t flags, V3 dirOut, uint32_t wl) {

@@ -286,7 +286,17 @@ struct FeatureSums {
 void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream);
 void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays, uint32_t* pixelXY, hipStream_t stream);
 void launchFeatureResolve(const FeatureParams& fp, const FeatureSums& sums, uint32_t channel, void* dst, hipStream_t stream);
+// the traversal half of launchFeatures alone: the window's records, and b2 when fp.b2 is given
+void launchFeatureTrace(const DevScene& sc, const FeatureParams& fp, int numCUs, hipStream_t stream);
 
+// The albedo feature buffer (slrhip_render_albedo; pt_albedo.hip): launchFeatureTrace fills the record window, launchAlbedoFold adds
+// the base colour of each hit (a miss: one) to the pixel in pass order.  sums: `components` float planes of numPixels floats each.
+// fp.b2 must be given when the scene has textures (the texture coordinate needs both barycentrics).
+void launchAlbedoFold(const DevScene& sc, const FeatureParams& fp, bool spectral, float* sums, hipStream_t stream);
+// the sums as [height][width][components] (dst cleared by the caller: pixels outside the shard stay 0)
+void launchAlbedoResolve(const FeatureParams& fp, uint32_t components, const float* sums, float* dst, hipStream_t stream);
+// slrhip_modulate (pt_albedo.hip): one launch on `stream`; the descriptor has passed modulateRefusal (render_plan.h)
+void launchModulate(const slrhip_modulate_desc& d, hipStream_t stream);
 
 // Per-pixel noise statistics (slrhip_statistics_begin; pt_stats.hip).  One record per pixel of the shard, updated by k_fold in
 // pass order: {mean, M2, n (uint32 bits), max} of the samples' luminance (float32 Welford).

@@ -952,7 +952,8 @@ __global__ __launch_bounds__(256) void k_feature_fold(DevScene sc, FeatureParams
     sums.geometric[pix] = g; sums.shading[pix] = s; sums.tangent[pix] = t;
 }
 
-void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream) {
+// the traversal of a window alone: the records (and b2, if fp.b2 is given) of its samples; shared with the albedo pass (pt_albedo.hip)
+void launchFeatureTrace(const DevScene& sc, const FeatureParams& fp, int numCUs, hipStream_t stream) {
     const bool quant = sc.nodesQ != nullptr && !sc.instances;
     const uint32_t n = fp.numPixels * fp.numPasses;
     const uint32_t chunks = (n + kSub * 64 - 1) / (kSub * 64);
@@ -961,6 +962,10 @@ void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSu
     if (nc == 15) launchFeaturesWsT<15>(sc, fp, n, blocks, stream);
     else if (nc == 7) launchFeaturesWsT<7>(sc, fp, n, blocks, stream);
     else launchFeaturesWsT<3>(sc, fp, n, blocks, stream);
+}
+
+void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream) {
+    launchFeatureTrace(sc, fp, numCUs, stream);
     hipLaunchKernelGGL(k_feature_fold, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, sc, fp, sums, idsPass);
 }
 

@@ -183,6 +183,32 @@ const char* tonemapRefusal(const slrhip_tonemap_desc& d) {
     return nullptr;
 }
 
+const char* modulateRefusal(const slrhip_modulate_desc& d) {
+    if (d.reserved != 0) return "reserved must be 0";
+    if (d.components != 3 && d.components != 16) return "components must be 3 or 16";
+    if (d.op != SLRHIP_MODULATE_DIVIDE && d.op != SLRHIP_MODULATE_MULTIPLY) return "unknown op";
+    const uint64_t pixels = (uint64_t)d.width * d.height;
+    if (pixels == 0 || pixels >= (1ull << 31)) return "width and height must be >= 1 and width * height < 2^31";
+    if (d.albedo_passes == 0) return "albedo_passes must be >= 1";
+    if (!(d.floor > 0.0f) || !(d.floor <= 3.402823466e+38f)) return "floor must be finite and > 0";
+    if (!d.color || !d.albedo || !d.output) return "null color, albedo or output";
+    if (((uintptr_t)d.color | (uintptr_t)d.variance | (uintptr_t)d.albedo | (uintptr_t)d.output | (uintptr_t)d.output_variance) & 3u)
+        return "a misaligned pointer (4 bytes)";
+    if (d.output_variance && !d.variance) return "output_variance needs variance";
+    const size_t plane = (size_t)pixels * sizeof(float), frame = plane * d.components;
+    // an output may be exactly its own input (in place); every other overlap of an output with a buffer of the call is refused
+    if (d.output != d.color && rangesOverlap(d.output, frame, d.color, frame)) return "output overlaps color without being equal to it";
+    if (rangesOverlap(d.output, frame, d.albedo, frame)) return "output overlaps albedo";
+    if (d.variance && rangesOverlap(d.output, frame, d.variance, plane)) return "output overlaps variance";
+    if (d.output_variance) {
+        if (d.output_variance != d.variance && rangesOverlap(d.output_variance, plane, d.variance, plane)) return "output_variance overlaps variance without being equal to it";
+        if (rangesOverlap(d.output_variance, plane, d.color, frame)) return "output_variance overlaps color";
+        if (rangesOverlap(d.output_variance, plane, d.albedo, frame)) return "output_variance overlaps albedo";
+        if (rangesOverlap(d.output_variance, plane, d.output, frame)) return "output_variance overlaps output";
+    }
+    return nullptr;
+}
+
 } // namespace slrhip
 
 extern "C" size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format) {

@@ -80,5 +80,7 @@ bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes);
 size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format);
 // The argument checks of slrhip_tonemap on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
 const char* tonemapRefusal(const slrhip_tonemap_desc& d);
+// The argument checks of slrhip_modulate on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
+const char* modulateRefusal(const slrhip_modulate_desc& d);
 
 } // namespace slrhip

@@ -163,6 +163,12 @@ struct slrhip_ctx {
     uint32_t featChannels = 0;                    // the channel set of the feature calls since render_begin (0: none yet)
     uint32_t featWindow = 0;                      // passes per launch (the record window)
     uint64_t featPassEnd = 0;                     // 1 + the highest pass rendered since render_begin (whose ids the pixels hold)
+    bool featErrorReady = false;                  // featError allocated and cleared since render_begin (by the first feature or albedo call)
+    // the albedo buffer (slrhip_render_albedo): the sums are allocated by the first albedo call after render_begin; the record window is the feature pass's
+    DevArray<float> albSums;                      // `components` planes of numPixels floats
+    bool albReady = false;                        // sums allocated and cleared since render_begin
+    uint32_t albWindow = 0;                       // passes per launch
+    uint64_t albPasses = 0;                       // passes accumulated since render_begin
     // per-pixel noise statistics (slrhip_statistics_begin): allocated by the first enabling call, kept for later renders
     DevArray<float4> statRecords;                 // {mean, M2, n, max} per pixel of the shard, updated by k_fold
     DevArray<StatsTotals> statPartials, statTotals;      // the summary's first-stage partials and its result
@@ -681,6 +687,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->iterations = 0;
     ctx->firstRenderCall = true;
     ctx->featReady = false; ctx->featChannels = 0; ctx->featPassEnd = 0;      // the feature accumulation restarts (its arrays are kept for reuse)
+    ctx->featErrorReady = false; ctx->albReady = false; ctx->albPasses = 0;   // ... and the albedo accumulation and the error word they share
     ctx->statsOn = false; ctx->statsClear = true;                             // statistics are per render (slrhip_statistics_begin); the records are kept, stale
     ctx->activePixels = plan.numPixels; ctx->activeList = -1;                 // every pixel is active again (slrhip_render_adaptive)
     ctx->haveRender = true;
@@ -894,6 +901,15 @@ static FeatureParams featureParams(const slrhip_ctx* ctx, uint32_t channels, uin
     fp.imageWidth = rp.imageWidth; fp.imageHeight = rp.imageHeight;
     return fp;
 }
+// The error word the feature and the albedo passes share: allocated and cleared, in stream order, by whichever runs first after a
+// slrhip_render_begin; sticky until the next one.
+static int clearFeatureError(slrhip_ctx* ctx, hipStream_t s) {
+    if (ctx->featErrorReady) return SLRHIP_OK;
+    HIP_TRY(ctx->featError.alloc(1));
+    HIP_TRY(hipMemsetAsync(ctx->featError.ptr, 0, sizeof(uint32_t), s));
+    ctx->featErrorReady = true;
+    return SLRHIP_OK;
+}
 static FeatureSums featureSums(const slrhip_ctx* ctx) { return FeatureSums{ctx->featGeometric.ptr, ctx->featShading.ptr, ctx->featTangent.ptr, ctx->featIds.ptr}; }
 
 int slrhip_render_features(slrhip_ctx* ctx, uint32_t channels, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
@@ -919,14 +935,14 @@ int slrhip_render_features(slrhip_ctx* ctx, uint32_t channels, uint32_t sppBegin
         const uint64_t perPass = (uint64_t)pixels * (sizeof(float4) + (wantB2 ? sizeof(float) : 0));
         ctx->featWindow = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>({kFeatureRecordBytes / perPass, 0x7FFFFFFFull / pixels, 64u}));
         HIP_TRY(ctx->featGeometric.alloc(pixels)); HIP_TRY(ctx->featShading.alloc(pixels)); HIP_TRY(ctx->featTangent.alloc(pixels));
-        HIP_TRY(ctx->featIds.alloc(pixels)); HIP_TRY(ctx->featError.alloc(1));
+        HIP_TRY(ctx->featIds.alloc(pixels));
         HIP_TRY(ctx->featRecords.alloc(pixels * ctx->featWindow));
         if (wantB2) HIP_TRY(ctx->featB2.alloc(pixels * ctx->featWindow));
         HIP_TRY(hipMemsetAsync(ctx->featGeometric.ptr, 0, pixels * sizeof(float4), s));
         HIP_TRY(hipMemsetAsync(ctx->featShading.ptr, 0, pixels * sizeof(float4), s));
         HIP_TRY(hipMemsetAsync(ctx->featTangent.ptr, 0, pixels * sizeof(float4), s));
         HIP_TRY(hipMemsetAsync(ctx->featIds.ptr, 0xFF, pixels * sizeof(uint4), s));
-        HIP_TRY(hipMemsetAsync(ctx->featError.ptr, 0, sizeof(uint32_t), s));
+        if (const int rc = clearFeatureError(ctx, s)) return rc;
         ctx->featReady = true;
     }
     const FeatureSums sums = featureSums(ctx);
@@ -998,11 +1014,85 @@ int slrhip_camera_rays(slrhip_ctx* ctx, uint32_t pass, slrhip_ray* rays, uint32_
 int slrhip_features_status(slrhip_ctx* ctx, uint32_t* bits, void* stream) {
     if (!ctx || !bits) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_features_status: null argument");
     *bits = 0;
-    if (!ctx->haveRender || !ctx->featReady) return SLRHIP_OK;          // no feature pass can have run
+    if (!ctx->haveRender || !ctx->featErrorReady) return SLRHIP_OK;     // no feature or albedo pass can have run
     HIP_TRY(hipSetDevice(ctx->device));
     const hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(bits, ctx->featError.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return SLRHIP_OK;
+}
+
+// ---- the albedo buffer (slrhip_render_albedo / slrhip_resolve_albedo / slrhip_read_albedo) -----------------------------------------
+// The traversal and the record window are the feature pass's; the fold and the sums are pt_albedo.hip's.
+int slrhip_render_albedo(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_albedo: null context");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_render_albedo: call slrhip_render_begin first");
+    if ((uint64_t)sppBegin + sppCount > 0xFFFFFFFFull) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_albedo: pass range beyond 2^32");
+    if (sppCount == 0) return SLRHIP_OK;
+    const RenderParams& rp = ctx->params;
+    if (rp.numPixels == 0) { ctx->albPasses += sppCount; return SLRHIP_OK; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    const bool wantB2 = ctx->scene.numTextures != 0;                 // the texture coordinate needs both barycentrics
+    const uint32_t components = rp.spectral ? SLRHIP_SPECTRAL_COMPONENTS : SLRHIP_RGB_COMPONENTS;
+    if (!ctx->albReady) {
+        // the first albedo call since render_begin: the sums (cleared in stream order) and room in the record window, sized by the
+        // shard and the scene alone, so that no later call allocates whatever its pass count.  The window's arrays only ever grow:
+        // a feature call that sized them for more passes keeps its room.  Growing MOVES them (DevArray::alloc frees and allocates),
+        // here and in the first feature call alike: graphs are captured after both first calls (include/slrhip.h).
+        const size_t pixels = rp.numPixels;
+        const uint64_t perPass = (uint64_t)pixels * (sizeof(float4) + (wantB2 ? sizeof(float) : 0));
+        ctx->albWindow = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>({kFeatureRecordBytes / perPass, 0x7FFFFFFFull / pixels, 64u}));
+        HIP_TRY(ctx->albSums.alloc(pixels * components));
+        HIP_TRY(ctx->featRecords.alloc(std::max(ctx->featRecords.capacity, pixels * ctx->albWindow)));
+        if (wantB2) HIP_TRY(ctx->featB2.alloc(std::max(ctx->featB2.capacity, pixels * ctx->albWindow)));
+        HIP_TRY(hipMemsetAsync(ctx->albSums.ptr, 0, pixels * components * sizeof(float), s));
+        if (const int rc = clearFeatureError(ctx, s)) return rc;
+        ctx->albReady = true;
+    }
+    for (uint32_t done = 0; done < sppCount; done += ctx->albWindow) {
+        const uint32_t n = std::min(ctx->albWindow, sppCount - done);
+        FeatureParams fp = featureParams(ctx, 0, sppBegin + done, n);
+        fp.b2 = wantB2 ? ctx->featB2.ptr : nullptr;
+        launchFeatureTrace(ctx->scene, fp, ctx->numCUs, s);
+        launchAlbedoFold(ctx->scene, fp, rp.spectral != 0, ctx->albSums.ptr, s);
+    }
+    ctx->albPasses += sppCount;
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_albedo(slrhip_ctx* ctx, float* deviceDst, size_t numFloats, uint32_t* passes, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_albedo: null context");
+    if (!deviceDst || ((uintptr_t)deviceDst & 3u)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_albedo: null or misaligned destination (4 bytes)");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_resolve_albedo: call slrhip_render_begin first");
+    const RenderParams& rp = ctx->params;
+    const size_t need = frameFloats(rp);
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_albedo: destination too small");
+    if (passes) *passes = (uint32_t)std::min<uint64_t>(ctx->albPasses, 0xFFFFFFFFull);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    HIP_TRY(hipMemsetAsync(deviceDst, 0, need * sizeof(float), s));
+    if (rp.numPixels && ctx->albReady)
+        launchAlbedoResolve(featureParams(ctx, 0, 0, 0), rp.spectral ? SLRHIP_SPECTRAL_COMPONENTS : SLRHIP_RGB_COMPONENTS, ctx->albSums.ptr, deviceDst, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_albedo(slrhip_ctx* ctx, float* hostDst, size_t numFloats, uint32_t* passes) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_albedo: null context");
+    if (!hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_albedo: null destination");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_read_albedo: call slrhip_render_begin first");
+    const size_t need = frameFloats(ctx->params);
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_albedo: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->resolveScratch.alloc(need));
+    HIP_TRY(hipDeviceSynchronize());                   // albedo passes queued on any stream of the caller's
+    if (const int rc = slrhip_resolve_albedo(ctx, ctx->resolveScratch.ptr, need, passes, nullptr)) return rc;
+    uint32_t bits = 0;
+    if (const int rc = slrhip_features_status(ctx, &bits, nullptr)) return rc;
+    if (bits) return fail(SLRHIP_ERR_HIP, "slrhip_read_albedo: the feature error word is set (a traversal gave up): " + std::to_string(bits));
+    HIP_TRY(hipMemcpy(hostDst, ctx->resolveScratch.ptr, need * sizeof(float), hipMemcpyDeviceToHost));
     return SLRHIP_OK;
 }
 
@@ -1265,6 +1355,23 @@ int slrhip_tonemap(slrhip_ctx* ctx, const slrhip_tonemap_desc* d, void* streamPt
     HIP_TRY(hipSetDevice(ctx->device));
     launchTonemap(*d, (hipStream_t)streamPtr);
     HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+// Albedo demodulation: the argument checks (render_plan.cpp), one launch (pt_albedo.hip).  It reads nothing of the render state.
+int slrhip_modulate(slrhip_ctx* ctx, const slrhip_modulate_desc* d, void* streamPtr) {
+    if (!ctx || !d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_modulate: null argument");
+    if (const char* what = modulateRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_modulate: ") + what);
+    HIP_TRY(hipSetDevice(ctx->device));
+    launchModulate(*d, (hipStream_t)streamPtr);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the argument checks of slrhip_modulate alone.
+int slrhip_debug_modulate_check(const slrhip_modulate_desc* d) {
+    if (!d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_modulate: null argument");
+    if (const char* what = modulateRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_modulate: ") + what);
     return SLRHIP_OK;
 }
 

@@ -18,6 +18,9 @@ pixels x sample limit.
 `--denoise [ITERATIONS]` (default 5, 1 .. 8) also filters the final frame on the device (Context.denoised: the mean frame guided by
 the variance of the mean, the shading normals and the camera distance, which are rendered alongside) and writes
 "<name>_denoised.bmp" next to the last image.
+`--demodulate` (with `--denoise`) writes "<name>_denoised.bmp" from the albedo-demodulated pipeline: the first-hit albedo is rendered
+alongside (Context.render_albedo), the frame is divided by it before the filter and multiplied back afterwards, so that texture
+detail passes the filter.  `--albedo FILE.npy` writes the mean first-hit albedo [height, width, components].
 `--device-tonemap` tone-maps every BMP above on the device (Context.frame_image, slrhip_tonemap): the frame is resolved into device
 memory (or is the denoiser's output there) and only the 8-bit rows are copied back, in place of a read-back of the floats and the
 host loop of slrhip_tonemap_bgr8.
@@ -119,11 +122,12 @@ def render_adaptively(ctx, st, args, spp, sensitivity):
 DENOISE_CHANNELS = abi.FEATURE_SHADING_NORMAL | abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE
 
 
-def write_denoised(ctx, st, iterations, sensitivity, path, device_tonemap=False):
+def write_denoised(ctx, st, iterations, sensitivity, path, device_tonemap=False, demodulate=False):
     """--denoise: the filtered MEAN frame (scale brightness x sensitivity, as --adaptive writes its image) to `path`."""
     scale = float(np.float32(st.brightness) * np.float32(sensitivity))
-    write_image(ctx, st, scale, path, "denoised", device_tonemap, iterations=iterations)
-    print("denoised (%u iterations): %s" % (iterations, os.path.basename(path)), flush=True)
+    extra = dict(demodulate=True) if demodulate else {}
+    write_image(ctx, st, scale, path, "denoised", device_tonemap, iterations=iterations, **extra)
+    print("denoised (%u iterations%s): %s" % (iterations, ", albedo-demodulated" if demodulate else "", os.path.basename(path)), flush=True)
 
 
 def build_parser():
@@ -148,6 +152,9 @@ def build_parser():
     ap.add_argument("--spp-min", type=int, default=16, metavar="N", help="with --adaptive: passes every pixel gets before the first check (>= 2)")
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS",
                     help="also write <name>_denoised.bmp: the final frame filtered on the device (a-trous iterations, 1 .. 8; default 5)")
+    ap.add_argument("--demodulate", action="store_true",
+                    help="with --denoise: divide the frame by the first-hit albedo before the filter and multiply it back afterwards")
+    ap.add_argument("--albedo", default=None, metavar="FILE.npy", help="write the mean first-hit albedo [height, width, components]")
     ap.add_argument("--device-tonemap", action="store_true",
                     help="tone-map every BMP on the device and read back only the 8-bit image, not the float frame")
     return ap
@@ -166,6 +173,8 @@ def main(argv=None):
 
     if args.denoise is not None and not 1 <= args.denoise <= 8:
         ap.error("--denoise takes 1 .. 8 iterations")
+    if args.demodulate and args.denoise is None:
+        ap.error("--demodulate goes with --denoise")
 
     try:
         scene, settings, renderer = scene_language.load_scene(args.scene)
@@ -215,8 +224,15 @@ def main(argv=None):
         write_features(ctx, spp, feature_dir, feature_channels | (DENOISE_CHANNELS if args.denoise is not None else 0))
     elif args.denoise is not None:
         ctx.render_features(DENOISE_CHANNELS, spp)
+    if args.demodulate or args.albedo:
+        ctx.render_albedo(spp)
+    if args.albedo:
+        sums, passes = ctx.albedo()
+        np.save(args.albedo, sums / np.float32(passes))
+        print("albedo (%u passes): %s" % (passes, os.path.basename(args.albedo)), flush=True)
     if args.denoise is not None:
-        write_denoised(ctx, st, args.denoise, sensitivity, os.path.join(args.out, os.path.splitext(name)[0] + "_denoised.bmp"), args.device_tonemap)
+        write_denoised(ctx, st, args.denoise, sensitivity, os.path.join(args.out, os.path.splitext(name)[0] + "_denoised.bmp"), args.device_tonemap,
+                       args.demodulate)
     ctx.close()
     return 0
 

@@ -1,0 +1,950 @@
+"""The albedo feature buffer (slrhip_render_albedo / slrhip_resolve_albedo / slrhip_read_albedo) and albedo demodulation
+(slrhip_modulate, Context.denoised(demodulate=True)), against include/slrhip.h's definitions.
+
+The expected colours are read from the scene's own material, spectrum and texture records by the table of the header (RGB mode,
+compared bit for bit through uint32 views) or evaluated by the compiled reference's spectrum code (spectral mode, the project's
+standing device-against-CPU tolerance rtol 2e-6 / atol 1e-9 of test_gpu_parity.py).  Per-sample values come from rendering one pass
+at a time; the material of a sample's hit is the IDS channel of the feature pass of the same (pixel, pass).  Every test calls entry
+points that the parent commit does not have."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import load_golden, scene_from_golden
+from slr_amd import abi, binding, host, scenes
+from test_denoise import luminance, restate
+from test_features import SCENES, counter_fields, one_pass, per_pixel, settings
+from test_ray_queries import triangles_of
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MISS = abi.MISS
+INVALID, NO_SCENE = 1, 4
+GUIDES = abi.FEATURE_SHADING_NORMAL | abi.FEATURE_DISTANCE | abi.FEATURE_COVERAGE
+TREES = {"host": 0, "device": abi.FLAG_BVH_DEVICE_BUILD, "splits": abi.FLAG_BVH_SPATIAL_SPLITS}
+
+
+def u32(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def assert_same_bits(got, want, what):
+    got, want = np.ascontiguousarray(got, F), np.ascontiguousarray(want, F)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = u32(got) != u32(want)
+    assert not bad.any(), "%s: %d of %d floats differ; first %r vs %r" % (what, bad.sum(), bad.size, got[bad][:3], want[bad][:3])
+
+
+# ---- the restatements -------------------------------------------------------------------------------------------------------------
+def fresnel_conductor_at_one(eta, k):
+    """FresnelConductor::evaluate(1.0f) (Core/directional_distribution_functions.cpp:68-78) in float32, operation by operation;
+    the final `/ 2.0f` of a spectrum multiplies by the reciprocal 0.5f (RGBTypes.h:67), which is exact either way."""
+    eta, k = np.asarray(eta, F), np.asarray(k, F)
+    cos = F(1.0)
+    cos2 = cos * cos
+    two = (F(2.0) * eta) * cos
+    tmp_f = eta * eta + k * k
+    tmp = tmp_f * cos2
+    rparl2 = (tmp - two + F(1.0)) / (tmp + two + F(1.0))
+    rperp2 = (tmp_f - two + cos2) / (tmp_f + two + cos2)
+    out = (rparl2 + rperp2) * F(0.5)
+    assert out.dtype == F
+    return out
+
+
+def multi_leaves(sc, index, scale=None):
+    """The lobes of MULTI record `index` in buildMultiTree's order: (material index, scale); nested scales are float32 products."""
+    m = sc.materials[index]
+    leaves = []
+    for i, s in ((0, F(m["param"])), (1, F(m["param2"]))):
+        child = int(m["spectrum"][i])
+        s = s if scale is None else F(scale * s)
+        if sc.materials[child]["type"] == abi.MAT_MULTI:
+            leaves += multi_leaves(sc, child, s)
+        else:
+            leaves.append((child, s))
+    return leaves
+
+
+def base_color_rgb(sc, index, slot_value=None, scale=None):
+    """include/slrhip.h's table for material `index` in RGB mode, float32.  slot_value(material index, slot) -> the [3] value of a
+    TEXTURED spectrum slot (constant slots are read from the spectrum records)."""
+    m = sc.materials[index]
+    kind = int(m["type"])
+
+    def slot(k):
+        s = int(m["spectrum"][k])
+        return np.asarray(slot_value(index, k), F) if s <= -2 else sc.spectra["rgb"][s].astype(F)
+
+    def scaled(v):
+        return v if scale is None else F(scale) * v
+    if kind in (abi.MAT_MATTE, abi.MAT_METAL, abi.MAT_GLASS, abi.MAT_WARD):
+        return scaled(slot(0))
+    if kind == abi.MAT_MF_METAL:
+        return fresnel_conductor_at_one(slot(1), slot(2))
+    if kind == abi.MAT_MF_GLASS:
+        return np.ones(3, F)
+    if kind == abi.MAT_ASHIKHMIN:
+        rs, rd = scaled(slot(0)), scaled(slot(1))
+        return rs + (F(1.0) - rs) * rd
+    assert kind == abi.MAT_MULTI
+    color = np.zeros(3, F)
+    for child, s in multi_leaves(sc, index):
+        color = base_color_rgb(sc, child, slot_value, s)
+        if (color != 0).any():
+            break
+    return color
+
+
+def constant_table(sc):
+    """[materials, 3]: the base colour of every material of a scene without textured spectrum slots."""
+    return np.stack([base_color_rgb(sc, i) for i in range(len(sc.materials))])
+
+
+def np_modulate(color, albedo, passes, op, floor, variance=None):
+    """slrhip_modulate as include/slrhip.h states it, float32 step by step (np.fmax returns the other operand for a NaN)."""
+    color, albedo = np.asarray(color), np.asarray(albedo)
+    assert color.dtype == F and albedo.dtype == F
+    with np.errstate(all="ignore"):
+        a = np.fmax(albedo / F(passes), F(floor))
+        out = color * a if op == abi.MODULATE_MULTIPLY else color / a
+        assert a.dtype == F and out.dtype == F
+        if variance is None:
+            return out
+        ya = luminance(a)
+        y2 = ya * ya
+        out_v = variance * y2 if op == abi.MODULATE_MULTIPLY else variance / y2
+        assert out_v.dtype == F
+    return out, out_v
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ("slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate")
+
+
+def test_null_context_is_refused_without_a_device():
+    lib = binding.load_library()
+    for name in NEW_SYMBOLS:
+        assert name in binding.EXPORTS and hasattr(lib, name)
+    passes = C.c_uint32(0)
+    buf = np.zeros(16, F)
+    d = abi.ModulateDesc(2, 2, 3, abi.MODULATE_DIVIDE, 16, None, 4096, 8192, None, 1, 1e-3, 0)
+    calls = [lambda: lib.slrhip_render_albedo(None, 0, 1, None),
+             lambda: lib.slrhip_resolve_albedo(None, 16, 16, C.byref(passes), None),
+             lambda: lib.slrhip_read_albedo(None, buf.ctypes.data, buf.size, C.byref(passes)),
+             lambda: lib.slrhip_modulate(None, C.byref(d), None)]
+    for call in calls:
+        assert call() == INVALID
+        assert b"null" in lib.slrhip_last_error_string()
+    assert lib.slrhip_modulate(None, None, None) == INVALID
+
+
+def test_modulate_struct_layout():
+    """slrhip_modulate_desc under LP64: four uint32, five pointers, a uint32, a float, a uint32, padded to 72 bytes."""
+    offsets = {n: getattr(abi.ModulateDesc, n).offset for n, _ in abi.ModulateDesc._fields_}
+    assert offsets == dict(width=0, height=4, components=8, op=12, color=16, variance=24, albedo=32, output=40, output_variance=48,
+                           albedo_passes=56, floor=60, reserved=64)
+    assert C.sizeof(abi.ModulateDesc) == 72
+    text = open(os.path.join(ROOT, "include", "slrhip.h")).read()
+    body = text[text.index("typedef struct slrhip_modulate_desc {"):text.index("} slrhip_modulate_desc;")]
+    order = [body.index(" " + n) for n in ("width", "height", "components;", "op;", "color;", "variance;", "albedo;", "output;", "output_variance;",
+                                           "albedo_passes;", "floor;", "reserved;")]
+    assert order == sorted(order)
+    assert (abi.MODULATE_DIVIDE, abi.MODULATE_MULTIPLY) == (0, 1)
+    assert "#define SLRHIP_MODULATE_DIVIDE   0u" in text and "#define SLRHIP_MODULATE_MULTIPLY 1u" in text
+    assert abi.FEATURE_ALL == 63 and "#define SLRHIP_FEATURE_ALL             63u" in text       # the albedo is no feature channel
+
+
+def bad_descriptors(w, h, comps, color, variance, albedo, output, output_variance):
+    """Every refusal of include/slrhip.h's list, as overrides of a good descriptor over the given buffers (byte addresses; `output`
+    has room for a frame before and behind it inside the caller's allocation only where the case says so)."""
+    frame, plane = 4 * w * h * comps, 4 * w * h
+    return [dict(width=0), dict(height=0), dict(width=65536, height=32768), dict(components=4), dict(components=0), dict(components=15),
+            dict(op=2), dict(op=0xFFFFFFFF), dict(albedo_passes=0), dict(floor=0.0), dict(floor=-1.0), dict(floor=float("inf")), dict(floor=float("nan")),
+            dict(reserved=1), dict(color=None), dict(albedo=None), dict(output=None),
+            dict(color=color + 2), dict(albedo=albedo + 1), dict(output=output + 2), dict(variance=variance + 2), dict(output_variance=output_variance + 1),
+            dict(variance=None),                                           # output_variance without variance
+            dict(output=albedo), dict(output=albedo + frame - 4), dict(output=color + 4), dict(output=color - 4 if color >= 4 else color + 8),
+            dict(output=variance), dict(output_variance=variance + 4), dict(output_variance=color), dict(output_variance=albedo + frame - plane),
+            dict(output_variance=output), dict(output_variance=output + frame - 4)]
+
+
+def good_descriptor(w, h, comps, color, variance, albedo, output, output_variance, **over):
+    f = dict(width=w, height=h, components=comps, op=abi.MODULATE_DIVIDE, color=color, variance=variance, albedo=albedo, output=output,
+             output_variance=output_variance, albedo_passes=3, floor=1e-3, reserved=0)
+    f.update(over)
+    return abi.ModulateDesc(**f)
+
+
+def test_invalid_descriptors_are_refused_by_the_argument_check():
+    """The pure check (slrhip_debug_modulate_check: the function slrhip_modulate calls) on addresses that are never followed."""
+    lib = binding.load_library()
+    w, h, comps = 5, 3, 3
+    frame = 4 * w * h * comps
+    bufs = dict(color=0x10000, variance=0x20000, albedo=0x30000, output=0x40000, output_variance=0x50000)
+    assert lib.slrhip_debug_modulate_check(C.byref(good_descriptor(w, h, comps, **bufs))) == 0
+    for over in bad_descriptors(w, h, comps, **bufs):
+        assert lib.slrhip_debug_modulate_check(C.byref(good_descriptor(w, h, comps, **{**bufs, **over}))) == INVALID, over
+        assert b"slrhip_modulate" in lib.slrhip_last_error_string()
+    assert lib.slrhip_debug_modulate_check(None) == INVALID
+    # in place is allowed, adjacent ranges do not overlap, and either op, 16 components and no variance at all pass
+    ok = [dict(output=bufs["color"]), dict(output=bufs["color"], output_variance=bufs["variance"]), dict(output=bufs["albedo"] + frame),
+          dict(output=bufs["albedo"] - frame), dict(op=abi.MODULATE_MULTIPLY), dict(components=16), dict(variance=None, output_variance=None),
+          dict(output_variance=None), dict(floor=1e-30), dict(albedo_passes=0xFFFFFFFF)]
+    for over in ok:
+        assert lib.slrhip_debug_modulate_check(C.byref(good_descriptor(w, h, comps, **{**bufs, **over}))) == 0, over
+
+
+def test_host_program_parses_the_albedo_flags():
+    ap = host.build_parser()
+    a = ap.parse_args(["scene.txt"])
+    assert a.demodulate is False and a.albedo is None
+    a = ap.parse_args(["scene.txt", "--denoise", "--demodulate", "--albedo", "a.npy"])
+    assert (a.denoise, a.demodulate, a.albedo) == (5, True, "a.npy")
+
+
+def test_restatements_on_known_values():
+    """A perfect mirror (k -> infinity is not representable; eta = 1, k = 0 reflects nothing): F(1) = ((1-1)^2 + 0) / ((1+1)^2 + 0) = 0;
+    eta = 3, k = 0 gives ((3-1)/(3+1))^2 = 0.25 exactly."""
+    assert (fresnel_conductor_at_one(np.array([1, 3], F), np.array([0, 0], F)) == np.array([0, 0.25], F)).all()
+    c, v = np_modulate(np.full((1, 1, 3), 0.5, F), np.full((1, 1, 3), 2.0, F), 4, abi.MODULATE_DIVIDE, 1e-3, np.ones((1, 1), F))
+    assert (c == 1.0).all() and v[0, 0] == F(1.0) / (luminance(np.full((1, 3), 0.5, F))[0] ** 2)
+    assert (np_modulate(np.ones((1, 1, 3), F), np.array([[[np.nan, 0, np.inf]]], F), 1, abi.MODULATE_MULTIPLY, 0.25) == np.array([0.25, 0.25, np.inf], F)).all()
+
+
+# ---- GPU helpers ------------------------------------------------------------------------------------------------------------------
+def one_albedo_pass(ctx, st, pass_, shard=(0, 1)):
+    ctx.render_begin(st, shard)
+    ctx.render_albedo(1, pass_)
+    sums, passes = ctx.albedo()
+    assert passes == 1
+    return sums
+
+
+def ids_of_pass(ctx, st, pass_):
+    """(triangle, material) [h, w] uint32 of the pass's samples, from the feature pass of the same (pixel, pass)."""
+    ids = one_pass(ctx, st, abi.FEATURE_IDS, pass_)[abi.FEATURE_IDS]
+    return ids[:, :, 0], ids[:, :, 2]
+
+
+def expected_from_table(table, material):
+    hit = material != MISS
+    return np.where(hit[..., None], table[np.where(hit, material, 0)], F(1.0)).astype(F)
+
+
+# ---- 1. RGB, constant materials, bit for bit --------------------------------------------------------------------------------------
+CONSTANT_SCENES = {"cornell_box_spheres": lambda: scenes.cornell_box_spheres(4.0 / 3.0, 16, 8, "glass"),
+                   "cornell_instanced": lambda: scenes.cornell_instanced(1.0, 10, 5, copies=6),
+                   "displaced_grid_400": lambda: scenes.displaced_grid(400)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tree", sorted(TREES))
+@pytest.mark.parametrize("name", sorted(CONSTANT_SCENES))
+def test_rgb_constant_materials_bit_for_bit(name, tree):
+    sc = CONSTANT_SCENES[name]()
+    assert (sc.materials["spectrum"][sc.materials["type"] != abi.MAT_MULTI] >= -1).all()
+    table = constant_table(sc)
+    w, h = 32, 24
+    st = settings(w, h, seed=17)
+    ctx = binding.Context(flags=TREES[tree])
+    seen = set()
+    try:
+        ctx.upload_scene(sc)
+        for p in (0, 5):
+            _, material = ids_of_pass(ctx, st, p)
+            got = one_albedo_pass(ctx, st, p)
+            assert_same_bits(got, expected_from_table(table, material), "%s, %s tree, pass %d" % (name, tree, p))
+            seen |= set(np.unique(material).tolist())
+        assert ctx.features_status() == 0
+    finally:
+        ctx.close()
+    assert len(seen - {MISS}) >= (2 if name != "displaced_grid_400" else 1), seen
+
+
+# ---- 2. spectral, constant materials ------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CONSTANT_SCENES))
+def test_spectral_constant_materials_against_the_reference_spectra(ref_spectral, oracle_rgb, name):
+    """Component i = the reference's ContinuousSpectrum::evaluate at lambda_i of createWithEqualOffsets(offset, .), offset = the fourth
+    float of the sample's stream.  Tolerance: rtol 2e-6, atol 1e-9, the standing device-against-CPU tolerance of test_gpu_parity.py."""
+    sc = CONSTANT_SCENES[name]()
+    simple = (abi.MAT_MATTE, abi.MAT_METAL, abi.MAT_GLASS, abi.MAT_WARD)
+    ev = ref_spectral.lib.slr_ref_eval_spectrum
+    ev.argtypes = [C.POINTER(abi.SceneDesc), C.c_uint32, C.c_float, C.c_void_p]
+    d = sc.desc()
+    w, h = 16, 12
+    st = settings(w, h, seed=23)
+    rgb, ctx = binding.Context(), binding.Context(mode=abi.MODE_SPECTRAL)
+    hits = 0
+    try:
+        rgb.upload_scene(sc)
+        ctx.upload_scene(sc)
+        for p in (0, 1):
+            _, material = ids_of_pass(rgb, st, p)
+            got = one_albedo_pass(ctx, st, p)
+            want = np.ones((h, w, 16), F)
+            for y in range(h):
+                for x in range(w):
+                    m = int(material[y, x])
+                    if m == MISS:
+                        continue
+                    assert int(sc.materials[m]["type"]) in simple
+                    offset = oracle_rgb.rng(abi.sample_seed(st.rng_seed, x, y, p), 4)[1][3]
+                    assert ev(C.byref(d), int(sc.materials[m]["spectrum"][0]), float(offset), want[y, x].ctypes.data) == 0
+                    hits += 1
+            close = np.isclose(got, want, rtol=2e-6, atol=1e-9)
+            print("%s pass %d: largest relative difference %.3g" % (name, p, float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-9)))))
+            assert close.all(), "%s pass %d: %d of %d components outside the tolerance" % (name, p, (~close).sum(), close.size)
+        assert hits > 100 and ctx.features_status() == 0
+    finally:
+        rgb.close()
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_spectral_checker_texture_against_the_reference_spectra(ref_spectral, oracle_rgb):
+    """The spectral fold through texturizeMat: a hit on the checkerboard matte of cornell_textured is the reference's evaluation of
+    ONE of the texture's two spectra at the sample's own wavelength offset.  Which one: the RGB context's albedo of the same
+    (pixel, pass) — same ray, same hit, same texture coordinate — equals one of the two record colours bit for bit.  Same tolerance
+    as the constant materials (rtol 2e-6, atol 1e-9)."""
+    sc = SCENES["cornell_textured"][0]()
+    slots = textured_slots(sc)
+    checkers = {m: t for m, t in slots.items() if int(sc.textures[t]["kind"]) == abi.TEX_CHECKER_SPECTRUM and int(sc.materials[m]["type"]) == abi.MAT_MATTE}
+    assert checkers
+    ev = ref_spectral.lib.slr_ref_eval_spectrum
+    ev.argtypes = [C.POINTER(abi.SceneDesc), C.c_uint32, C.c_float, C.c_void_p]
+    d = sc.desc()
+    w, h = 24, 18
+    st = settings(w, h, seed=37)
+    rgb, ctx = binding.Context(), binding.Context(mode=abi.MODE_SPECTRAL)
+    cells = set()
+    try:
+        rgb.upload_scene(sc)
+        ctx.upload_scene(sc)
+        for p in (0, 1):
+            _, material = ids_of_pass(rgb, st, p)
+            colour = one_albedo_pass(rgb, st, p)
+            got = one_albedo_pass(ctx, st, p)
+            for y, x in zip(*np.nonzero(np.isin(material, list(checkers)))):
+                tex = sc.textures[checkers[int(material[y, x])]]
+                values = sc.spectra["rgb"][tex["spectrum"]].astype(F)
+                cell = [k for k in (0, 1) if (u32(values[k]) == u32(colour[y, x])).all()]
+                assert len(cell) == 1, (x, y, p)
+                offset = oracle_rgb.rng(abi.sample_seed(st.rng_seed, int(x), int(y), p), 4)[1][3]
+                want = np.zeros(16, F)
+                assert ev(C.byref(d), int(tex["spectrum"][cell[0]]), float(offset), want.ctypes.data) == 0
+                assert np.isclose(got[y, x], want, rtol=2e-6, atol=1e-9).all(), (x, y, p, got[y, x], want)
+                cells.add(cell[0])
+        assert cells == {0, 1} and ctx.features_status() == 0
+    finally:
+        rgb.close()
+        ctx.close()
+
+
+# ---- 3. / 4. glossy lobes and MultiBSDF scenes --------------------------------------------------------------------------------------
+def zero_lobe_scene():
+    """rgb_multi's scene with a new MULTI whose FIRST lobe is a matte of reflectance zero: the second lobe's colour must come out."""
+    sc = scene_from_golden(load_golden("rgb_multi"))
+    spectra = np.concatenate([sc.spectra, sc.spectra[:1]])
+    spectra[-1]["rgb"] = 0.0
+    n = len(sc.materials)
+    mats = np.concatenate([sc.materials, np.zeros(2, abi.material_dtype)])
+    mats[n] = (abi.MAT_MATTE, [len(spectra) - 1, -1, -1], -1.0, -1, 0.0, 0)
+    mats[n + 1] = (abi.MAT_MULTI, [n, 5, 0], 0.25, -1, 0.75, 0)
+    tris = sc.triangles.copy()
+    tris["material"][tris["material"] == 9] = n + 1
+    return abi.Scene(sc.vertices, tris, mats, spectra, sc.spectrum_data, sc.camera, name="zero_lobe"), n + 1
+
+
+def inverted_lobe_scene():
+    """rgb_multi's scene with a new MULTI whose first lobe is inverted: it has its base's colour, on either side."""
+    sc = scene_from_golden(load_golden("rgb_multi"))
+    n = len(sc.materials)
+    mats = np.concatenate([sc.materials, np.zeros(1, abi.material_dtype)])
+    mats[n] = (abi.MAT_MULTI, [6, 5, abi.MULTI_INVERSE_0], 0.5, -1, 0.5, 0)
+    tris = sc.triangles.copy()
+    tris["material"][tris["material"] == 9] = n
+    return abi.Scene(sc.vertices, tris, mats, sc.spectra, sc.spectrum_data, sc.camera, name="inverted_lobe"), n
+
+
+def golden_scene(name):
+    return lambda: (scene_from_golden(load_golden(name)), None)
+
+
+LOBE_SCENES = {"rgb_ggx_metal": (golden_scene("rgb_ggx_metal"), abi.MAT_MF_METAL), "rgb_ashikhmin": (golden_scene("rgb_ashikhmin"), abi.MAT_ASHIKHMIN),
+               "rgb_ward": (golden_scene("rgb_ward"), abi.MAT_WARD), "rgb_multi": (golden_scene("rgb_multi"), abi.MAT_MULTI),
+               "rgb_multi_nested": (golden_scene("rgb_multi_nested"), abi.MAT_MULTI), "zero_lobe": (zero_lobe_scene, abi.MAT_MULTI),
+               "inverted_lobe": (inverted_lobe_scene, abi.MAT_MULTI)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(LOBE_SCENES))
+def test_glossy_and_multi_materials_bit_for_bit(name):
+    """Microfacet metal: the float32 restatement of FresnelConductor::evaluate(1.0f); Ashikhmin: Rs + (1 - Rs) * Rd; Ward: R; MULTI: the
+    first lobe with a non-zero colour, each lobe with its `scale * spectrum`.  Bit for bit: the restatements are sequences of
+    correctly rounded float32 operations, which numpy and the device (no contraction, IEEE division) both perform."""
+    make, kind = LOBE_SCENES[name]
+    sc, special = make()
+    table = constant_table(sc)
+    if name == "zero_lobe":
+        assert (table[special] == F(0.75) * sc.spectra["rgb"][sc.materials[5]["spectrum"][0]]).all() and (table[special] != 0).any()
+    if name == "inverted_lobe":
+        assert (table[special] == F(0.5) * sc.spectra["rgb"][sc.materials[6]["spectrum"][0]]).all() and (table[special] != 0).any()
+    w, h = 40, 30
+    st = settings(w, h, seed=29)
+    ctx = binding.Context()
+    seen = set()
+    try:
+        ctx.upload_scene(sc)
+        for p in (0, 2):
+            _, material = ids_of_pass(ctx, st, p)
+            got = one_albedo_pass(ctx, st, p)
+            assert_same_bits(got, expected_from_table(table, material), "%s pass %d" % (name, p))
+            seen |= set(np.unique(material).tolist()) - {MISS}
+        assert ctx.features_status() == 0
+    finally:
+        ctx.close()
+    kinds = {int(sc.materials[m]["type"]) for m in seen}
+    assert kind in kinds, (name, kinds)
+    if special is not None:
+        assert special in seen
+    if name.startswith("rgb_multi"):
+        assert sum(int(sc.materials[m]["type"]) == abi.MAT_MULTI for m in seen) >= 2
+
+
+# ---- 5. textures --------------------------------------------------------------------------------------------------------------------
+def textured_slots(sc):
+    """{material index: texture index} for the materials whose slot 0 names a texture."""
+    return {i: -2 - int(m["spectrum"][0]) for i, m in enumerate(sc.materials) if int(m["type"]) != abi.MAT_MULTI and int(m["spectrum"][0]) <= -2}
+
+
+def texture_values(sc, t):
+    tex = sc.textures[t]
+    if int(tex["kind"]) == abi.TEX_CHECKER_SPECTRUM:
+        return sc.spectra["rgb"][tex["spectrum"]].astype(F)
+    assert int(tex["kind"]) == abi.TEX_IMAGE_SPECTRUM
+    tw, th, first = [int(v) for v in tex["reserved"]]
+    return sc.texture_texels[first:first + tw * th].astype(F)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell_textured", "rgb_image_textured"])
+def test_textured_materials_yield_the_textures_own_values(name):
+    """Every hit on a textured material (slot 0 of MATTE and METAL: R, coeffR) is, bit for bit, one of its texture's values.  For the
+    checkerboards the cell is predicted as well: the texture coordinate in float64 from the camera ray's hit (slrhip_camera_rays +
+    slrhip_intersect_rays) and the vertices' texture coordinates; a sample whose doubled mapped coordinate lies within 1e-4 of an
+    integer (a cell boundary, where float32 and float64 may disagree) is excluded.  The boundaries are lines: in a cell of side 1/2 the
+    excluded band is 2 * 1e-4 / 2 of each axis, about 0.04 % of the area; the cap of 2 % of the hits leaves room for perspective."""
+    sc = SCENES["cornell_textured"][0]() if name == "cornell_textured" else scene_from_golden(load_golden(name))
+    slots = textured_slots(sc)
+    table = np.stack([base_color_rgb(sc, i, slot_value=lambda *_: np.zeros(3, F)) for i in range(len(sc.materials))])
+    w, h = 64, 48
+    st = settings(w, h, seed=31)
+    ctx = binding.Context()
+    occurs = {m: set() for m in slots}
+    checked = excluded = 0
+    try:
+        ctx.upload_scene(sc)
+        for p in (0, 1, 2):
+            tri, material = ids_of_pass(ctx, st, p)
+            got = one_albedo_pass(ctx, st, p)
+            plain = ~np.isin(material, list(slots))
+            assert_same_bits(got[plain], expected_from_table(table, material)[plain], "%s pass %d: untextured materials and misses" % (name, p))
+            ctx.render_begin(st)
+            rows, xy = ctx.camera_rays(p)
+            hits, _ = ctx.intersect_rays(rows, want_instances=True)
+            assert (per_pixel(triangles_of(hits), xy, h, w) == tri).all()
+            b0, b1 = per_pixel(hits[:, 2], xy, h, w).astype(np.float64), per_pixel(hits[:, 3], xy, h, w).astype(np.float64)
+            for m, t in slots.items():
+                at = material == m
+                if not at.any():
+                    continue
+                values = texture_values(sc, t)
+                vb, gb = u32(values), u32(got[at])
+                which = (gb[:, None, :] == vb[None, :, :]).all(axis=2)
+                assert which.any(axis=1).all(), "%s pass %d material %d: a colour that is no value of texture %d" % (name, p, m, t)
+                occurs[m] |= set(np.flatnonzero(which.any(axis=0)).tolist())
+                if int(sc.textures[t]["kind"]) != abi.TEX_CHECKER_SPECTRUM:
+                    continue
+                tc = sc.vertices["texcoord"][sc.triangles["v"][tri[at]]].astype(np.float64)          # [n, 3, 2]
+                bb0, bb1 = b0[at], b1[at]
+                uv = bb0[:, None] * tc[:, 0] + bb1[:, None] * tc[:, 1] + (1.0 - bb0 - bb1)[:, None] * tc[:, 2]
+                tex = sc.textures[t]
+                xy2 = (uv + tex["offset"].astype(np.float64)) * tex["scale"].astype(np.float64) * 2.0
+                safe = (np.abs(xy2 - np.rint(xy2)) > 1e-4).all(axis=1)
+                cell = np.abs(np.trunc(xy2[:, 0]).astype(np.int64) + np.trunc(xy2[:, 1]).astype(np.int64)) % 2      # |C's s % 2|
+                assert (gb[safe] == vb[cell[safe]]).all(), "%s pass %d material %d: a checker cell other than the predicted one" % (name, p, m)
+                checked += int(safe.sum())
+                excluded += int((~safe).sum())
+        assert ctx.features_status() == 0
+    finally:
+        ctx.close()
+    assert any(occurs.values()), "no textured material was hit"
+    for m, t in slots.items():
+        if int(sc.textures[t]["kind"]) == abi.TEX_CHECKER_SPECTRUM and occurs[m]:
+            assert occurs[m] == {0, 1}, "material %d: not every checker colour occurs" % m
+    if name == "cornell_textured":
+        print("checker samples predicted: %d, excluded near a boundary: %d" % (checked, excluded))
+        assert checked > 500 and excluded <= 0.02 * (checked + excluded)
+
+
+# ---- 6. identities, bit for bit -----------------------------------------------------------------------------------------------------
+def albedo_of(ctx, st, calls, shard=(0, 1)):
+    ctx.render_begin(st, shard)
+    for begin, count in calls:
+        ctx.render_albedo(count, begin)
+    sums, passes = ctx.albedo()
+    assert passes == sum(c for _, c in calls)
+    return sums
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [abi.MODE_RGB, abi.MODE_SPECTRAL])
+def test_sums_do_not_depend_on_how_the_passes_are_cut_or_sharded(mode):
+    sc = SCENES["cornell_textured"][0]()
+    w, h = 40, 30
+    st = settings(w, h, seed=33)
+    ctx = binding.Context(mode=mode)
+    try:
+        ctx.upload_scene(sc)
+        whole = albedo_of(ctx, st, [(0, 16)])
+        assert_same_bits(albedo_of(ctx, st, [(0, 5), (5, 11)]), whole, "[0, 5) + [5, 16)")
+        shards = [albedo_of(ctx, st, [(0, 16)], (k, 2)) for k in range(2)]
+        assert ((shards[0] == 0) | (shards[1] == 0)).all()
+        assert_same_bits(shards[0] + shards[1], whole, "two shards")
+        sums = np.zeros_like(whole)
+        for p in range(16):
+            sums = sums + one_albedo_pass(ctx, st, p)
+        assert_same_bits(sums, whole, "the float32 sum of single passes in order")
+        assert ctx.features_status() == 0
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_a_call_longer_than_the_record_window_is_the_pass_ordered_sum():
+    """The record window holds at most 64 passes: 150 passes in one call run in three windows."""
+    sc = SCENES["cornell_textured"][0]()
+    st = settings(24, 18, seed=4)
+    ctx = binding.Context()
+    try:
+        ctx.upload_scene(sc)
+        whole = albedo_of(ctx, st, [(0, 150)])
+        assert_same_bits(albedo_of(ctx, st, [(0, 70), (70, 80)]), whole, "[0, 70) + [70, 150)")
+        sums = np.zeros_like(whole)
+        for p in range(150):
+            sums = sums + one_albedo_pass(ctx, st, p)
+        assert_same_bits(sums, whole, "150 single passes in order")
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_tree_kinds_give_the_same_sums():
+    sc = CONSTANT_SCENES["cornell_box_spheres"]()
+    st = settings(48, 36, seed=6)
+    got = {}
+    for tree, flags in TREES.items():
+        ctx = binding.Context(flags=flags)
+        try:
+            ctx.upload_scene(sc)
+            got[tree] = albedo_of(ctx, st, [(0, 6)])
+        finally:
+            ctx.close()
+    assert_same_bits(got["device"], got["host"], "device-built tree")
+    assert_same_bits(got["splits"], got["host"], "spatial splits")
+    assert (got["host"] != 6.0).any()
+
+
+@pytest.mark.gpu
+def test_an_environment_only_pixel_equals_the_pass_count():
+    sc = scene_from_golden(load_golden("rgb_ibl"))
+    w, h, spp = 40, 40, 7
+    st = settings(w, h, seed=2)
+    ctx = binding.Context()
+    try:
+        ctx.upload_scene(sc)
+        ctx.render_begin(st)
+        ctx.render_features(abi.FEATURE_COVERAGE, spp)
+        coverage = ctx.features(abi.FEATURE_COVERAGE)
+        sums = albedo_of(ctx, st, [(0, spp)])
+    finally:
+        ctx.close()
+    env_only = coverage == 0
+    assert env_only.sum() > 20 and (coverage == spp).sum() > 20
+    assert (sums[env_only] == F(spp)).all()
+    assert (sums[coverage == spp] != F(spp)).any()                       # (the mirror sphere's coeffR is one: not every covered pixel differs)
+
+
+@pytest.mark.gpu
+def test_render_feature_and_albedo_calls_interleave_without_changing_a_bit():
+    sc = SCENES["cornell_textured"][0]()
+    st = settings(48, 36, seed=3)
+
+    def fresh(work):
+        c = binding.Context(stripes=1)
+        try:
+            c.upload_scene(sc)
+            c.render_begin(st)
+            return work(c)
+        finally:
+            c.close()
+
+    def features(c):
+        return {ch: c.features(ch) for ch in abi.FEATURE_CHANNELS}
+
+    def render_alone(c):
+        c.render(0, 4)
+        c.render(4, 4)
+        return c.read_framebuffer(), counter_fields(c.counters())
+
+    def features_alone(c):
+        c.render_features(abi.FEATURE_ALL, 5, 0)
+        c.render_features(abi.FEATURE_ALL, 3, 5)
+        return features(c)
+
+    def albedo_alone(c):
+        c.render_albedo(3, 0)
+        c.render_albedo(5, 3)
+        return c.albedo()
+
+    def mixed(c):
+        c.render_albedo(3, 0)
+        c.render(0, 4)
+        c.render_features(abi.FEATURE_ALL, 5, 0)
+        c.render_albedo(5, 3)
+        c.render(4, 4)
+        c.render_features(abi.FEATURE_ALL, 3, 5)
+        assert c.features_status() == 0
+        return c.read_framebuffer(), counter_fields(c.counters()), features(c), c.albedo()
+    frame, counters = fresh(render_alone)
+    feats = fresh(features_alone)
+    albedo, passes = fresh(albedo_alone)
+    got = fresh(mixed)
+    assert_same_bits(got[0], frame, "the frame")
+    assert got[1] == counters
+    for ch in feats:
+        assert (got[2][ch].view(np.uint32) == feats[ch].view(np.uint32)).all(), abi.FEATURE_CHANNELS[ch][0]
+    assert got[3][1] == passes == 8
+    assert_same_bits(got[3][0], albedo, "the albedo")
+
+
+def in_child(check):
+    src = ("import sys, torch\nsys.path[:0] = [%r, %r]\nimport test_albedo as T\nT.%s()\nprint('CHILD_OK')\n"
+           % (ROOT, os.path.join(ROOT, "tests"), check))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", src]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "CHILD_OK" in p.stdout, (check, p.returncode, p.stdout[-3000:], p.stderr[-3000:])
+
+
+@pytest.mark.gpu
+def test_graph_captured_albedo_call_replays_the_eager_result():
+    """A later albedo call, its resolve and a modulate captured in a graph (a single branch) and replayed."""
+    in_child("_graph_check")
+
+
+def _graph_check():
+    import torch
+    sc = scenes.cornell_textured(1.0, 16, 8)
+    w, h = 48, 36
+    st = settings(w, h, seed=8)
+    ctx = binding.Context()
+    try:
+        ctx.upload_scene(sc)
+        want = albedo_of(ctx, st, [(0, 8)])
+        ctx.render_begin(st)
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            ctx.render_albedo(4, 0, stream=side)                          # the first call allocates and clears: passes [0, 4)
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+            ones = torch.ones((h, w, 3), dtype=torch.float32, device="cuda")
+            divided = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                s = torch.cuda.current_stream()
+                ctx.render_albedo(4, 4, stream=s)                         # passes [4, 8)
+                passes = ctx.albedo_into(out.data_ptr(), out.numel(), stream=s)
+                ctx.modulate_into(w, h, 3, abi.MODULATE_MULTIPLY, ones.data_ptr(), out.data_ptr(), 8, divided.data_ptr(), floor=1e-3, stream=s)
+            g.replay()
+            torch.cuda.synchronize()
+        assert passes == 8 and ctx.features_status(side) == 0
+        assert (out.cpu().numpy().view(np.uint32) == want.view(np.uint32)).all()
+        assert (divided.cpu().numpy().view(np.uint32) == np_modulate(np.ones((h, w, 3), F), want, 8, abi.MODULATE_MULTIPLY, 1e-3).view(np.uint32)).all()
+    finally:
+        ctx.close()
+
+
+# ---- 7. slrhip_modulate against the restatement --------------------------------------------------------------------------------------
+class DeviceBuffers:
+    def __init__(self):
+        self.hip, self.ptrs = binding._hip_runtime(), []
+
+    def put(self, array):
+        a = np.ascontiguousarray(array)
+        p = C.c_void_p()
+        binding._hip_check(self.hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
+        self.ptrs.append(p.value)
+        binding._hip_check(self.hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
+        return p.value
+
+    def get(self, ptr, shape, dtype=F):
+        a = np.empty(shape, dtype)
+        binding._hip_check(self.hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2), "hipMemcpy")
+        return a
+
+    def free(self):
+        for p in self.ptrs:
+            self.hip.hipFree(p)
+
+
+FLOOR, PASSES = 0.02, 7
+
+
+def modulate_inputs(w, h, comps):
+    rng = np.random.default_rng(100 * w + 10 * h + comps)
+    color = np.exp2(rng.uniform(-6.0, 6.0, (h, w, comps))).astype(F)
+    albedo = (PASSES * rng.uniform(0.03, 1.0, (h, w, comps))).astype(F)
+    variance = np.exp2(rng.uniform(-12.0, 2.0, (h, w))).astype(F)
+    special = np.zeros((h, w), bool)
+    if w * h >= 15:
+        flat, sp = albedo.reshape(-1, comps), special.reshape(-1)
+        where = rng.choice(w * h, 5, replace=False)
+        for k, v in enumerate((0.0, np.nan, np.inf, PASSES * FLOOR * 0.5, PASSES * FLOOR * 0.999)):
+            flat[where[k], rng.integers(0, comps)] = v
+            sp[where[k]] = True
+        flat[where[0]] = 0.0                                               # one pixel black in every component
+    return color, albedo, variance, special
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = binding.Context()
+    yield c
+    c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("comps", [3, 16])
+@pytest.mark.parametrize("width, height", [(1, 1), (5, 3), (67, 35)])
+def test_modulate_equals_the_restatement(ctx, width, height, comps):
+    """Bit for bit, both ops, with and without variance, in place and out of place.  Then DIVIDE followed by MULTIPLY returns every
+    finite colour within 2 ulp wherever the divisor is finite: two roundings of at most 2^-24 relative each."""
+    w, h = width, height
+    color, albedo, variance, special = modulate_inputs(w, h, comps)
+    dev = DeviceBuffers()
+    try:
+        pa = dev.put(albedo)
+        for op in (abi.MODULATE_DIVIDE, abi.MODULATE_MULTIPLY):
+            want, want_v = np_modulate(color, albedo, PASSES, op, FLOOR, variance)
+            # out of place, with variance: the inputs stay as they are
+            pc, pv = dev.put(color), dev.put(variance)
+            po, pov = dev.put(np.full(color.shape, -7.0, F)), dev.put(np.full(variance.shape, -7.0, F))
+            ctx.modulate_into(w, h, comps, op, pc, pa, PASSES, po, pv, pov, FLOOR)
+            ctx.synchronize()
+            assert_same_bits(dev.get(po, color.shape), want, "op %d out of place" % op)
+            assert_same_bits(dev.get(pov, variance.shape), want_v, "op %d variance out of place" % op)
+            assert_same_bits(dev.get(pc, color.shape), color, "color untouched")
+            assert_same_bits(dev.get(pv, variance.shape), variance, "variance untouched")
+            assert_same_bits(dev.get(pa, albedo.shape), albedo, "albedo untouched")
+            # without variance: the variance output is not written
+            po2 = dev.put(np.full(color.shape, -7.0, F))
+            ctx.modulate_into(w, h, comps, op, pc, pa, PASSES, po2, None, None, FLOOR)
+            ctx.modulate_into(w, h, comps, op, pc, pa, PASSES, po, pv, None, FLOOR)          # a variance without an output for it
+            ctx.synchronize()
+            assert_same_bits(dev.get(po2, color.shape), want, "op %d without variance" % op)
+            assert_same_bits(dev.get(pov, variance.shape), want_v, "op %d: the variance output of the earlier call" % op)
+            # in place
+            ctx.modulate_into(w, h, comps, op, pc, pa, PASSES, pc, pv, pv, FLOOR)
+            ctx.synchronize()
+            assert_same_bits(dev.get(pc, color.shape), want, "op %d in place" % op)
+            assert_same_bits(dev.get(pv, variance.shape), want_v, "op %d variance in place" % op)
+            # the host-array convenience
+            got = ctx.modulate(color, albedo, PASSES, op, variance, FLOOR)
+            assert_same_bits(got[0], want, "Context.modulate")
+            assert_same_bits(got[1], want_v, "Context.modulate variance")
+            assert_same_bits(ctx.modulate(color, albedo, PASSES, op, floor=FLOOR), want, "Context.modulate without variance")
+        # the round trip
+        back = ctx.modulate(ctx.modulate(color, albedo, PASSES, abi.MODULATE_DIVIDE, floor=FLOOR), albedo, PASSES, abi.MODULATE_MULTIPLY, floor=FLOOR)
+        finite = np.isfinite(np.fmax(albedo / F(PASSES), F(FLOOR)))
+        ulp = np.spacing(color)
+        assert finite.sum() >= albedo.size - 1 and (np.abs(back[finite].astype(np.float64) - color[finite]) <= 2.0 * ulp[finite]).all()
+        if special.any():
+            a = np.fmax(albedo / F(PASSES), F(FLOOR))
+            assert (a == F(FLOOR)).sum() >= 3 + comps and np.isinf(a).sum() == 1
+    finally:
+        dev.free()
+
+
+# ---- 8. loud failures -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_loud_failures():
+    c = binding.Context()
+    lib = c.lib
+    passes = C.c_uint32(0)
+    host_buf = np.zeros(32 * 24 * 3, F)
+    dev = DeviceBuffers()
+    try:
+        room = dev.put(np.zeros(32 * 24 * 3 + 4, F))
+        with pytest.raises(binding.SlrHipError, match=r"\(4\).*render_begin"):
+            c.render_albedo(1)
+        c.upload_scene(scenes.tiny_box())
+        with pytest.raises(binding.SlrHipError, match=r"\(4\).*render_begin"):
+            c.render_albedo(1)
+        assert lib.slrhip_resolve_albedo(c.handle, room, host_buf.size, C.byref(passes), None) == NO_SCENE
+        assert lib.slrhip_read_albedo(c.handle, host_buf.ctypes.data, host_buf.size, C.byref(passes)) == NO_SCENE
+        st = settings(32, 24)
+        c.render_begin(st)
+        with pytest.raises(binding.SlrHipError, match=r"\(1\).*2\^32"):
+            c.render_albedo(2, 0xFFFFFFFF)
+        c.render_albedo(0, 5)                                             # spp_count == 0 does nothing
+        sums, n = c.albedo()
+        assert n == 0 and (sums == 0).all()
+        c.render_albedo(2)
+        for ptr, size, what in ((None, host_buf.size, b"null"), (room + 2, host_buf.size, b"misaligned"), (room, host_buf.size - 1, b"too small")):
+            assert lib.slrhip_resolve_albedo(c.handle, ptr, size, C.byref(passes), None) == INVALID
+            assert what in lib.slrhip_last_error_string()
+        assert lib.slrhip_read_albedo(c.handle, None, host_buf.size, None) == INVALID and b"null" in lib.slrhip_last_error_string()
+        assert lib.slrhip_read_albedo(c.handle, host_buf.ctypes.data, host_buf.size - 1, None) == INVALID and b"too small" in lib.slrhip_last_error_string()
+        assert lib.slrhip_resolve_albedo(c.handle, room, host_buf.size, None, None) == 0          # `passes` may be NULL
+        # slrhip_modulate: every refusal of the header's list, on real buffers; nothing is written
+        w, h, comps = 5, 3, 3
+        frame = 4 * w * h * comps
+        big = dev.put(np.full(5 * frame // 4, -3.0, F))
+        bufs = dict(color=dev.put(np.ones((h, w, comps), F)), variance=dev.put(np.ones((h, w), F)), albedo=big + frame,
+                    output=big + 3 * frame, output_variance=dev.put(np.full((h, w), -3.0, F)))
+        for over in bad_descriptors(w, h, comps, **bufs):
+            assert lib.slrhip_modulate(c.handle, C.byref(good_descriptor(w, h, comps, **{**bufs, **over})), None) == INVALID, over
+            assert b"slrhip_modulate" in lib.slrhip_last_error_string()
+        assert lib.slrhip_modulate(c.handle, None, None) == INVALID
+        c.synchronize()
+        assert (dev.get(big, 5 * frame // 4) == -3.0).all() and (dev.get(bufs["output_variance"], (h, w)) == -3.0).all(), "a refused call wrote"
+        assert (dev.get(bufs["color"], (h, w, comps)) == 1.0).all() and (dev.get(bufs["variance"], (h, w)) == 1.0).all()
+        with pytest.raises(binding.SlrHipError, match="albedo_passes"):
+            c.render_begin(st)
+            c.statistics_begin()
+            c.render(0, 2)
+            c.render_features(GUIDES, 2)
+            c.denoised(demodulate=True)                                   # no render_albedo call: zero passes
+        # demodulation with a variance output but no variance input: the filtered variance could not be multiplied back
+        with pytest.raises(ValueError, match="variance"):
+            c._denoise_staged((h, w, comps), lambda name, ptr: name == "color", dict(iterations=1), True, None, 1e-3)
+        # the context is usable afterwards
+        c.render_begin(st)
+        c.render_albedo(3)
+        sums, n = c.albedo()
+        assert n == 3 and (sums >= 0).all() and sums.max() > 0 and c.features_status() == 0
+        assert lib.slrhip_modulate(c.handle, C.byref(good_descriptor(w, h, comps, **bufs)), None) == 0
+        c.synchronize()
+    finally:
+        dev.free()
+        c.close()
+
+
+# ---- 9. end to end --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_denoised_with_demodulation_equals_the_numpy_pipeline():
+    """cornell_textured, 48 x 36, 8 spp, statistics on: Context.denoised(demodulate=True) = numpy modulate -> the numpy filter of
+    test_denoise.py -> numpy modulate, bit for bit, variance included; demodulate=False is the call without the argument."""
+    sc = SCENES["cornell_textured"][0]()
+    w, h, spp = 48, 36, 8
+    st = settings(w, h, seed=5)
+    params = dict(iterations=5, sigma_luminance=4.0, sigma_distance=abi.DENOISE_SIGMA_DISTANCE, normal_power_log2=7)
+    c = binding.Context()
+    try:
+        c.upload_scene(sc)
+        c.render_begin(st)
+        c.statistics_begin()
+        c.render(0, spp)
+        c.render_features(GUIDES, spp)
+        plain_before = c.denoised(want_variance=True)
+        c.render_albedo(spp)
+        inputs = dict(color=c.read_framebuffer_mean(), variance=c.statistics(abi.STATISTICS_VARIANCE_OF_MEAN),
+                      normal=c.features(abi.FEATURE_SHADING_NORMAL), distance=c.features(abi.FEATURE_DISTANCE), coverage=c.features(abi.FEATURE_COVERAGE))
+        albedo, passes = c.albedo()
+        got, got_v = c.denoised(want_variance=True, demodulate=True)
+        plain, plain_v = c.denoised(want_variance=True, demodulate=False)
+        only = c.denoised(demodulate=True)
+    finally:
+        c.close()
+    assert passes == spp
+    floor = abi.MODULATE_FLOOR
+    color, variance = np_modulate(inputs["color"], albedo, passes, abi.MODULATE_DIVIDE, floor, inputs["variance"])
+    out, out_v = restate(color, variance, inputs["normal"], inputs["distance"], inputs["coverage"], **params)
+    want, want_v = np_modulate(out, albedo, passes, abi.MODULATE_MULTIPLY, floor, out_v)
+    assert_same_bits(got, want, "the demodulated pipeline")
+    assert_same_bits(got_v, want_v, "its variance")
+    assert_same_bits(only, want, "without the variance output")
+    want_plain = restate(**inputs, **params)
+    assert_same_bits(plain, want_plain[0], "demodulate=False")
+    assert_same_bits(plain_v, want_plain[1], "demodulate=False, variance")
+    assert_same_bits(plain_before[0], plain, "the plain result before and after the albedo pass")
+    assert (u32(got) != u32(plain)).mean() > 0.5                         # the two pipelines are different filters
+
+
+# ---- 10. the edge-preservation property ------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_a_texture_edge_survives_the_demodulated_filter_exactly():
+    """Synthetic buffers: a flat wall (constant normal and distance, full coverage), an albedo of 0.1 left and 0.9 right of a vertical
+    edge, color = albedo * 0.5, no variance (the luminance stop is off).
+
+    The bound, from the operation count: it is ZERO.  (1) color = a * 0.5 is exact (a power of two), so DIVIDE gives (a * 0.5) / a =
+    0.5 exactly in every pixel: the filter's input is the constant 0.5.  (2) The guides are equal in all pixels, so w_n = 1^128 = 1 and
+    w_z = (1 - 0)^2 = 1 exactly, and every tap weight is a product h[dx] h[dy] of {1/16, 1/4, 3/8}: a multiple of 1/256, exact.  (3) The
+    sums of at most 25 such weights are multiples of 1/256 not above 1 and the sums of w * 0.5 multiples of 1/512: both exact in a
+    24-bit significand.  So every iteration returns (W * 0.5) / W = 0.5 with no rounding at all, and (4) MULTIPLY gives 0.5 * a = color
+    exactly.  The normalised tap sum performs no inexact operation, hence equality of bits.
+
+    The plain filter of the same color mixes across the edge: in the first iteration (B3 weights) the two columns across the edge
+    carry 1/4 + 1/16 = 5/16 of the row weight, so 0.05 becomes at least 0.05 + 0.4 * 5/16 = 0.175: far more than 10 %."""
+    w, h, edge, comps = 40, 24, 20, 3
+    a = np.where(np.arange(w)[None, :, None] < edge, F(0.1), F(0.9)) * np.ones((h, w, comps), F)
+    albedo = a.astype(F)
+    color = albedo * F(0.5)
+    normal = np.zeros((h, w, 3), F)
+    normal[..., 2] = 1.0
+    distance, coverage = np.full((h, w), 2.5, F), np.ones((h, w), F)
+    params = dict(iterations=5, sigma_luminance=4.0, sigma_distance=abi.DENOISE_SIGMA_DISTANCE, normal_power_log2=7)
+    c = binding.Context()
+    try:
+        divided = c.modulate(color, albedo, 1, abi.MODULATE_DIVIDE, floor=1e-3)
+        assert (divided == F(0.5)).all()
+        filtered = c.denoise(divided, None, normal, distance, coverage, **params)
+        back = c.modulate(filtered, albedo, 1, abi.MODULATE_MULTIPLY, floor=1e-3)
+        plain = c.denoise(color, None, normal, distance, coverage, **params)
+    finally:
+        c.close()
+    assert_same_bits(filtered, divided, "the filter on the constant irradiance")
+    assert_same_bits(back, color, "divide -> denoise -> multiply")
+    dark, bright = plain[h // 2, edge - 1, 0], plain[h // 2, edge, 0]
+    print("plain filter next to the edge: %.4f (was 0.05), %.4f (was 0.45)" % (dark, bright))
+    assert dark >= 0.175 and abs(dark - 0.05) > 0.1 * 0.05 and abs(bright - 0.45) > 0.1 * 0.45
+
+
+# ---- the host program -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_host_program_writes_the_demodulated_image_and_the_albedo(tmp_path, capsys):
+    from test_scene_language import cornell_script
+    w, h, spp = 32, 24, 4
+    script = tmp_path / "box.txt"
+    script.write_text(cornell_script("matte").replace('"width": 320, "height": 240', '"width": %d, "height": %d' % (w, h)))
+    plain, demod = tmp_path / "plain", tmp_path / "demod"
+    plain.mkdir()
+    demod.mkdir()
+    args = [str(script), "--samples", str(spp), "--denoise", "2"]
+    assert host.main(args + ["--out", str(plain)]) == 0
+    assert host.main(args + ["--out", str(demod), "--demodulate", "--albedo", str(tmp_path / "albedo.npy")]) == 0
+    capsys.readouterr()
+    names = ["000.bmp", "001.bmp", "002.bmp", "002_denoised.bmp"]
+    assert sorted(os.listdir(plain)) == sorted(os.listdir(demod)) == names
+    for name in names[:3]:                                              # without the flags the program does what it did
+        assert (plain / name).read_bytes() == (demod / name).read_bytes(), name
+    a, b = (plain / names[3]).read_bytes(), (demod / names[3]).read_bytes()
+    assert len(a) == len(b) and a[:54] == b[:54] and a != b
+    mean = np.load(tmp_path / "albedo.npy")
+    assert mean.shape == (h, w, 3) and mean.dtype == F and (mean > 0).all() and (mean <= 1).all()
