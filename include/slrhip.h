@@ -751,6 +751,95 @@ int slrhip_read_framebuffer_mean(slrhip_ctx* ctx, float* host_dst, size_t num_fl
  * host since the last check (slrhip_render_adaptive blocks), so nothing is queued on `stream`.                                */
 int slrhip_adaptive_active(slrhip_ctx* ctx, uint32_t* host_count, void* stream);   /* pixels of the shard not yet retired */
 
+/* ---- sample clamp: bound a sample's luminance, drop non-finite samples ---------------------------------------------------------
+ * A firefly — one sample many orders of magnitude brighter than its pixel's mean — or a single NaN sample spoils a pixel for any
+ * pass count a user can afford, and everything downstream with it (the noise records, the denoiser, the tone map).  With a clamp
+ * on, the pass that adds a window's samples to the sensor first puts EVERY sample through the rule below: those of slrhip_render,
+ * slrhip_render_until and slrhip_render_adaptive, whichever kernel rendered them (no kernel adds to the sensor anywhere else).
+ *
+ * The rule, per sample v of C components as the sensor would receive it, BEFORE the Kahan add and the Welford step; float32, every
+ * operation IEEE-rounded on its own (no fused multiply-add), IEEE division:
+ *     Y = the expression of slrhip_sample_luminance on v
+ *     if (flags & SLRHIP_CLAMP_DROP_NONFINITE) && !(fabsf(Y) < INFINITY):            NaN or +-infinity
+ *         v[k] = +0.0f for every k;  Y = +0.0f;  record.dropped += 1
+ *     else if Y > limit:                                                             false for a NaN; Y == limit is not clamped
+ *         f = limit / Y;  v[k] = v[k] * f for every k
+ *         Y' = the same expression on the scaled v
+ *         record.clamped += 1;  record.removed = record.removed + (Y - Y');  record.largest = fmaxf(record.largest, Y);  Y = Y'
+ *     then the Kahan add of v into the sensor and, with statistics on, the Welford step on Y, both as without a clamp.
+ * A generated NaN (infinity x 0 when an infinite sample is clamped, infinity - infinity) has no specified sign or payload: where
+ * the rule yields a NaN, only THAT it is one is defined.
+ *
+ * Consequences.
+ *   - The statistics are those of the samples as the sensor received them: the noise records of a clamped render are the Welford
+ *     steps over the clamped samples' luminances.
+ *   - Without DROP_NONFINITE a NaN sample is added as before (NaN > limit is false), and an infinite one is "clamped" into NaNs.
+ *   - A sample of negative luminance is never touched; nor is one whose components are non-finite but whose Y is finite and
+ *     <= limit (the test is on Y alone).
+ *   - Directly visible emitters are clamped like everything else: the sensor receives only a sample's total.
+ *   - `limit` is in the un-normalised units of slrhip_sample_luminance (not divided by the pass count).  For an image tone-mapped
+ *     with `scale`, the displayed value of a sample is scale x Y.
+ *   - The clamp is BIASED: it removes energy, record.removed per pixel.  It trades that bias for variance; choose the limit well
+ *     above what a converged pixel of the scene shows.
+ *   - The rule reads (pixel, pass) samples alone, in pass order, so the frame, the noise records and the clamp records keep every
+ *     invariant of the unclamped ones: they do not depend — in any bit — on the slot count, the shard split, the result windows,
+ *     how the passes are cut into calls (ascending), the tail kernel or scheduling.  A multi-rank host needs no exchange.
+ *   - A render that does not call slrhip_clamp_begin launches the kernels it launched before and produces the same bits.        */
+#define SLRHIP_CLAMP_DROP_NONFINITE 1u     /* slrhip_clamp_desc::flags                                                         */
+typedef struct slrhip_clamp_desc {
+    float    limit;        /* > 0; INFINITY: clamp nothing (with DROP_NONFINITE: "drop only")                              */
+    uint32_t flags;        /* SLRHIP_CLAMP_DROP_NONFINITE or 0                                                             */
+    uint32_t reserved[2];  /* 0                                                                                            */
+} slrhip_clamp_desc;
+/* Switches the clamp on for the render that slrhip_render_begin just began: after slrhip_render_begin and before that render's
+ * first render call, the contract of slrhip_statistics_begin (later: SLRHIP_ERR_INVALID_ARGUMENT, the render goes on untouched;
+ * before slrhip_render_begin: SLRHIP_ERR_NO_SCENE).  Independent of statistics: with or without them, in either order.  A second
+ * call before the first render replaces the first's limit and flags.  SLRHIP_ERR_INVALID_ARGUMENT for a null argument, a NaN or
+ * non-positive limit, unknown flag bits or a nonzero `reserved`; a refused call changes nothing.  Allocates one 16-byte record
+ * per pixel of the shard, {uint32 clamped, uint32 dropped, float removed, float largest}, and the summary's partials; they are
+ * kept for later renders and freed with the context, and a failed allocation (SLRHIP_ERR_HIP) leaves the clamp off and the render
+ * usable.  The records are cleared in stream order by the first clamp-aware call that follows (render, resolve, summary), on that
+ * call's stream.  Every slrhip_render_begin switches the clamp off again.                                                     */
+int slrhip_clamp_begin(slrhip_ctx* ctx, const slrhip_clamp_desc* desc);
+
+/* Channels of slrhip_resolve_clamp / slrhip_read_clamp (ONE bit per call), each [height][width] float32:                    */
+#define SLRHIP_CLAMP_CLAMPED  1u   /* samples of the pixel that were scaled down, as float                                     */
+#define SLRHIP_CLAMP_DROPPED  2u   /* samples of the pixel that were replaced by zero, as float                                */
+#define SLRHIP_CLAMP_REMOVED  4u   /* luminance taken away from the pixel: the float32 sum, in pass order, of Y - Y'           */
+#define SLRHIP_CLAMP_LARGEST  8u   /* largest luminance a clamped sample of the pixel came with (0: none was clamped)          */
+#define SLRHIP_CLAMP_ALL     15u
+/* One channel into DEVICE memory / HOST memory: pointer, alignment, size, zero-fill and blocking rules are those of
+ * slrhip_resolve_statistics / slrhip_read_statistics, so the channels of shards add up to the whole frame's.
+ * SLRHIP_ERR_INVALID_ARGUMENT when the clamp is off, when `channel` is not exactly one SLRHIP_CLAMP_* bit, or when the
+ * destination is null, misaligned (4 bytes) or too small; SLRHIP_ERR_NO_SCENE before slrhip_render_begin.                     */
+int slrhip_resolve_clamp(slrhip_ctx* ctx, uint32_t channel, float* device_dst, size_t num_floats, void* stream);
+int slrhip_read_clamp(slrhip_ctx* ctx, uint32_t channel, float* host_dst, size_t num_floats);
+
+/* Totals over the pixels of the shard.  clamped, dropped and removed ADD over shards, largest takes the larger.  `removed` is the
+ * sum in double of the pixels' float32 REMOVED values in a FIXED order, that of slrhip_statistics_summary.  With the shard's
+ * pixels p = 0 .. P-1 in the order of its pixel list, and x[p] = 0 for p >= P:
+ *     block b = 0 .. ceil(P / 4096) - 1, thread t = 0 .. 255:   a[b][t] = (..((0 + x[4096 b + t]) + x[4096 b + 256 + t]) + ..) + x[4096 b + 3840 + t]
+ *     per wave w = 0..3 of a block, over its 64 threads:        for off = 32, 16, 8, 4, 2, 1:  a[t] = a[t] + a[t + off]  for t < off
+ *     per block:                                                 B[b] = ((a[0] + a[64]) + a[128]) + a[192]   (the waves' results)
+ *     removed = (..((0 + B[0]) + B[1]) + ..)
+ * so the value can be restated exactly.  Two calls on the same state return the same bits.                                    */
+struct slrhip_clamp_summary {
+    uint64_t clamped;                 /* sum of CLAMPED                                               */
+    uint64_t dropped;                 /* sum of DROPPED                                               */
+    double removed;                   /* sum of REMOVED, in the order above                           */
+    float largest;                    /* largest LARGEST                                              */
+    uint32_t reserved;
+};                                    /* 32 bytes */
+/* Fills *host_out (HOST memory) in order on `stream`; waits for that stream only, not for the device.  Allocates nothing.
+ * SLRHIP_ERR_INVALID_ARGUMENT when the clamp is off; SLRHIP_ERR_NO_SCENE before slrhip_render_begin.                          */
+int slrhip_clamp_summary(slrhip_ctx* ctx, struct slrhip_clamp_summary* host_out, void* stream);
+
+/* The rule on ONE sample, on the host, with the very function the kernels call: `in` and `out` hold `components` (3 or 16) floats
+ * and may be the same array; *y_in receives Y of the sample as given, *y_out that of the sample as the sensor would receive it
+ * (either may be NULL).  Returns 0 (kept), 1 (clamped) or 2 (dropped); -1 for another component count or a null `in` / `out`
+ * (nothing is written).  `limit` and `flags` are taken as they are, unchecked.  Pure function; no GPU is touched.               */
+int slrhip_clamp_sample(int32_t components, const float* in, float limit, uint32_t flags, float* out, float* y_in, float* y_out);
+
 /* ---- denoising: a variance-guided, edge-avoiding a-trous filter on device buffers --------------------------------------------
  * The feature buffers, the noise records and the mean frame above are the inputs of a denoiser; this is the denoiser: the 5 x 5
  * B3-spline a-trous wavelet filter with the edge-stopping weights of SVGF (normal, distance, luminance over the local standard

@@ -53,6 +53,16 @@ int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t s
  * slrhip_last_error_string.  The pointers are only compared, never followed.  No GPU is touched.                                  */
 int slrhip_debug_modulate_check(const slrhip_modulate_desc* desc);
 
+/* The caller's samples through the fold: host_samples is [passes][height][width][components] float32 (HOST memory), passes 1 .. 64.
+ * The shard's pixels are reordered with the context's own pixel list into a result window (pass-major, as the render kernels
+ * write it; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's
+ * current state — statistics on or off, clamp on or off — adds it to the sensor, the noise records and the clamp records, after
+ * whatever the render has added so far.  Blocking (synchronises the device).  The render's counters and its error word are
+ * untouched.  The call counts as the render having begun (slrhip_statistics_begin and slrhip_clamp_begin are refused after it),
+ * and as the first such call it clears the sensor.  This is how NaN, infinite and huge samples reach the kernel at tiny sizes.
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null argument or a pass count out of range; SLRHIP_ERR_NO_SCENE before slrhip_render_begin.   */
+int slrhip_debug_fold(slrhip_ctx* ctx, const float* host_samples, uint32_t passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,21 @@ class StatisticsSummary(C.Structure):
                 ("sum_variance_of_mean", C.c_double), ("max_sample", C.c_float), ("reserved", C.c_uint32)]
 
 
+# the sample clamp (slrhip_clamp_begin): the flag, the record channels -> npz name
+CLAMP_DROP_NONFINITE = 1
+CLAMP_CLAMPED, CLAMP_DROPPED, CLAMP_REMOVED, CLAMP_LARGEST = 1, 2, 4, 8
+CLAMP_ALL = 15
+CLAMP_CHANNELS = {CLAMP_CLAMPED: "clamped", CLAMP_DROPPED: "dropped", CLAMP_REMOVED: "removed", CLAMP_LARGEST: "largest"}
+
+
+class ClampDesc(C.Structure):
+    _fields_ = [("limit", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ClampSummary(C.Structure):
+    _fields_ = [("clamped", C.c_uint64), ("dropped", C.c_uint64), ("removed", C.c_double), ("largest", C.c_float), ("reserved", C.c_uint32)]
+
+
 class NoiseTarget(C.Structure):
     _fields_ = [("metric", C.c_uint32), ("target", C.c_float), ("spp_step", C.c_uint32), ("spp_max", C.c_uint32)]
 

@@ -19,6 +19,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_render_adaptive", "slrhip_resolve_framebuffer_mean", "slrhip_read_framebuffer_mean", "slrhip_adaptive_active", "slrhip_debug_adaptive_blocks",
            "slrhip_denoise", "slrhip_denoise_scratch_bytes", "slrhip_tonemap", "slrhip_tonemap_bytes",
            "slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate", "slrhip_debug_modulate_check",
+           "slrhip_clamp_begin", "slrhip_resolve_clamp", "slrhip_read_clamp", "slrhip_clamp_summary", "slrhip_clamp_sample", "slrhip_debug_fold",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -105,6 +106,15 @@ def load_library():
                            ("slrhip_read_albedo", [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
                            ("slrhip_modulate", [C.c_void_p, C.POINTER(abi.ModulateDesc), C.c_void_p]),
                            ("slrhip_debug_modulate_check", [C.POINTER(abi.ModulateDesc)])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before the sample clamp lacks these six)
+    for name, argtypes in (("slrhip_clamp_begin", [C.c_void_p, C.POINTER(abi.ClampDesc)]),
+                           ("slrhip_resolve_clamp", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_read_clamp", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_clamp_summary", [C.c_void_p, C.POINTER(abi.ClampSummary), C.c_void_p]),
+                           ("slrhip_clamp_sample", [C.c_int32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+                           ("slrhip_debug_fold", [C.c_void_p, C.c_void_p, C.c_uint32])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
@@ -465,6 +475,41 @@ class Context:
                "slrhip_render_until")
         return done.value, self._summary_dict(last)
 
+    # ---- the sample clamp (slrhip_clamp_begin / slrhip_resolve_clamp / slrhip_clamp_summary) ----
+    def clamp_begin(self, limit, drop_nonfinite=False):
+        """Switches the sample clamp on for the render that render_begin just began (before its first render()): a sample whose
+        luminance exceeds `limit` (un-normalised, the units of sample_luminance) is scaled down to it; with `drop_nonfinite` a
+        sample whose luminance is NaN or infinite is replaced by zero.  limit = inf: drop only."""
+        d = abi.ClampDesc(limit, abi.CLAMP_DROP_NONFINITE if drop_nonfinite else 0)
+        _check(self.lib, self.lib.slrhip_clamp_begin(self.handle, C.byref(d)), "slrhip_clamp_begin")
+
+    def clamp_into(self, channel, device_ptr, num_floats, stream=None):
+        """One abi.CLAMP_* channel into device memory at `device_ptr` ([height, width] float32), ordered on `stream`."""
+        _check(self.lib, self.lib.slrhip_resolve_clamp(self.handle, channel, device_ptr, num_floats, self._stream_handle(stream)), "slrhip_resolve_clamp")
+
+    def clamp(self, channel):
+        """One abi.CLAMP_* channel as a numpy array [height, width] float32, zeros outside the shard.  Synchronises."""
+        h, w = self.settings.image_height, self.settings.image_width
+        out = np.empty((h, w), np.float32)
+        _check(self.lib, self.lib.slrhip_read_clamp(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_clamp")
+        return out
+
+    def clamp_summary(self, stream=None):
+        """The shard's totals (slrhip_clamp_summary) as a dict; waits for `stream` only.  Dicts of shards add field by field,
+        except `largest` (take the larger)."""
+        s = abi.ClampSummary()
+        _check(self.lib, self.lib.slrhip_clamp_summary(self.handle, C.byref(s), self._stream_handle(stream)), "slrhip_clamp_summary")
+        return {name: getattr(s, name) for name, _ in abi.ClampSummary._fields_ if name != "reserved"}
+
+    def debug_fold(self, samples):
+        """Diagnostic (slrhip_debug_fold): `samples` [passes, height, width, components] float32 through the fold of the context's
+        current state (statistics and clamp on or off), added to the sensor and the records.  Blocking."""
+        h, w = self.settings.image_height, self.settings.image_width
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 4 or samples.shape[1:] != (h, w, self.components):
+            raise ValueError("debug_fold: samples must be [passes, %d, %d, %d]" % (h, w, self.components))
+        _check(self.lib, self.lib.slrhip_debug_fold(self.handle, samples.ctypes.data, samples.shape[0]), "slrhip_debug_fold")
+
     # ---- adaptive sampling (slrhip_render_adaptive / slrhip_read_framebuffer_mean / slrhip_adaptive_active) ----
     def render_adaptive(self, spp_begin, threshold, floor, spp_min, spp_step, spp_max, stream=None):
         """Renders blocks of passes from `spp_begin` (spp_min, then spp_step each, cut to spp_max) and retires, after each block,
@@ -681,3 +726,16 @@ class Context:
         self.render_begin(settings, shard)
         self.render(0, spp)
         return self.read_framebuffer()
+
+
+def clamp_sample(values, limit, flags=0):
+    """The sample clamp on one sample of 3 or 16 float32 values, on the host with the function the kernels call
+    (slrhip_clamp_sample): (what, values as the sensor receives them, Y as given, Y as received); what = 0 kept, 1 clamped, 2 dropped."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, np.float32)
+    out = np.empty_like(v)
+    y_in, y_out = C.c_float(0), C.c_float(0)
+    what = lib.slrhip_clamp_sample(v.size, v.ctypes.data, limit, flags, out.ctypes.data, C.byref(y_in), C.byref(y_out))
+    if what < 0:
+        raise ValueError("clamp_sample: 3 or 16 components")
+    return what, out, np.float32(y_in.value), np.float32(y_out.value)

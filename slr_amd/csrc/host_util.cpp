@@ -9,6 +9,7 @@
 
 #include "../../include/slrhip.h"
 #include "cmf16_table.h"
+#include "pt_clamp.h"
 #include "pt_luminance.h"
 #include "pt_tonemap.h"
 #include "cmf_2deg_table.h"
@@ -262,6 +263,27 @@ float slrhip_sample_luminance(int32_t components, const float* v) {
     float p[4];
     for (uint32_t q = 0; q < 4; ++q) p[q] = slrhip::sampleLuminancePlane(q, v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
     return slrhip::sampleLuminanceOfPlanes(p[0] + p[1], p[2] + p[3]);
+}
+
+// The sample clamp on one sample, as the fold kernel applies it (pt_clamp.h: the same function).
+int slrhip_clamp_sample(int32_t components, const float* in, float limit, uint32_t flags, float* out, float* yIn, float* yOut) {
+    if (!in || !out || (components != 3 && components != 16)) return -1;
+    float a = 0.0f, b = 0.0f;
+    uint32_t what;
+    if (components == 3) {
+        float v[3] = {in[0], in[1], in[2]};
+        what = slrhip::clampSample(v, limit, flags, slrhip::LuminanceRGB(), a, b);
+        std::memcpy(out, v, sizeof(v));
+    }
+    else {
+        float v[16];
+        std::memcpy(v, in, sizeof(v));
+        what = slrhip::clampSample(v, limit, flags, slrhip::LuminanceSpec16(), a, b);
+        std::memcpy(out, v, sizeof(v));
+    }
+    if (yIn) *yIn = a;
+    if (yOut) *yOut = b;
+    return (int)what;
 }
 
 int slrhip_tonemap_bgr8(const float* fb, int32_t width, int32_t height, int32_t components, float scale, uint8_t* dst,

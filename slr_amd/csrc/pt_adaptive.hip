@@ -95,21 +95,30 @@ void launchAdaptiveSelect(const AdaptiveSelect& a, hipStream_t stream) {
 }
 
 // k_fold over a compact window: element e of the window adds into the pixel indexMap[compact pixel of e] of the shard (pt_fold.h).
-// Only with statistics: the adaptive render needs the records.
-template <bool kSpectral>
+// Only with statistics: the adaptive render needs the records.  kClamp: as in k_fold.
+template <bool kClamp, bool kSpectral>
 __global__ __launch_bounds__(256) void k_fold_indexed(PathBuffers pb, uint32_t elems, uint32_t passes, float4* statRecords,
-                                                      const uint32_t* __restrict__ indexMap) {
+                                                      const uint32_t* __restrict__ indexMap, FoldClampArgs<kClamp> clamp) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= elems) return;
-    foldElement<true, kSpectral, true>(pb, e, elems, passes, statRecords, indexMap);
+    foldElement<kClamp, true, kSpectral, true>(pb, e, elems, passes, statRecords, indexMap, clamp);
 }
 
-void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const uint32_t* indexMap, hipStream_t stream) {
+void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const uint32_t* indexMap, const ClampParams& clamp,
+                       hipStream_t stream) {
     const uint32_t elems = rp.numPixels * (rp.spectral ? 4u : 1u);
     if (elems == 0 || rp.sppCount == 0) return;
     const dim3 grid((elems + 255) / 256), block(256);
-    if (rp.spectral) hipLaunchKernelGGL(k_fold_indexed<true>, grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap);
-    else hipLaunchKernelGGL(k_fold_indexed<false>, grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap);
+    if (clamp.records) {
+        FoldClampArgs<true> on;
+        static_cast<ClampParams&>(on) = clamp;
+        if (rp.spectral) hipLaunchKernelGGL((k_fold_indexed<true, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap, on);
+        else hipLaunchKernelGGL((k_fold_indexed<true, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap, on);
+        return;
+    }
+    const FoldClampArgs<false> off;
+    if (rp.spectral) hipLaunchKernelGGL((k_fold_indexed<false, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap, off);
+    else hipLaunchKernelGGL((k_fold_indexed<false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, indexMap, off);
 }
 
 // The mean frame: [H][W][N] = sum / (float)n with n from the pixel's noise record, 0 where n == 0 (dst cleared by the caller:

@@ -239,9 +239,20 @@ __device__ __forceinline__ bool tailModeBegins(const PathBuffers& pb, uint32_t l
 }
 
 void launchResetSlots(const PathBuffers& pb, const RenderParams& rp, bool clearSensor, hipStream_t stream);
+// The sample clamp of a render (slrhip_clamp_begin; pt_clamp.h).  records == nullptr: off.  One record per pixel of the shard:
+// {clamped, dropped (uint32 bits), removed, largest}.
+struct ClampParams {
+    float4* records;
+    float limit;
+    uint32_t flags;               // SLRHIP_CLAMP_* bits
+};
+// ... as the fold kernels take it: nothing at all in the instantiations without a clamp
+template <bool kClamp> struct FoldClampArgs {};
+template <> struct FoldClampArgs<true> : ClampParams {};
 // ImageSensor::add for the window's passes, in pass order: the result window folded into the per-pixel Kahan sums
 // statRecords != nullptr (slrhip_statistics_begin): the instantiation that also updates the per-pixel noise records
-void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, hipStream_t stream);
+// clamp.records != nullptr (slrhip_clamp_begin): the instantiation that puts every sample through clampSample first
+void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const ClampParams& clamp, hipStream_t stream);
 // one wavefront iteration = launchShade(parity) then launchTraceWs(parity)
 void launchShade(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);
 void launchCountSamples(const PathBuffers& pb, const RenderParams& rp, hipStream_t stream);
@@ -314,6 +325,16 @@ void launchStatsResolve(const float4* records, const uint32_t* pixelXY, uint32_t
                         hipStream_t stream);
 // the shard's totals, in double, in a fixed order: partials[statsSummaryBlocks(numPixels)], then *out (both DEVICE memory)
 void launchStatsSummary(const float4* records, uint32_t numPixels, StatsTotals* partials, StatsTotals* out, hipStream_t stream);
+// The same two read-outs of the clamp records (slrhip_resolve_clamp / slrhip_clamp_summary; pt_stats.hip), with the summary's grid.
+struct ClampTotals {                                       // slrhip_clamp_summary's layout (checked in slrhip_api.hip)
+    uint64_t clamped, dropped;
+    double removed;
+    float largest;
+    uint32_t pad;
+};
+void launchClampResolve(const float4* records, const uint32_t* pixelXY, uint32_t numPixels, uint32_t imageWidth, uint32_t channel, float* dst,
+                        hipStream_t stream);
+void launchClampSummary(const float4* records, uint32_t numPixels, ClampTotals* partials, ClampTotals* out, hipStream_t stream);
 
 // Adaptive sampling (slrhip_render_adaptive; pt_adaptive.hip).  The pixels that have not retired are a compact list in ascending
 // shard-pixel order: activeXY (x | y << 16: what a window over the list hands the kernels as PathBuffers::pixelXY) and activeIndex
@@ -337,7 +358,8 @@ struct AdaptiveSelect {
 void launchAdaptiveSelect(const AdaptiveSelect& a, hipStream_t stream);
 // launchFold (with statistics) for a window over a compact list: rp.numPixels = the list's length, pb.fbSum / fbComp and
 // statRecords are the shard's, compact pixel i adds into pixel indexMap[i]
-void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const uint32_t* indexMap, hipStream_t stream);
+void launchFoldIndexed(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const uint32_t* indexMap, const ClampParams& clamp,
+                       hipStream_t stream);
 // the frame as per-pixel means: sum / (float)n with n of the pixel's record, 0 where n == 0 (dst cleared by the caller)
 void launchResolveMean(const PathBuffers& pb, const RenderParams& rp, const float4* records, float* dst, hipStream_t stream);
 

@@ -52,21 +52,32 @@ __global__ __launch_bounds__(kShadeBlock) void k_count_samples(PathBuffers pb, R
 
 // ImageSensor::add for the passes of a finished window, in pass order (+ the noise records with kStats): one thread per float4 of
 // the sensor.  The body is foldElement (pt_fold.h), shared with the indexed instantiations of slrhip_render_adaptive
-// (pt_adaptive.hip); here an element's pixel is its own.
-template <bool kStats, bool kSpectral>
-__global__ __launch_bounds__(256) void k_fold(PathBuffers pb, uint32_t elems, uint32_t passes, float4* statRecords) {
+// (pt_adaptive.hip); here an element's pixel is its own.  kClamp (slrhip_clamp_begin): the samples go through the clamp first; the
+// clamp needs the luminance, so without statistics there is a spectral instantiation of it too.
+template <bool kClamp, bool kStats, bool kSpectral>
+__global__ __launch_bounds__(256) void k_fold(PathBuffers pb, uint32_t elems, uint32_t passes, float4* statRecords, FoldClampArgs<kClamp> clamp) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= elems) return;
-    foldElement<kStats, kSpectral, false>(pb, e, elems, passes, statRecords, nullptr);
+    foldElement<kClamp, kStats, kSpectral, false>(pb, e, elems, passes, statRecords, nullptr, clamp);
 }
 
-void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, hipStream_t stream) {
+void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const ClampParams& clamp, hipStream_t stream) {
     const uint32_t elems = rp.numPixels * (rp.spectral ? 4u : 1u);
     if (elems == 0 || rp.sppCount == 0) return;
     const dim3 grid((elems + 255) / 256), block(256);
-    if (!statRecords) hipLaunchKernelGGL((k_fold<false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords);
-    else if (rp.spectral) hipLaunchKernelGGL((k_fold<true, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords);
-    else hipLaunchKernelGGL((k_fold<true, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords);
+    if (clamp.records) {
+        FoldClampArgs<true> on;
+        static_cast<ClampParams&>(on) = clamp;
+        if (!statRecords && rp.spectral) hipLaunchKernelGGL((k_fold<true, false, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, on);
+        else if (!statRecords) hipLaunchKernelGGL((k_fold<true, false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, on);
+        else if (rp.spectral) hipLaunchKernelGGL((k_fold<true, true, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, on);
+        else hipLaunchKernelGGL((k_fold<true, true, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, on);
+        return;
+    }
+    const FoldClampArgs<false> off;
+    if (!statRecords) hipLaunchKernelGGL((k_fold<false, false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
+    else if (rp.spectral) hipLaunchKernelGGL((k_fold<false, true, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
+    else hipLaunchKernelGGL((k_fold<false, true, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
 }
 void launchCountSamples(const PathBuffers& pb, const RenderParams& rp, hipStream_t stream) {
     if (rp.numSlots == 0) return;

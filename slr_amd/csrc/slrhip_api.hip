@@ -20,6 +20,7 @@
 
 #include "../../include/slrhip.h"
 #include "bvh.h"
+#include "pt_clamp.h"
 #include "pt_kernels.h"
 #include "render_plan.h"
 #include "scene_prep.h"
@@ -174,6 +175,13 @@ struct slrhip_ctx {
     DevArray<StatsTotals> statPartials, statTotals;      // the summary's first-stage partials and its result
     bool statsOn = false;                         // this render folds with the statistics instantiation of k_fold
     bool statsClear = false;                      // the records still hold an earlier render's: cleared in stream order before their first use
+    // the sample clamp (slrhip_clamp_begin): allocated by the first enabling call, kept for later renders
+    DevArray<float4> clampRecords;                // {clamped, dropped (uint32 bits), removed, largest} per pixel of the shard, updated by k_fold
+    DevArray<ClampTotals> clampPartials, clampTotals;     // the summary's first-stage partials and its result
+    bool clampOn = false;                         // this render folds with the clamp instantiation of k_fold
+    bool clampClear = false;                      // as statsClear
+    float clampLimit = 0.0f;
+    uint32_t clampFlags = 0;
     // adaptive sampling (slrhip_render_adaptive): the list buffers are allocated by the first adaptive call and kept for later renders
     DevArray<uint32_t> adaptXY[2], adaptIndex[2]; // the active list (pt_kernels.h AdaptiveSelect), two pairs that alternate
     DevArray<uint32_t> adaptOffsets, adaptCount;  // the select's workgroup offsets; the new list's length (read back once per block)
@@ -479,6 +487,8 @@ struct ActiveWindow {
 // the buffer table: ctx->params and ctx->buffers stay the shard's (the resolves, the statistics, the feature passes and
 // slrhip_camera_rays read them).  `active` (slrhip_render_adaptive): the window is over that list — its length as the pixel count, its
 // xy as the pixel list, its index as the map of the fold; the slots, the queues' owners and the tail bound stay the shard's.
+static ClampParams clampParams(const slrhip_ctx* ctx) { return ClampParams{ctx->clampOn ? ctx->clampRecords.ptr : nullptr, ctx->clampLimit, ctx->clampFlags}; }
+
 static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, hipStream_t stream, const ActiveWindow* active = nullptr) {
     RenderParams rp = ctx->params;
     PathBuffers pb = ctx->buffers;
@@ -554,8 +564,9 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
     }
     ctx->iterations += it;
     launchCountSamples(pb, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
-    if (active) launchFoldIndexed(pb, rp, ctx->statRecords.ptr, active->index, s);       // the same, scattered to the list's pixels of the shard
-    else launchFold(pb, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, s);       // sensor->add, in pass order (+ the noise records)
+    const ClampParams clamp = clampParams(ctx);                                          // slrhip_clamp_begin: every sample through the clamp first
+    if (active) launchFoldIndexed(pb, rp, ctx->statRecords.ptr, active->index, clamp, s);       // the same, scattered to the list's pixels of the shard
+    else launchFold(pb, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, clamp, s);       // sensor->add, in pass order (+ the noise records)
     HIP_TRY(hipGetLastError());
     const int rc = checkWindow(ctx, rp.workItems, s);
     if (rc == SLRHIP_OK && iterLogPath) writeIterationLog(iterLogPath, rp, iterLog);
@@ -564,6 +575,10 @@ static int renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, h
 
 // The noise records of an earlier render are cleared before their first use in this one, in order on the stream of that use.
 static int clearStatistics(slrhip_ctx* ctx, hipStream_t stream) {
+    if (ctx->clampOn && ctx->clampClear) {         // ... and the clamp records, which every statistics-aware call may touch as well
+        HIP_TRY(hipMemsetAsync(ctx->clampRecords.ptr, 0, std::max<size_t>(ctx->params.numPixels, 1u) * sizeof(float4), stream));
+        ctx->clampClear = false;
+    }
     if (!ctx->statsOn || !ctx->statsClear) return SLRHIP_OK;
     HIP_TRY(hipMemsetAsync(ctx->statRecords.ptr, 0, std::max<size_t>(ctx->params.numPixels, 1u) * sizeof(float4), stream));
     ctx->statsClear = false;
@@ -579,6 +594,9 @@ static uint64_t resultWindowBudget() {
 
 static_assert(sizeof(StatsTotals) == sizeof(struct slrhip_statistics_summary) && offsetof(StatsTotals, sumVarianceOfMean) == offsetof(struct slrhip_statistics_summary, sum_variance_of_mean) &&
               offsetof(StatsTotals, maxSample) == offsetof(struct slrhip_statistics_summary, max_sample), "StatsTotals is slrhip_statistics_summary's layout");
+static_assert(sizeof(ClampTotals) == sizeof(struct slrhip_clamp_summary) && offsetof(ClampTotals, removed) == offsetof(struct slrhip_clamp_summary, removed) &&
+              offsetof(ClampTotals, largest) == offsetof(struct slrhip_clamp_summary, largest), "ClampTotals is slrhip_clamp_summary's layout");
+static_assert(kClampDropNonFinite == SLRHIP_CLAMP_DROP_NONFINITE, "pt_clamp.h's flag is the ABI's");
 
 extern "C" {
 
@@ -689,6 +707,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->featReady = false; ctx->featChannels = 0; ctx->featPassEnd = 0;      // the feature accumulation restarts (its arrays are kept for reuse)
     ctx->featErrorReady = false; ctx->albReady = false; ctx->albPasses = 0;   // ... and the albedo accumulation and the error word they share
     ctx->statsOn = false; ctx->statsClear = true;                             // statistics are per render (slrhip_statistics_begin); the records are kept, stale
+    ctx->clampOn = false; ctx->clampClear = true;                             // ... and so is the clamp (slrhip_clamp_begin)
     ctx->activePixels = plan.numPixels; ctx->activeList = -1;                 // every pixel is active again (slrhip_render_adaptive)
     ctx->haveRender = true;
     return SLRHIP_OK;
@@ -1194,6 +1213,112 @@ int slrhip_render_until(slrhip_ctx* ctx, uint32_t sppBegin, const slrhip_noise_t
         // "at least 2 passes": the variance of one sample is not defined (the channels are 0 then, which would read as "no noise")
         if (totals.samples >= 2 * totals.pixels && noiseMetric(totals, target->metric) <= (double)target->target) break;
     }
+    return SLRHIP_OK;
+}
+
+// ---- the sample clamp (slrhip_clamp_begin / slrhip_resolve_clamp / slrhip_clamp_summary; the rule: pt_clamp.h) ----
+int slrhip_clamp_begin(slrhip_ctx* ctx, const slrhip_clamp_desc* d) {
+    if (!ctx || !d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_begin: null argument");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_clamp_begin: call slrhip_render_begin first");
+    if (!ctx->firstRenderCall) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_begin: this render has begun (call it before the first slrhip_render after slrhip_render_begin)");
+    if (!(d->limit > 0.0f)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_begin: the limit must be > 0 (and not NaN); INFINITY clamps nothing");
+    if (d->flags & ~SLRHIP_CLAMP_DROP_NONFINITE) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_begin: unknown flag bits");
+    if (d->reserved[0] || d->reserved[1]) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_begin: reserved must be 0");
+    if (!ctx->clampOn) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const uint32_t pixels = ctx->params.numPixels;
+        hipError_t e = ctx->clampRecords.alloc(pixels);
+        if (e == hipSuccess) e = ctx->clampPartials.alloc(statsSummaryBlocks(pixels));
+        if (e == hipSuccess) e = ctx->clampTotals.alloc(1);
+        if (e != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_clamp_begin: allocating the records: ") + hipGetErrorString(e));
+    }
+    ctx->clampLimit = d->limit; ctx->clampFlags = d->flags;
+    ctx->clampOn = true; ctx->clampClear = true;
+    return SLRHIP_OK;
+}
+
+static int checkClamp(slrhip_ctx* ctx, const char* what) {
+    const std::string w(what);
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": null context");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, w + ": call slrhip_render_begin first");
+    if (!ctx->clampOn) return fail(SLRHIP_ERR_INVALID_ARGUMENT, w + ": the clamp is off (slrhip_clamp_begin after slrhip_render_begin switches it on)");
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_clamp(slrhip_ctx* ctx, uint32_t channel, float* deviceDst, size_t numFloats, void* streamPtr) {
+    if (const int rc = checkClamp(ctx, "slrhip_resolve_clamp")) return rc;
+    if (channel == 0 || (channel & (channel - 1u)) || (channel & ~SLRHIP_CLAMP_ALL))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_clamp: `channel` must be one SLRHIP_CLAMP_* bit");
+    if (!deviceDst || ((uintptr_t)deviceDst & 3u)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_clamp: null or misaligned destination (4 bytes)");
+    const RenderParams& rp = ctx->params;
+    const size_t need = (size_t)rp.imageWidth * rp.imageHeight;
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_clamp: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (const int rc = clearStatistics(ctx, s)) return rc;
+    HIP_TRY(hipMemsetAsync(deviceDst, 0, need * sizeof(float), s));
+    launchClampResolve(ctx->clampRecords.ptr, ctx->pixelXY.ptr, rp.numPixels, rp.imageWidth, channel, deviceDst, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_clamp(slrhip_ctx* ctx, uint32_t channel, float* hostDst, size_t numFloats) {
+    if (const int rc = checkClamp(ctx, "slrhip_read_clamp")) return rc;
+    if (!hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_clamp: null destination");
+    const size_t need = (size_t)ctx->params.imageWidth * ctx->params.imageHeight;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->resolveScratch.alloc(need));
+    HIP_TRY(hipDeviceSynchronize());                   // renders queued on any stream of the caller's
+    if (const int rc = slrhip_resolve_clamp(ctx, channel, ctx->resolveScratch.ptr, numFloats, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hostDst, ctx->resolveScratch.ptr, need * sizeof(float), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+int slrhip_clamp_summary(slrhip_ctx* ctx, struct slrhip_clamp_summary* hostOut, void* streamPtr) {
+    if (const int rc = checkClamp(ctx, "slrhip_clamp_summary")) return rc;
+    if (!hostOut) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_clamp_summary: null destination");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (const int rc = clearStatistics(ctx, s)) return rc;
+    launchClampSummary(ctx->clampRecords.ptr, ctx->params.numPixels, ctx->clampPartials.ptr, ctx->clampTotals.ptr, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hostOut, ctx->clampTotals.ptr, sizeof(*hostOut), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    hostOut->reserved = 0;
+    return SLRHIP_OK;
+}
+
+// slrhip_debug.h: the caller's samples as a result window, through the fold of the context's current state.
+int slrhip_debug_fold(slrhip_ctx* ctx, const float* hostSamples, uint32_t passes) {
+    if (!ctx || !hostSamples) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_fold: null argument");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_debug_fold: call slrhip_render_begin first");
+    if (passes < 1 || passes > 64) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_fold: 1 .. 64 passes");
+    HIP_TRY(hipSetDevice(ctx->device));
+    RenderParams rp = ctx->params;
+    if (rp.numSlots == 0) { ctx->firstRenderCall = false; return SLRHIP_OK; }       // an empty shard
+    if (const int rc = clearStatistics(ctx, nullptr)) return rc;
+    if (ctx->firstRenderCall)                                                        // clears the sensor, as a render call of zero passes does
+        if (const int rc = renderWindow(ctx, 0, 0, nullptr)) return rc;
+    const uint32_t planes = rp.spectral ? 4u : 1u, comps = rp.spectral ? 16u : 3u;
+    const size_t elems = (size_t)rp.numPixels * planes;
+    std::vector<uint32_t> xy(rp.numPixels);
+    HIP_TRY(hipMemcpy(xy.data(), ctx->pixelXY.ptr, xy.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<float4> window((size_t)passes * elems);
+    for (uint32_t p = 0; p < passes; ++p)
+        for (uint32_t i = 0; i < rp.numPixels; ++i) {
+            const float* src = hostSamples + (((size_t)p * rp.imageHeight + (xy[i] >> 16)) * rp.imageWidth + (xy[i] & 0xFFFFu)) * comps;
+            float4* dst = window.data() + (size_t)p * elems + (size_t)i * planes;
+            if (rp.spectral) for (uint32_t q = 0; q < 4; ++q) dst[q] = make_float4(src[4 * q], src[4 * q + 1], src[4 * q + 2], src[4 * q + 3]);
+            else dst[0] = make_float4(src[0], src[1], src[2], 0.0f);
+        }
+    HIP_TRY(ctx->results.alloc(window.size()));
+    ctx->buffers.results = ctx->results.ptr;
+    HIP_TRY(hipMemcpy(ctx->results.ptr, window.data(), window.size() * sizeof(float4), hipMemcpyHostToDevice));
+    rp.sppBegin = 0; rp.sppCount = passes;
+    launchFold(ctx->buffers, rp, ctx->statsOn ? ctx->statRecords.ptr : nullptr, clampParams(ctx), nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return SLRHIP_OK;
 }
 

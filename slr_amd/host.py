@@ -157,7 +157,30 @@ def build_parser():
     ap.add_argument("--albedo", default=None, metavar="FILE.npy", help="write the mean first-hit albedo [height, width, components]")
     ap.add_argument("--device-tonemap", action="store_true",
                     help="tone-map every BMP on the device and read back only the 8-bit image, not the float frame")
+    ap.add_argument("--clamp", type=float, default=None, metavar="L",
+                    help="scale a sample whose luminance (un-normalised: brightness and sample count not applied) exceeds L down to L")
+    ap.add_argument("--drop-nonfinite", action="store_true", help="replace a sample whose luminance is NaN or infinite by zero")
+    ap.add_argument("--clamp-map", default=None, metavar="FILE.npy",
+                    help="with --clamp or --drop-nonfinite: write the per-pixel clamp records [4, height, width]: clamped, dropped, removed, largest")
     return ap
+
+
+def clamp_begin(ctx, args):
+    """--clamp / --drop-nonfinite: Context.clamp_begin for the render that has just begun.  True if the clamp is on."""
+    if args.clamp is None and not args.drop_nonfinite:
+        return False
+    ctx.clamp_begin(float("inf") if args.clamp is None else args.clamp, args.drop_nonfinite)
+    return True
+
+
+def report_clamp(ctx, args):
+    """The clamp's summary line and, with --clamp-map, the four record channels."""
+    s = ctx.clamp_summary()
+    print("clamp %g%s: %u samples clamped, %u dropped, luminance removed %g, largest clamped sample %g"
+          % (float("inf") if args.clamp is None else args.clamp, " (non-finite samples dropped)" if args.drop_nonfinite else "",
+             s["clamped"], s["dropped"], s["removed"], s["largest"]), flush=True)
+    if args.clamp_map:
+        np.save(args.clamp_map, np.stack([ctx.clamp(c) for c in sorted(abi.CLAMP_CHANNELS)]))
 
 
 def main(argv=None):
@@ -175,6 +198,10 @@ def main(argv=None):
         ap.error("--denoise takes 1 .. 8 iterations")
     if args.demodulate and args.denoise is None:
         ap.error("--demodulate goes with --denoise")
+    if args.clamp is not None and not args.clamp > 0:
+        ap.error("--clamp takes a limit > 0")
+    if args.clamp_map and args.clamp is None and not args.drop_nonfinite:
+        ap.error("--clamp-map goes with --clamp or --drop-nonfinite")
 
     try:
         scene, settings, renderer = scene_language.load_scene(args.scene)
@@ -196,6 +223,7 @@ def main(argv=None):
     ctx = binding.Context(device=args.device, mode=abi.MODE_SPECTRAL if args.spectral else abi.MODE_RGB)
     ctx.upload_scene(scene)
     ctx.render_begin(st)
+    clamped = clamp_begin(ctx, args)                                         # before the first render call, like the statistics
     cam = scene.camera
     sensitivity = cam.sensitivity if cam.sensitivity > 0 else float(np.float32(1.0 / (np.pi * float(np.float32(cam.lens_radius)) ** 2))) if cam.lens_radius > 0 else 1.0
     start = time.time()
@@ -218,6 +246,8 @@ def main(argv=None):
             print("%u samples: %s, %g[s]" % (export, name, time.time() - start), flush=True)
             img += 1
             export += export
+    if clamped:
+        report_clamp(ctx, args)
     if feature_dir is not None:
         os.makedirs(feature_dir, exist_ok=True)
         # one channel set per render: with --denoise the guides ride with the channels asked for
