@@ -159,6 +159,41 @@ def _check(lib, rc, what):
         raise SlrHipError("%s failed (%d): %s" % (what, rc, lib.slrhip_last_error_string().decode()))
 
 
+class DeviceBlocks:
+    """hipMalloc'ed blocks for staging host arrays through a call on device pointers, from the HIP runtime the library is bound to:
+    `with DeviceBlocks() as dev:` frees every block on the way out.  Addresses are plain integers."""
+
+    def __init__(self):
+        self.hip, self.blocks = _hip_runtime(), []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.blocks:
+            self.hip.hipFree(p)
+        self.blocks = []
+
+    def alloc(self, nbytes):
+        p = C.c_void_p()
+        _hip_check(self.hip.hipMalloc(C.byref(p), max(nbytes, 16)), "hipMalloc")
+        self.blocks.append(p.value)
+        return p.value
+
+    def put(self, array):
+        """A block holding a copy of `array`."""
+        a = np.ascontiguousarray(array)
+        p = self.alloc(a.nbytes)
+        _hip_check(self.hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
+        return p
+
+    def get(self, ptr, shape, dtype=np.float32):
+        """The device memory at `ptr` (anywhere inside a block) as a new numpy array."""
+        out = np.empty(shape, dtype)
+        _hip_check(self.hip.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2), "hipMemcpy")
+        return out
+
+
 class Context:
     """One rendering context on one GPU (slrhip_ctx)."""
 
@@ -197,10 +232,24 @@ class Context:
                "slrhip_resolve_framebuffer")
 
     def read_framebuffer(self):
-        h, w = self.settings.image_height, self.settings.image_width
-        fb = np.zeros((h, w, self.components), np.float32)
-        _check(self.lib, self.lib.slrhip_read_framebuffer(self.handle, fb.ctypes.data, fb.size), "slrhip_read_framebuffer")
+        return self._read_frame("slrhip_read_framebuffer")
+
+    def _read_frame(self, symbol, *more):
+        """A [height, width, components] frame through slrhip_read_framebuffer, _mean or slrhip_read_albedo."""
+        fb = np.zeros((self.settings.image_height, self.settings.image_width, self.components), np.float32)
+        _check(self.lib, getattr(self.lib, symbol)(self.handle, fb.ctypes.data, fb.size, *more), symbol)
         return fb
+
+    def _read_plane(self, symbol, channel):
+        """One [height, width] channel through slrhip_read_statistics or slrhip_read_clamp."""
+        out = np.empty((self.settings.image_height, self.settings.image_width), np.float32)
+        _check(self.lib, getattr(self.lib, symbol)(self.handle, channel, out.ctypes.data, out.size), symbol)
+        return out
+
+    def _summary(self, symbol, summary, stream):
+        """The fields of a slrhip_*_summary struct as a dict."""
+        _check(self.lib, getattr(self.lib, symbol)(self.handle, C.byref(summary), self._stream_handle(stream)), symbol)
+        return self._summary_dict(summary)
 
     def synchronize(self):
         _check(self.lib, self.lib.slrhip_synchronize(self.handle), "slrhip_synchronize")
@@ -248,22 +297,12 @@ class Context:
         a = rays.view(np.float32) if rays.dtype == abi.ray_dtype else rays
         a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8)
         n = len(a)
-        hip = _hip_runtime()
-        host = {name: np.empty(shape(n), dt) for name, shape, dt in outs}
-        ptrs = {}
-        try:
-            for name, arr in [("rays", a)] + list(host.items()):
-                p = C.c_void_p()
-                _hip_check(hip.hipMalloc(C.byref(p), max(arr.nbytes, 16)), "hipMalloc")
-                ptrs[name] = p.value
-            _hip_check(hip.hipMemcpy(ptrs["rays"], a.ctypes.data, a.nbytes, 1), "hipMemcpy")
-            call(ptrs["rays"], n, {k: ptrs[k] for k in host}, None)
+        shapes = {name: (shape(n), np.dtype(dt)) for name, shape, dt in outs}
+        with DeviceBlocks() as dev:
+            ptrs = {name: dev.alloc(int(np.prod(sh)) * dt.itemsize) for name, (sh, dt) in shapes.items()}
+            call(dev.put(a), n, ptrs, None)
             bits = self.query_status(0)
-            for k, arr in host.items():
-                _hip_check(hip.hipMemcpy(arr.ctypes.data, ptrs[k], arr.nbytes, 2), "hipMemcpy")
-        finally:
-            for p in ptrs.values():
-                hip.hipFree(p)
+            host = {name: dev.get(ptrs[name], sh, dt) for name, (sh, dt) in shapes.items()}
         if bits:
             raise SlrHipError("ray query: the query error word is 0x%x (a traversal gave up)" % bits)
         return tuple(host[name] for name, _, _ in outs) if len(outs) > 1 else host[outs[0][0]]
@@ -354,11 +393,8 @@ class Context:
     def albedo(self):
         """(sums [height, width, components] float32, passes): the per-pixel albedo sums in pass order, zeros outside the shard, and the
         passes accumulated; sums / passes is the mean albedo.  Synchronises, and raises if the feature error word is set."""
-        h, w = self.settings.image_height, self.settings.image_width
-        out = np.empty((h, w, self.components), np.float32)
         passes = C.c_uint32(0)
-        _check(self.lib, self.lib.slrhip_read_albedo(self.handle, out.ctypes.data, out.size, C.byref(passes)), "slrhip_read_albedo")
-        return out, passes.value
+        return self._read_frame("slrhip_read_albedo", C.byref(passes)), passes.value
 
     # ---- albedo demodulation (slrhip_modulate): a pure function of device buffers ----
     def modulate_into(self, width, height, components, op, color, albedo, albedo_passes, output, variance=None, output_variance=None,
@@ -380,30 +416,13 @@ class Context:
             variance = np.ascontiguousarray(variance, np.float32)
             if variance.shape != (h, w):
                 raise ValueError("variance: shape %r expected" % ((h, w),))
-        hip = _hip_runtime()
-        ptrs = []
-
-        def put(a):
-            p = C.c_void_p()
-            _hip_check(hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
-            ptrs.append(p.value)
-            _hip_check(hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
-            return p.value
-        try:
-            pc, pa = put(color), put(albedo)
-            pv = put(variance) if variance is not None else None
+        with DeviceBlocks() as dev:
+            pc, pa = dev.put(color), dev.put(albedo)
+            pv = dev.put(variance) if variance is not None else None
             self.modulate_into(w, h, comps, op, pc, pa, passes, pc, pv, pv, floor)      # in place
             self.synchronize()
-            out = np.empty_like(color)
-            _hip_check(hip.hipMemcpy(out.ctypes.data, pc, out.nbytes, 2), "hipMemcpy")
-            if variance is None:
-                return out
-            out_v = np.empty_like(variance)
-            _hip_check(hip.hipMemcpy(out_v.ctypes.data, pv, out_v.nbytes, 2), "hipMemcpy")
-            return out, out_v
-        finally:
-            for p in ptrs:
-                hip.hipFree(p)
+            out = dev.get(pc, color.shape)
+            return out if variance is None else (out, dev.get(pv, variance.shape))
 
     def camera_rays(self, pass_, device=False, stream=None):
         """The camera rays of sample `pass_` of every pixel of the shard (slrhip_camera_rays): (rows, pixel_xy), rows [n, 8] float32
@@ -421,21 +440,11 @@ class Context:
                 _check(self.lib, self.lib.slrhip_camera_rays(self.handle, pass_, rows.data_ptr(), xy.data_ptr(), n, C.byref(count), s.cuda_stream),
                        "slrhip_camera_rays")
             return rows, xy
-        rows, xy = np.empty((n, 8), np.float32), np.empty((n,), np.uint32)
-        hip = _hip_runtime()
-        pr, px = C.c_void_p(), C.c_void_p()
-        try:
-            _hip_check(hip.hipMalloc(C.byref(pr), max(rows.nbytes, 16)), "hipMalloc")
-            _hip_check(hip.hipMalloc(C.byref(px), max(xy.nbytes, 16)), "hipMalloc")
-            _check(self.lib, self.lib.slrhip_camera_rays(self.handle, pass_, pr.value, px.value, n, C.byref(count), None), "slrhip_camera_rays")
+        with DeviceBlocks() as dev:
+            pr, px = dev.alloc(32 * n), dev.alloc(4 * n)
+            _check(self.lib, self.lib.slrhip_camera_rays(self.handle, pass_, pr, px, n, C.byref(count), None), "slrhip_camera_rays")
             self.synchronize()
-            _hip_check(hip.hipMemcpy(rows.ctypes.data, pr.value, rows.nbytes, 2), "hipMemcpy")
-            _hip_check(hip.hipMemcpy(xy.ctypes.data, px.value, xy.nbytes, 2), "hipMemcpy")
-        finally:
-            for p in (pr, px):
-                if p.value:
-                    hip.hipFree(p)
-        return rows, xy
+            return dev.get(pr, (n, 8)), dev.get(px, (n,), np.uint32)
 
     # ---- per-pixel noise statistics and rendering to a noise target (slrhip_statistics_begin ... slrhip_render_until) ----
     def statistics_begin(self):
@@ -449,21 +458,16 @@ class Context:
 
     def statistics(self, channel):
         """One abi.STATISTICS_* channel as a numpy array [height, width] float32, zeros outside the shard.  Synchronises."""
-        h, w = self.settings.image_height, self.settings.image_width
-        out = np.empty((h, w), np.float32)
-        _check(self.lib, self.lib.slrhip_read_statistics(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_statistics")
-        return out
+        return self._read_plane("slrhip_read_statistics", channel)
 
     @staticmethod
     def _summary_dict(s):
-        return {name: getattr(s, name) for name, _ in abi.StatisticsSummary._fields_ if name != "reserved"}
+        return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
 
     def statistics_summary(self, stream=None):
         """The shard's totals (slrhip_statistics_summary) as a dict; waits for `stream` only.  Dicts of shards add field by
         field, except max_sample (take the larger); abi.noise_metric evaluates the stop check on one."""
-        s = abi.StatisticsSummary()
-        _check(self.lib, self.lib.slrhip_statistics_summary(self.handle, C.byref(s), self._stream_handle(stream)), "slrhip_statistics_summary")
-        return self._summary_dict(s)
+        return self._summary("slrhip_statistics_summary", abi.StatisticsSummary(), stream)
 
     def render_until(self, metric, target, step, spp_max, spp_begin=0, stream=None):
         """Renders blocks of `step` passes from `spp_begin` until abi.noise_metric(summary, metric) <= target (and every pixel has
@@ -489,17 +493,12 @@ class Context:
 
     def clamp(self, channel):
         """One abi.CLAMP_* channel as a numpy array [height, width] float32, zeros outside the shard.  Synchronises."""
-        h, w = self.settings.image_height, self.settings.image_width
-        out = np.empty((h, w), np.float32)
-        _check(self.lib, self.lib.slrhip_read_clamp(self.handle, channel, out.ctypes.data, out.size), "slrhip_read_clamp")
-        return out
+        return self._read_plane("slrhip_read_clamp", channel)
 
     def clamp_summary(self, stream=None):
         """The shard's totals (slrhip_clamp_summary) as a dict; waits for `stream` only.  Dicts of shards add field by field,
         except `largest` (take the larger)."""
-        s = abi.ClampSummary()
-        _check(self.lib, self.lib.slrhip_clamp_summary(self.handle, C.byref(s), self._stream_handle(stream)), "slrhip_clamp_summary")
-        return {name: getattr(s, name) for name, _ in abi.ClampSummary._fields_ if name != "reserved"}
+        return self._summary("slrhip_clamp_summary", abi.ClampSummary(), stream)
 
     def debug_fold(self, samples):
         """Diagnostic (slrhip_debug_fold): `samples` [passes, height, width, components] float32 through the fold of the context's
@@ -530,10 +529,7 @@ class Context:
     def read_framebuffer_mean(self):
         """The frame as per-pixel means [height, width, components]: sum / count with the count of the pixel's noise record, 0
         where no sample was rendered and outside the shard.  Needs statistics_begin(); synchronises."""
-        h, w = self.settings.image_height, self.settings.image_width
-        fb = np.zeros((h, w, self.components), np.float32)
-        _check(self.lib, self.lib.slrhip_read_framebuffer_mean(self.handle, fb.ctypes.data, fb.size), "slrhip_read_framebuffer_mean")
-        return fb
+        return self._read_frame("slrhip_read_framebuffer_mean")
 
     def adaptive_active(self, stream=None):
         """Pixels of the shard that have not retired since render_begin (slrhip_adaptive_active)."""
@@ -559,42 +555,29 @@ class Context:
         multiplied with it afterwards (slrhip_modulate, in place)."""
         h, w, comps = shape
         sizes = {"color": h * w * comps, "variance": h * w, "normal": h * w * 3, "distance": h * w, "coverage": h * w}
-        hip = _hip_runtime()
-        ptrs = {}
-
-        def malloc(name, floats):
-            p = C.c_void_p()
-            _hip_check(hip.hipMalloc(C.byref(p), max(4 * floats, 16)), "hipMalloc")
-            ptrs[name] = p.value
-            return p.value
-        out, out_v = np.empty((h, w, comps), np.float32), np.empty((h, w), np.float32)
-        try:
-            given = {name: malloc(name, n) for name, n in sizes.items() if fill(name, None)}
+        with DeviceBlocks() as dev:
+            given = {name: dev.alloc(4 * n) for name, n in sizes.items() if fill(name, None)}
             for name, p in given.items():
                 fill(name, p)
             if demodulate is not None:
                 if want_variance and "variance" not in given:
                     raise ValueError("demodulate with want_variance needs a variance input: the filtered variance could not be multiplied back")
-                albedo = malloc("albedo", out.size)
-                passes = self.albedo_into(albedo, out.size)
+                albedo = dev.alloc(4 * sizes["color"])
+                passes = self.albedo_into(albedo, sizes["color"])
                 self.modulate_into(w, h, comps, abi.MODULATE_DIVIDE, given["color"], albedo, passes, given["color"], given.get("variance"),
                                    given.get("variance"), demodulate)
-            self.denoise_into(w, h, comps, color=given["color"], output=malloc("output", out.size),
-                              output_variance=malloc("output_variance", out_v.size) if want_variance else None,
+            output = dev.alloc(4 * sizes["color"])
+            output_variance = dev.alloc(4 * h * w) if want_variance else None
+            self.denoise_into(w, h, comps, color=given["color"], output=output, output_variance=output_variance,
                               **{k: given.get(k) for k in ("variance", "normal", "distance", "coverage")}, **params)
             if demodulate is not None:
-                pv = ptrs.get("output_variance") if given.get("variance") else None
-                self.modulate_into(w, h, comps, abi.MODULATE_MULTIPLY, ptrs["output"], albedo, passes, ptrs["output"], pv, pv, demodulate)
+                pv = output_variance if given.get("variance") else None
+                self.modulate_into(w, h, comps, abi.MODULATE_MULTIPLY, output, albedo, passes, output, pv, pv, demodulate)
             if image is not None:
-                return self._tonemap_staged(ptrs["output"], w, h, comps, *image)
+                return self._tonemap_staged(output, w, h, comps, *image)
             self.synchronize()
-            _hip_check(hip.hipMemcpy(out.ctypes.data, ptrs["output"], out.nbytes, 2), "hipMemcpy")
-            if want_variance:
-                _hip_check(hip.hipMemcpy(out_v.ctypes.data, ptrs["output_variance"], out_v.nbytes, 2), "hipMemcpy")
-        finally:
-            for p in ptrs.values():
-                hip.hipFree(p)
-        return (out, out_v) if want_variance else out
+            out = dev.get(output, (h, w, comps))
+            return (out, dev.get(output_variance, (h, w))) if want_variance else out
 
     def denoise(self, color, variance=None, normal=None, distance=None, coverage=None, iterations=5, sigma_luminance=4.0,
                 sigma_distance=abi.DENOISE_SIGMA_DISTANCE, normal_power_log2=7, want_variance=False):
@@ -678,16 +661,12 @@ class Context:
     def _tonemap_staged(self, color_ptr, width, height, components, scale, format):
         """The image of the device floats at color_ptr as a numpy uint8 array: hipMalloc the image, tone-map on the null stream,
         copy the 8-bit rows back."""
-        hip = _hip_runtime()
-        out = np.empty(self.lib.slrhip_tonemap_bytes(width, height, format), np.uint8)
-        p = C.c_void_p()
-        _hip_check(hip.hipMalloc(C.byref(p), max(out.nbytes, 16)), "hipMalloc")
-        try:
-            self.tonemap_into(width, height, components, color_ptr, p.value, out.nbytes, scale, format)
+        size = self.lib.slrhip_tonemap_bytes(width, height, format)
+        with DeviceBlocks() as dev:
+            p = dev.alloc(size)
+            self.tonemap_into(width, height, components, color_ptr, p, size, scale, format)
             self.synchronize()
-            _hip_check(hip.hipMemcpy(out.ctypes.data, p.value, out.nbytes, 2), "hipMemcpy")
-        finally:
-            hip.hipFree(p)
+            out = dev.get(p, (size,), np.uint8)
         return out.reshape(height, width, 4) if format == abi.IMAGE_RGBA8 else out
 
     def frame_image(self, scale, mean=False, format=abi.IMAGE_BGR8_BMP):
@@ -699,14 +678,10 @@ class Context:
             raise SlrHipError("frame_image: call render_begin first")
         h, w = self.settings.image_height, self.settings.image_width
         floats = h * w * self.components
-        hip = _hip_runtime()
-        p = C.c_void_p()
-        _hip_check(hip.hipMalloc(C.byref(p), 4 * floats), "hipMalloc")
-        try:
-            (self.mean_into if mean else self.resolve_into)(p.value, floats)
-            return self._tonemap_staged(p.value, w, h, self.components, scale, format)
-        finally:
-            hip.hipFree(p)
+        with DeviceBlocks() as dev:
+            p = dev.alloc(4 * floats)
+            (self.mean_into if mean else self.resolve_into)(p, floats)
+            return self._tonemap_staged(p, w, h, self.components, scale, format)
 
     def bsdf_queries(self, material, queries, wl_offset=0.5, u_lambda=0.5):
         """Function-level BSDF queries (slrhip_bsdf_queries): queries [n][12] -> [n][6 + 2C]."""

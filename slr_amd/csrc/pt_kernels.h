@@ -1,4 +1,4 @@
-// pt_kernels.h — launch interface between the C-ABI layer (slrhip_api.hip) and the kernels.
+// pt_kernels.h — launch interface between the C-ABI layer (slrhip_api.hip and the slrhip_*.hip beside it) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -313,28 +313,28 @@ void launchModulate(const slrhip_modulate_desc& d, hipStream_t stream);
 // pass order: {mean, M2, n (uint32 bits), max} of the samples' luminance (float32 Welford).
 static const uint32_t kStatsBlock = 256;                   // threads per block of the summary's first stage
 static const uint32_t kStatsPixelsPerThread = 16;          // a block reduces kStatsBlock x kStatsPixelsPerThread consecutive pixels
-struct StatsTotals {                                       // slrhip_statistics_summary's layout (checked in slrhip_api.hip)
+struct StatsTotals {                                       // slrhip_statistics_summary's layout (checked in slrhip_buffers.hip)
     uint64_t pixels, samples;
     double sumMean, sumMeanSq, sumVarianceOfMean;
     float maxSample;
     uint32_t pad;
 };
 inline uint32_t statsSummaryBlocks(uint32_t numPixels) { return (numPixels + kStatsBlock * kStatsPixelsPerThread - 1) / (kStatsBlock * kStatsPixelsPerThread); }
-// one SLRHIP_STATISTICS_* channel as [height][width] floats (dst cleared by the caller: pixels outside the shard stay 0)
-void launchStatsResolve(const float4* records, const uint32_t* pixelXY, uint32_t numPixels, uint32_t imageWidth, uint32_t channel, float* dst,
-                        hipStream_t stream);
-// the shard's totals, in double, in a fixed order: partials[statsSummaryBlocks(numPixels)], then *out (both DEVICE memory)
-void launchStatsSummary(const float4* records, uint32_t numPixels, StatsTotals* partials, StatsTotals* out, hipStream_t stream);
-// The same two read-outs of the clamp records (slrhip_resolve_clamp / slrhip_clamp_summary; pt_stats.hip), with the summary's grid.
-struct ClampTotals {                                       // slrhip_clamp_summary's layout (checked in slrhip_api.hip)
+// The clamp records (slrhip_clamp_begin) have the shape of the noise records and the same two read-outs, with the summary's grid.
+struct ClampTotals {                                       // slrhip_clamp_summary's layout (checked in slrhip_buffers.hip)
     uint64_t clamped, dropped;
     double removed;
     float largest;
     uint32_t pad;
 };
-void launchClampResolve(const float4* records, const uint32_t* pixelXY, uint32_t numPixels, uint32_t imageWidth, uint32_t channel, float* dst,
-                        hipStream_t stream);
-void launchClampSummary(const float4* records, uint32_t numPixels, ClampTotals* partials, ClampTotals* out, hipStream_t stream);
+// The read-outs of either record kind, named by its totals struct (StatsTotals, ClampTotals; pt_stats.hip instantiates both).
+// One SLRHIP_STATISTICS_* / SLRHIP_CLAMP_* channel as [height][width] floats (dst cleared by the caller: pixels outside the shard stay 0):
+template <typename Totals>
+void launchRecordResolve(const float4* records, const uint32_t* pixelXY, uint32_t numPixels, uint32_t imageWidth, uint32_t channel, float* dst,
+                         hipStream_t stream);
+// the shard's totals, in double, in a fixed order: partials[statsSummaryBlocks(numPixels)], then *out (both DEVICE memory)
+template <typename Totals>
+void launchRecordSummary(const float4* records, uint32_t numPixels, Totals* partials, Totals* out, hipStream_t stream);
 
 // Adaptive sampling (slrhip_render_adaptive; pt_adaptive.hip).  The pixels that have not retired are a compact list in ascending
 // shard-pixel order: activeXY (x | y << 16: what a window over the list hands the kernels as PathBuffers::pixelXY) and activeIndex

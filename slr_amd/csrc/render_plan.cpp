@@ -104,6 +104,14 @@ uint32_t planWindows(uint32_t numPixels, bool spectral, uint32_t sppCount, uint6
     return window;
 }
 
+// The record window of the feature and the albedo passes: 16 B per (pixel, pass), 20 B when the second barycentric is kept, within
+// kFeatureRecordBytes and 2^31 records, 64 passes at the most and one at the least.  It depends on the shard and the channel set
+// (or the scene) alone, so that no later call allocates whatever its pass count.
+uint32_t featureWindow(uint32_t numPixels, bool wantB2) {
+    const uint64_t perPass = (uint64_t)numPixels * (wantB2 ? 20u : 16u);
+    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>({kFeatureRecordBytes / perPass, 0x7FFFFFFFull / numPixels, 64u}));
+}
+
 WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthOverride) {
     WindowPlan w;
     w.workItems = numPixels * sppCount;                           // < 2^32: planWindows
@@ -158,6 +166,28 @@ bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes) {
     if (aBytes == 0 || bBytes == 0) return false;
     // a0 < b0 + bBytes && b0 < a0 + aBytes, written without a sum that could wrap
     return a0 < b0 ? b0 - a0 < aBytes : a0 - b0 < bBytes;
+}
+
+const char* denoiseRefusal(const slrhip_denoise_desc& d) {
+    if (d.reserved != 0) return "reserved must be 0";
+    if (d.components != 3 && d.components != 16) return "components must be 3 or 16";
+    if (d.iterations < 1 || d.iterations > 8) return "iterations must be 1 .. 8";
+    if (d.normal_power_log2 > 7) return "normal_power_log2 must be 0 .. 7";
+    if (d.sigma_luminance != d.sigma_luminance || d.sigma_distance != d.sigma_distance) return "a sigma is NaN";
+    if (denoiseScratch(d.width, d.height, d.components).bytes == 0) return "width and height must be >= 1 and width * height < 2^31";
+    if (!d.color || !d.output) return "null color or output";
+    const size_t pixels = (size_t)d.width * d.height, plane = pixels * sizeof(float), frame = plane * d.components;
+    struct Range { const void* p; size_t bytes; };
+    const Range inputs[5] = {{d.color, frame}, {d.variance, plane}, {d.normal, 3 * plane}, {d.distance, plane}, {d.coverage, plane}};
+    const Range outputs[2] = {{d.output, frame}, {d.output_variance, plane}};
+    for (const Range& r : inputs) if ((uintptr_t)r.p & 3u) return "a misaligned pointer (4 bytes)";
+    for (const Range& r : outputs) if ((uintptr_t)r.p & 3u) return "a misaligned pointer (4 bytes)";
+    if ((d.normal || d.distance) && !d.coverage) return "normal and distance need coverage";
+    for (const Range& o : outputs)
+        for (const Range& in : inputs)
+            if (o.p && in.p && rangesOverlap(o.p, o.bytes, in.p, in.bytes)) return "an output overlaps an input";
+    if (d.output_variance && rangesOverlap(d.output, frame, d.output_variance, plane)) return "output and output_variance overlap";
+    return nullptr;
 }
 
 size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format) {

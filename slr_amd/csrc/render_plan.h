@@ -1,7 +1,7 @@
 // render_plan.h — the host half of the render set-up: every decision of slrhip_render_begin / slrhip_render that is integer
 // arithmetic (the shard's pixel list, the slot count, the result windows, their run lengths, the tail-kernel bound), with no device
 // call, no context state and no environment variable: every override comes in as an argument (see render_plan.cpp).
-// slrhip_api.hip allocates and launches from the result; slrhip_debug_render_plan (include/slrhip_debug.h) shows it to the tests.
+// slrhip_api.hip and slrhip_buffers.hip allocate and launch from the result; slrhip_debug_render_plan (include/slrhip_debug.h) shows it to the tests.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -14,6 +14,7 @@
 namespace slrhip {
 
 const uint32_t kDefaultRunLength = 64;         // SLRHIP_RUN_LENGTH: passes of a pixel a wave takes in a row (pt_kernels.h WorkItem; measured: DESIGN.md)
+const uint64_t kFeatureRecordBytes = 512ull << 20;      // the record window of the feature and the albedo passes (featureWindow)
 const uint32_t kDefaultTailSlots = 1u << 18;   // SLRHIP_TAIL_SLOTS: measured on the headline frame and its N = 8 shard
 
 struct FramePlan {
@@ -41,6 +42,9 @@ std::vector<uint32_t> shardPixels(const FramePlan& plan);
 
 // Passes per result window of a call of `sppCount` passes over `numPixels` (> 0) pixels with `budgetBytes` for the window.
 uint32_t planWindows(uint32_t numPixels, bool spectral, uint32_t sppCount, uint64_t budgetBytes);
+
+// Passes per launch of slrhip_render_features / slrhip_render_albedo over `numPixels` (> 0) pixels: the length of their record window.
+uint32_t featureWindow(uint32_t numPixels, bool wantB2);
 
 struct WindowPlan {
     uint32_t workItems;                        // numPixels x sppCount
@@ -71,6 +75,9 @@ struct DenoiseScratch {
     size_t bytes = 0;
 };
 DenoiseScratch denoiseScratch(uint32_t width, uint32_t height, uint32_t components);
+
+// The argument checks of slrhip_denoise on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
+const char* denoiseRefusal(const slrhip_denoise_desc& d);
 
 // Do the byte ranges [a, a + aBytes) and [b, b + bBytes) share a byte?  An empty range shares none.
 bool rangesOverlap(const void* a, size_t aBytes, const void* b, size_t bBytes);

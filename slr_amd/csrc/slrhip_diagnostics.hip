@@ -1,0 +1,188 @@
+// slrhip_diagnostics.hip — the entry points of include/slrhip_debug.h, and the two function-level queries with host arrays in and
+// out (slrhip_trace_rays, slrhip_bsdf_queries): what the tests and tools call, never a renderer.
+#include "slrhip_ctx.h"
+
+using namespace slrhip;
+
+// The kernels' hit record is (triangle, t, b1, b2) — Moller-Trumbore's barycentrics; the ABI reports Intersection::u, ::v =
+// (b0, b1) with b0 = 1 - b1 - b2 exactly as Triangle::intersect computes it (TriangleMesh.cpp:159,172-173).
+static void hitsToUV(float* hits, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        float* h = hits + (size_t)i * 4;
+        const float b1 = h[2], b2 = h[3];
+        const float b0 = 1.0f - b1 - b2;
+        uint32_t tri; std::memcpy(&tri, h, 4);
+        h[2] = tri == 0xFFFFFFFFu ? 0.0f : b0;
+        h[3] = tri == 0xFFFFFFFFu ? 0.0f : b1;
+    }
+}
+
+extern "C" {
+
+// Diagnostic entry point: closest-hit queries against the uploaded scene (host arrays in and out).
+// rays: n x {org[3], dir[3], dist_min, dist_max}; hits: n x {triangle, dist, b0, b1}.
+int slrhip_trace_rays(slrhip_ctx* ctx, const float* rays, uint32_t n, float* hits) {
+    if (!ctx || !rays || !hits) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_trace_rays: null argument");
+    if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_trace_rays: no scene uploaded");
+    if (n == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<float4> org(n), dir(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* r = rays + (size_t)i * 8;
+        org[i] = make_float4(r[0], r[1], r[2], r[6]);
+        dir[i] = make_float4(r[3], r[4], r[5], r[7]);
+    }
+    DevArray<float4> dOrg, dDir, dOut;
+    HIP_TRY(dOrg.upload(org));
+    HIP_TRY(dDir.upload(dir));
+    HIP_TRY(dOut.alloc(n));
+    launchTraceBatch(ctx->scene, dOrg.ptr, dDir.ptr, dOut.ptr, n, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hits, dOut.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+    hitsToUV(hits, n);
+    return SLRHIP_OK;
+}
+
+// slrhip_debug.h: the caller's samples as a result window, through the fold of the context's current state.
+int slrhip_debug_fold(slrhip_ctx* ctx, const float* hostSamples, uint32_t passes) {
+    if (!ctx || !hostSamples) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_fold: null argument");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_debug_fold: call slrhip_render_begin first");
+    if (passes < 1 || passes > 64) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_fold: 1 .. 64 passes");
+    HIP_TRY(hipSetDevice(ctx->device));
+    RenderParams rp = ctx->params;
+    if (rp.numSlots == 0) { ctx->firstRenderCall = false; return SLRHIP_OK; }       // an empty shard
+    if (const int rc = clearStatistics(ctx, nullptr)) return rc;
+    if (ctx->firstRenderCall)                                                        // clears the sensor, as a render call of zero passes does
+        if (const int rc = renderWindow(ctx, 0, 0, nullptr)) return rc;
+    const uint32_t planes = rp.spectral ? 4u : 1u, comps = rp.spectral ? 16u : 3u;
+    const size_t elems = (size_t)rp.numPixels * planes;
+    std::vector<uint32_t> xy(rp.numPixels);
+    HIP_TRY(hipMemcpy(xy.data(), ctx->pixelXY.ptr, xy.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<float4> window((size_t)passes * elems);
+    for (uint32_t p = 0; p < passes; ++p)
+        for (uint32_t i = 0; i < rp.numPixels; ++i) {
+            const float* src = hostSamples + (((size_t)p * rp.imageHeight + (xy[i] >> 16)) * rp.imageWidth + (xy[i] & 0xFFFFu)) * comps;
+            float4* dst = window.data() + (size_t)p * elems + (size_t)i * planes;
+            if (rp.spectral) for (uint32_t q = 0; q < 4; ++q) dst[q] = make_float4(src[4 * q], src[4 * q + 1], src[4 * q + 2], src[4 * q + 3]);
+            else dst[0] = make_float4(src[0], src[1], src[2], 0.0f);
+        }
+    HIP_TRY(ctx->results.alloc(window.size()));
+    ctx->buffers.results = ctx->results.ptr;
+    HIP_TRY(hipMemcpy(ctx->results.ptr, window.data(), window.size() * sizeof(float4), hipMemcpyHostToDevice));
+    rp.sppBegin = 0; rp.sppCount = passes;
+    launchFold(ctx->buffers, rp, ctx->stats.on ? ctx->stats.records.ptr : nullptr, clampParams(ctx), nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the argument checks of slrhip_modulate alone.
+int slrhip_debug_modulate_check(const slrhip_modulate_desc* d) {
+    if (!d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_modulate: null argument");
+    if (const char* what = modulateRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_modulate: ") + what);
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the block lengths of a slrhip_render_adaptive call.
+int slrhip_debug_adaptive_blocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t* blocks, uint32_t maxBlocks, uint32_t* numBlocks) {
+    if (!numBlocks || (maxBlocks && !blocks)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_adaptive_blocks: null argument");
+    const std::vector<uint32_t> plan = planAdaptiveBlocks(sppMin, sppStep, sppMax);
+    *numBlocks = (uint32_t)plan.size();
+    for (uint32_t k = 0; k < std::min<uint32_t>(*numBlocks, maxBlocks); ++k) blocks[k] = plan[k];
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): function-level BSDF queries through the device functions the shade kernel calls.
+int slrhip_debug_work_distribution(uint32_t numPixels, uint32_t numSlots, uint32_t numPasses, uint32_t runLength, uint32_t* counts,
+                                   uint32_t* queueLengths) {
+    if (!counts || !queueLengths || numPixels == 0 || numSlots < 64 || numSlots % 64 || runLength == 0 || numPasses % runLength ||
+        (uint64_t)numPixels * numPasses > 0xFFFFFFFFull)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_work_distribution: bad arguments");
+    RenderParams rp;
+    std::memset(&rp, 0, sizeof(rp));
+    rp.numSlots = numSlots; rp.numWaves = numSlots / 64u; rp.numPixels = numPixels; rp.sppCount = numPasses;
+    rp.workItems = numPixels * numPasses; rp.runLength = runLength; rp.numRuns = numPixels * (numPasses / runLength);
+    for (uint32_t w = 0; w < rp.numWaves; ++w) {
+        uint32_t taken = 0;
+        for (;; ++taken) {
+            const WorkItem it = workItemOf(rp, w, taken);
+            if (!it.valid) break;
+            ++counts[(size_t)it.pass * numPixels + it.pix];
+        }
+        queueLengths[w] = taken;
+        if (workSamplesTaken(rp, w, taken + 7u) != taken) return fail(SLRHIP_ERR_HIP, "slrhip_debug_work_distribution: workSamplesTaken disagrees with the queue");
+    }
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the render plan of render_plan.cpp for a frame, a shard and a call of num_passes passes.
+int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shardIndex, uint32_t shardCount, uint32_t stripes, int32_t mode,
+                             uint32_t numPasses, uint64_t budgetBytes, uint32_t* plan, uint32_t* windows, uint32_t maxWindows,
+                             uint32_t* numWindows, uint32_t* pixels, uint32_t maxPixels) {
+    if (!plan || !numWindows || (maxWindows && !windows) || budgetBytes == 0 || stripes > SLRHIP_MAX_STRIPES ||
+        (mode != SLRHIP_MODE_RGB && mode != SLRHIP_MODE_SPECTRAL))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_render_plan: bad arguments");
+    const bool spectral = mode == SLRHIP_MODE_SPECTRAL;
+    FramePlan frame;
+    std::string err;
+    if (const int rc = planFrame(width, height, shardIndex, shardCount, stripes, spectral, autoStripesOverride(), pairsMask(), &frame, &err))
+        return fail(rc, err);
+    const uint32_t window = frame.numPixels ? planWindows(frame.numPixels, spectral, numPasses, budgetBytes) : 0u;
+    plan[0] = frame.numPixels; plan[1] = frame.stripes; plan[2] = frame.numSlots; plan[3] = window;
+    *numWindows = window ? (numPasses + window - 1) / window : 0u;
+    for (uint32_t k = 0; k < std::min(*numWindows, maxWindows); ++k) {
+        windows[2 * k] = std::min(window, numPasses - k * window);
+        windows[2 * k + 1] = planWindow(frame.numPixels, windows[2 * k], runLengthOverride()).runLength;
+    }
+    if (pixels) {
+        if (maxPixels < frame.numPixels) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_render_plan: pixel buffer too small");
+        if (frame.numPixels) { const std::vector<uint32_t> list = shardPixels(frame); std::memcpy(pixels, list.data(), list.size() * sizeof(uint32_t)); }
+    }
+    return SLRHIP_OK;
+}
+
+int slrhip_bsdf_queries(slrhip_ctx* ctx, uint32_t material, uint32_t n, const float* queries, float wl_offset, float u_lambda, float* out) {
+    if (!ctx || !queries || !out) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_bsdf_queries: null argument");
+    if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_bsdf_queries: no scene uploaded");
+    if (material >= ctx->scene.numMaterials) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_bsdf_queries: material index out of range");
+    if (!(wl_offset >= 0.0f && wl_offset < 1.0f) || !(u_lambda >= 0.0f && u_lambda < 1.0f))
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_bsdf_queries: wl_offset and u_lambda must be in [0, 1)");
+    if (n == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool spectral = ctx->config.mode == SLRHIP_MODE_SPECTRAL;
+    const uint32_t C = spectral ? 16u : 3u, planes = spectral ? 4u : 1u;
+    // WavelengthSamples::createWithEqualOffsets (SpectrumTypes.h:60, RGBTypes.h:41)
+    const uint32_t wl = std::min<uint32_t>((uint16_t)(C * u_lambda), C - 1);
+    std::vector<float> in(queries, queries + (size_t)n * 12);
+    DevArray<float> dIn;
+    DevArray<float4> dGeo, dMisc, dFsS, dFsE;
+    HIP_TRY(dIn.upload(in));
+    HIP_TRY(dGeo.alloc(n));
+    HIP_TRY(dMisc.alloc(n));
+    HIP_TRY(dFsS.alloc((size_t)planes * n));
+    HIP_TRY(dFsE.alloc((size_t)planes * n));
+    launchBsdfQueries(ctx->scene, spectral, material, n, dIn.ptr, wl_offset, wl, dGeo.ptr, dMisc.ptr, dFsS.ptr, dFsE.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<float4> geo(n), misc(n), fsS((size_t)planes * n), fsE((size_t)planes * n);
+    HIP_TRY(hipMemcpy(geo.data(), dGeo.ptr, geo.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(misc.data(), dMisc.ptr, misc.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fsS.data(), dFsS.ptr, fsS.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fsE.data(), dFsE.ptr, fsE.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    const uint32_t stride = 6 + 2 * C;
+    for (uint32_t i = 0; i < n; ++i) {
+        float* o = out + (size_t)stride * i;
+        o[0] = geo[i].x; o[1] = geo[i].y; o[2] = geo[i].z; o[3] = geo[i].w; o[4] = misc[i].x;
+        for (uint32_t k = 0; k < C; ++k) {
+            const float* a = reinterpret_cast<const float*>(&fsS[(size_t)(k / 4) * n + i]);
+            const float* b = reinterpret_cast<const float*>(&fsE[(size_t)(k / 4) * n + i]);
+            o[5 + k] = a[k % 4];
+            o[5 + C + k] = b[k % 4];
+        }
+        o[5 + 2 * C] = misc[i].y;
+    }
+    return SLRHIP_OK;
+}
+
+} // extern "C"

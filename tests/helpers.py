@@ -56,6 +56,26 @@ def assert_bit_equal(a, b, what=""):
     assert not bad.any(), "%s: %d of %d floats differ, max abs diff %g" % (what, bad.sum(), bad.size, np.abs(a - b).max())
 
 
+def summary_double_sum(values):
+    """The fixed order of the double sums of slrhip_statistics_summary and slrhip_clamp_summary (include/slrhip.h) over per-pixel
+    values in pixel-list order: per thread 16 pixels with stride 256 of a block of 4096, per wave the __shfl_down tree with offsets
+    32 .. 1, thread 0 adds waves 1 .. 3, one thread adds the blocks in index order.  A pixel past the end adds zero."""
+    x = np.asarray(values, np.float64)
+    blocks = -(-x.size // 4096)
+    x = np.concatenate([x, np.zeros(blocks * 4096 - x.size)]).reshape(blocks, 16, 256)
+    total = 0.0
+    with np.errstate(all="ignore"):
+        for b in range(blocks):
+            a = np.zeros(256)
+            for k in range(16):
+                a = a + x[b, k]
+            a = a.reshape(4, 64)
+            for off in (32, 16, 8, 4, 2, 1):
+                a = a[:, :off] + a[:, off:2 * off]
+            total = total + (((a[0, 0] + a[1, 0]) + a[2, 0]) + a[3, 0])
+    return float(total)
+
+
 def libm_tolerance(got, want, what, within=0.999, rtol=2e-6, rmse_rel=2e-5, cap=None):
     """Frames whose paths call float libm (GGX / Ward / Ashikhmin lobes, the environment sphere): the device math library is not
     glibc, so a sample moves by an ulp and — rarely — a discrete decision flips.  Stated tolerance: at least `within` of the

@@ -681,28 +681,6 @@ def _graph_check():
 
 
 # ---- 7. slrhip_modulate against the restatement --------------------------------------------------------------------------------------
-class DeviceBuffers:
-    def __init__(self):
-        self.hip, self.ptrs = binding._hip_runtime(), []
-
-    def put(self, array):
-        a = np.ascontiguousarray(array)
-        p = C.c_void_p()
-        binding._hip_check(self.hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
-        self.ptrs.append(p.value)
-        binding._hip_check(self.hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
-        return p.value
-
-    def get(self, ptr, shape, dtype=F):
-        a = np.empty(shape, dtype)
-        binding._hip_check(self.hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2), "hipMemcpy")
-        return a
-
-    def free(self):
-        for p in self.ptrs:
-            self.hip.hipFree(p)
-
-
 FLOOR, PASSES = 0.02, 7
 
 
@@ -737,8 +715,7 @@ def test_modulate_equals_the_restatement(ctx, width, height, comps):
     finite colour within 2 ulp wherever the divisor is finite: two roundings of at most 2^-24 relative each."""
     w, h = width, height
     color, albedo, variance, special = modulate_inputs(w, h, comps)
-    dev = DeviceBuffers()
-    try:
+    with binding.DeviceBlocks() as dev:
         pa = dev.put(albedo)
         for op in (abi.MODULATE_DIVIDE, abi.MODULATE_MULTIPLY):
             want, want_v = np_modulate(color, albedo, PASSES, op, FLOOR, variance)
@@ -777,8 +754,6 @@ def test_modulate_equals_the_restatement(ctx, width, height, comps):
         if special.any():
             a = np.fmax(albedo / F(PASSES), F(FLOOR))
             assert (a == F(FLOOR)).sum() >= 3 + comps and np.isinf(a).sum() == 1
-    finally:
-        dev.free()
 
 
 # ---- 8. loud failures -----------------------------------------------------------------------------------------------------------------
@@ -788,8 +763,7 @@ def test_loud_failures():
     lib = c.lib
     passes = C.c_uint32(0)
     host_buf = np.zeros(32 * 24 * 3, F)
-    dev = DeviceBuffers()
-    try:
+    with binding.DeviceBlocks() as dev:
         room = dev.put(np.zeros(32 * 24 * 3 + 4, F))
         with pytest.raises(binding.SlrHipError, match=r"\(4\).*render_begin"):
             c.render_albedo(1)
@@ -841,8 +815,6 @@ def test_loud_failures():
         assert n == 3 and (sums >= 0).all() and sums.max() > 0 and c.features_status() == 0
         assert lib.slrhip_modulate(c.handle, C.byref(good_descriptor(w, h, comps, **bufs)), None) == 0
         c.synchronize()
-    finally:
-        dev.free()
         c.close()
 
 

@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import summary_double_sum
 from oracle import binding as ob
 from slr_amd import Context, abi, binding, host, scenes
 from test_adaptive import expect_adaptive
@@ -100,28 +101,10 @@ def kahan(frames):
     return s
 
 
-def summary_removed(values):
-    """The fixed order of slrhip_clamp_summary's double sum (include/slrhip.h) over the shard's REMOVED values in pixel-list order."""
-    x = np.asarray(values, np.float64)
-    blocks = -(-x.size // 4096)
-    x = np.concatenate([x, np.zeros(blocks * 4096 - x.size)]).reshape(blocks, 16, 256)
-    total = 0.0
-    with np.errstate(all="ignore"):
-        for b in range(blocks):
-            a = np.zeros(256)
-            for k in range(16):
-                a = a + x[b, k]
-            a = a.reshape(4, 64)
-            for off in (32, 16, 8, 4, 2, 1):
-                a = a[:, :off] + a[:, off:2 * off]
-            total = total + (((a[0, 0] + a[1, 0]) + a[2, 0]) + a[3, 0])
-    return float(total)
-
-
 def expected_summary(rec, pixel_list):
     """slrhip_clamp_summary of the records of the pixels of `pixel_list` (x | y << 16, the shard's order)."""
     x, y = pixel_list & 0xFFFF, pixel_list >> 16
-    return dict(clamped=int(rec.clamped[y, x].sum()), dropped=int(rec.dropped[y, x].sum()), removed=summary_removed(rec.removed[y, x]),
+    return dict(clamped=int(rec.clamped[y, x].sum()), dropped=int(rec.dropped[y, x].sum()), removed=summary_double_sum(rec.removed[y, x]),
                 largest=float(np.fmax.reduce(rec.largest[y, x], initial=F(0))))
 
 

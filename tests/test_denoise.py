@@ -403,37 +403,12 @@ def test_non_finite_pixels(ctx, comps):
     assert_same_with_nan(ctx.denoise(want_variance=True, **inputs, **kw), want, "luminance stop off")
 
 
-class DeviceBuffers:
-    """hipMalloc'ed float buffers for the raw calls of the argument tests."""
-
-    def __init__(self):
-        self.hip, self.ptrs = binding._hip_runtime(), []
-
-    def put(self, array):
-        a = np.ascontiguousarray(array, F)
-        p = C.c_void_p()
-        binding._hip_check(self.hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
-        self.ptrs.append(p.value)
-        binding._hip_check(self.hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
-        return p.value
-
-    def get(self, ptr, shape):
-        a = np.empty(shape, F)
-        binding._hip_check(self.hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2), "hipMemcpy")
-        return a
-
-    def free(self):
-        for p in self.ptrs:
-            self.hip.hipFree(p)
-
-
 @pytest.mark.gpu
 def test_argument_errors(ctx):
     w, h, comps = 37, 21, 3
     k = case(w, h, comps, 2)
     inputs = k["inputs"]
-    dev = DeviceBuffers()
-    try:
+    with binding.DeviceBlocks() as dev:
         p = {name: dev.put(a) for name, a in inputs.items()}
         sentinel = F(-7.5)
         out, out_v = dev.put(np.full((h, w, comps), sentinel)), dev.put(np.full((h, w), sentinel))
@@ -476,8 +451,6 @@ def test_argument_errors(ctx):
         assert lib.slrhip_denoise(ctx.handle, C.byref(d), None) == 0
         ctx.synchronize()
         assert_result((dev.get(out, (h, w, comps)), dev.get(out_v, (h, w))), k["want"], "after the refused calls")
-    finally:
-        dev.free()
 
 
 @pytest.mark.gpu

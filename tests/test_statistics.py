@@ -12,9 +12,10 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, summary_double_sum
 from oracle import binding as ob
 from slr_amd import Context, abi, binding, host, scenes, spectra
+from test_cabi import render_plan
 
 F = np.float32
 CHANNELS = (abi.STATISTICS_MEAN, abi.STATISTICS_VARIANCE, abi.STATISTICS_VARIANCE_OF_MEAN, abi.STATISTICS_COUNT, abi.STATISTICS_MAX)
@@ -208,6 +209,32 @@ def test_statistics_do_not_depend_on_how_the_passes_are_cut(mode):
     assert max(part_summaries[0]["max_sample"], part_summaries[1]["max_sample"]) == first["max_sample"]
     for name in ("sum_mean", "sum_mean_sq", "sum_variance_of_mean"):
         assert abs(part_summaries[0][name] + part_summaries[1][name] - first[name]) <= 1e-9 * first[name], name
+
+
+@pytest.mark.gpu
+def test_summary_sums_in_the_fixed_order_over_two_blocks():
+    """67 x 63 = 4221 pixels: one full block of the summary's first stage and a second one of 125 pixels (less than a row of 256
+    threads, less than two waves), so the block loop, the guard past the last pixel and the partial wave all run.  The three double
+    sums equal, bit for bit, the restatement of their fixed order (helpers.summary_double_sum) over the float32 channels in
+    pixel-list order; the products mean x mean are exact in double."""
+    width, height, passes = 67, 63, 3
+    st = ob.settings(width, height, seed=5)
+    ctx = Context(mode=abi.MODE_RGB)
+    ctx.upload_scene(scenes.cornell_box_spheres(1.0, 16, 8, "matte"))
+    ch = render_with_statistics(ctx, st, [(0, passes)])
+    got = ctx.statistics_summary()
+    xy = render_plan(ctx.lib, width, height, (0, 1), 0, abi.MODE_RGB, want_pixels=True)[2]
+    ctx.close()
+    assert xy.size == width * height == 4221 and 4096 < xy.size < 4096 + 128
+    x, y = xy & 0xFFFF, xy >> 16
+    mean = ch[abi.STATISTICS_MEAN][y, x].astype(np.float64)
+    want = dict(pixels=xy.size, samples=xy.size * passes, sum_mean=summary_double_sum(mean), sum_mean_sq=summary_double_sum(mean * mean),
+                sum_variance_of_mean=summary_double_sum(ch[abi.STATISTICS_VARIANCE_OF_MEAN][y, x].astype(np.float64)),
+                max_sample=float(ch[abi.STATISTICS_MAX].max()))
+    print("summary %r, restated %r" % (got, want))
+    assert want["sum_mean"] > 0 and want["sum_variance_of_mean"] > 0
+    for name in ("pixels", "samples", "max_sample", "sum_mean", "sum_mean_sq", "sum_variance_of_mean"):
+        assert got[name] == want[name], name
 
 
 # ---- 4: edge counts -------------------------------------------------------------------------------------------------------------

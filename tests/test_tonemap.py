@@ -251,30 +251,6 @@ def ctx():
 GUARD = 64
 
 
-class DeviceBytes:
-    """hipMalloc'ed buffers for the raw calls."""
-
-    def __init__(self):
-        self.hip, self.ptrs = binding._hip_runtime(), []
-
-    def put(self, array):
-        a = np.ascontiguousarray(array)
-        p = C.c_void_p()
-        binding._hip_check(self.hip.hipMalloc(C.byref(p), max(a.nbytes, 16)), "hipMalloc")
-        self.ptrs.append(p.value)
-        binding._hip_check(self.hip.hipMemcpy(p.value, a.ctypes.data, a.nbytes, 1), "hipMemcpy")
-        return p.value
-
-    def get(self, ptr, nbytes):
-        a = np.empty(nbytes, np.uint8)
-        binding._hip_check(self.hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2), "hipMemcpy")
-        return a
-
-    def free(self):
-        for p in self.ptrs:
-            self.hip.hipFree(p)
-
-
 def device_image(ctx, dev, pixels, scale, fmt):
     """The image of pixels [H, W, C] in a 0xAA-filled buffer with GUARD bytes behind it: (image bytes, guard bytes)."""
     h, w, comps = pixels.shape
@@ -282,7 +258,7 @@ def device_image(ctx, dev, pixels, scale, fmt):
     out = dev.put(np.full(size + GUARD, 0xAA, np.uint8))
     ctx.tonemap_into(w, h, comps, dev.put(pixels), out, size, scale, fmt)
     ctx.synchronize()
-    got = dev.get(out, size + GUARD)
+    got = dev.get(out, size + GUARD, np.uint8)
     return got[:size], got[size:]
 
 
@@ -290,8 +266,7 @@ def device_image(ctx, dev, pixels, scale, fmt):
 @pytest.mark.parametrize("comps", [3, 16])
 @pytest.mark.parametrize("width, height", SHAPES)
 def test_bmp_layout_equals_the_host_function(ctx, width, height, comps):
-    dev = DeviceBytes()
-    try:
+    with binding.DeviceBlocks() as dev:
         for scale in SCALES:
             assert_input_condition(width, height, comps, scale)
             k = case(width, height, comps, scale)
@@ -301,16 +276,13 @@ def test_bmp_layout_equals_the_host_function(ctx, width, height, comps):
             bad = np.flatnonzero(got != want)
             assert len(bad) == 0, "%d x %d x %d, scale %g: %d bytes differ, first at %d: %d vs %d" % (width, height, comps, scale, len(bad), bad[0], got[bad[0]], want[bad[0]])
             assert (guard == 0xAA).all(), "bytes behind the image were written"
-    finally:
-        dev.free()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("comps", [3, 16])
 @pytest.mark.parametrize("width, height", SHAPES)
 def test_rgba8_is_the_bmp_reordered(ctx, width, height, comps):
-    dev = DeviceBytes()
-    try:
+    with binding.DeviceBlocks() as dev:
         for scale in SCALES:
             k = case(width, height, comps, scale)
             got, guard = device_image(ctx, dev, k["pixels"], scale, abi.IMAGE_RGBA8)
@@ -319,16 +291,13 @@ def test_rgba8_is_the_bmp_reordered(ctx, width, height, comps):
             assert (got[:, :, 3] == 255).all()
             assert np.array_equal(got, rgba_of_bmp(host_bmp(k["pixels"], width, height, scale), width, height))
             assert (guard == 0xAA).all(), "bytes behind the image were written"
-    finally:
-        dev.free()
 
 
 @pytest.mark.gpu
 def test_argument_errors(ctx):
     w, h, comps, scale = 37, 21, 3, 1.0
     k = case(w, h, comps, scale)
-    dev = DeviceBytes()
-    try:
+    with binding.DeviceBlocks() as dev:
         color = dev.put(k["pixels"])
         frame = 4 * w * h * comps
         size = ctx.lib.slrhip_tonemap_bytes(w, h, abi.IMAGE_BGR8_BMP)
@@ -353,25 +322,23 @@ def test_argument_errors(ctx):
             assert b"slrhip_tonemap" in lib.slrhip_last_error_string()
         assert lib.slrhip_tonemap(ctx.handle, None, None) == INVALID and lib.slrhip_tonemap(None, C.byref(desc()), None) == INVALID
         ctx.synchronize()
-        assert (dev.get(out, room) == 0xAA).all() and (dev.get(big, frame) == 0xAA).all(), "a refused call wrote"
-        assert np.array_equal(dev.get(color, frame), k["pixels"].view(np.uint8).reshape(-1)) and np.array_equal(dev.get(big + frame, frame), k["pixels"].view(np.uint8).reshape(-1))
+        assert (dev.get(out, room, np.uint8) == 0xAA).all() and (dev.get(big, frame, np.uint8) == 0xAA).all(), "a refused call wrote"
+        assert np.array_equal(dev.get(color, frame, np.uint8), k["pixels"].view(np.uint8).reshape(-1)) and np.array_equal(dev.get(big + frame, frame, np.uint8), k["pixels"].view(np.uint8).reshape(-1))
         # adjacent ranges do not overlap: the image ends where the colour begins
         want = host_bmp(k["pixels"], w, h, scale)
         d = desc(color=big + frame, output=big + frame - size)
         assert lib.slrhip_tonemap(ctx.handle, C.byref(d), None) == 0
         ctx.synchronize()
-        assert np.array_equal(dev.get(big + frame - size, size), want)
+        assert np.array_equal(dev.get(big + frame - size, size, np.uint8), want)
         # the good descriptor works after all the refusals; any scale is accepted
         assert lib.slrhip_tonemap(ctx.handle, C.byref(desc()), None) == 0
         ctx.synchronize()
-        got = dev.get(out, room)
+        got = dev.get(out, room, np.uint8)
         assert np.array_equal(got[:size], want) and (got[size:] == 0xAA).all()
         for s in (0.0, float("inf"), float("nan")):                 # (bytes the definition fixes: 0 or 255)
             assert lib.slrhip_tonemap(ctx.handle, C.byref(desc(scale=s)), None) == 0
             ctx.synchronize()
-            assert np.array_equal(dev.get(out, size), host_bmp(k["pixels"], w, h, s)), s
-    finally:
-        dev.free()
+            assert np.array_equal(dev.get(out, size, np.uint8), host_bmp(k["pixels"], w, h, s)), s
 
 
 # torch ships its own copy of the HIP runtime, and only one copy can open the device in a process.  The checks on torch tensors and
