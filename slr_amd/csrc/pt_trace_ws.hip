@@ -488,6 +488,8 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const IO& io, WsLd
                 // admits the boxes around the origin: 3x the triangle tests for shadow rays, 4x slower on the 10 M grid.)
                 // (Tried in round 2: the 24 subtractions + 24 multiplications as packed fp32, v_pk_add_f32 / v_pk_mul_f32 — same
                 // roundings, 110 -> 87 VALU in this block — measured 23 % SLOWER per launch: 1.55 -> 1.90 ms at 22 M slots.)
+                // The operand order of the fmaxf / fminf chains (here and in the eight-wide loop above) and -fno-fast-math are
+                // load-bearing: a NaN product (0 * inf) must be ignored (tests/test_traversal_edges.py).
                 const float tn0 = fmaxf(fmaxf((nX.x - ox) * idx, (nY.x - oy) * idy), fmaxf((nZ.x - oz) * idz, tmin));
                 const float tn1 = fmaxf(fmaxf((nX.y - ox) * idx, (nY.y - oy) * idy), fmaxf((nZ.y - oz) * idz, tmin));
                 const float tn2 = fmaxf(fmaxf((nX.z - ox) * idx, (nY.z - oy) * idy), fmaxf((nZ.z - oz) * idz, tmin));

@@ -130,7 +130,8 @@ __device__ __forceinline__ bool traverse(const DevScene& sc, const float4* __res
             const float4* n = nodes4 + (size_t)cur * 8;
             nX = n[nx]; nY = n[ny]; nZ = n[nz]; fX = n[fx]; fY = n[fy]; fZ = n[fz]; ch = n[6];
         }
-        // slab test of QBVH::Node::intersect (QBVH.h:55-76): tNear <= tFar
+        // slab test of QBVH::Node::intersect (QBVH.h:55-76): tNear <= tFar.  The operand order of the fmaxf / fminf chains and
+        // -fno-fast-math are load-bearing: a NaN product (0 * inf) must be ignored (tests/test_traversal_edges.py).
         const float tn0 = fmaxf(fmaxf((nX.x - org.x) * idx, (nY.x - org.y) * idy), fmaxf((nZ.x - org.z) * idz, tmin));
         const float tn1 = fmaxf(fmaxf((nX.y - org.x) * idx, (nY.y - org.y) * idy), fmaxf((nZ.y - org.z) * idz, tmin));
         const float tn2 = fmaxf(fmaxf((nX.z - org.x) * idx, (nY.z - org.y) * idy), fmaxf((nZ.z - org.z) * idz, tmin));

@@ -837,3 +837,106 @@ def displaced_grid(n=2236, aspect=16.0 / 9.0, seed=20240611, extent=4.0, relief=
     b.add_quad([(-1.0, 3.0, -1.0), (1.0, 3.0, -1.0), (1.0, 3.0, 1.0), (-1.0, 3.0, 1.0)], (0, -1, 0), (1, 0, 0), lm)
     cam = make_camera(_translate(0.0, 2.4, 5.2) @ _rotate(3.1415926536, (0, 1, 0)) @ _rotate(0.42, (1, 0, 0)), aspect, 0.6, 0.025, 1.0, 5.4)
     return b.build(cam, name="displaced_grid_%d" % (2 * n * n))
+
+
+# ---- exact lattice scenes for the traversal edge tests (tests/test_traversal_edges.py) -------------------------------------
+# Every coordinate is a small multiple of 1/4 (the needle's 1/128 apart), so subtractions and products in the slab test and in
+# Moller-Trumbore are exact in float32 and only 1 / det rounds: a brute-force float32 test of every triangle is THE answer.
+def _lattice_camera(n, aspect=1.0):
+    return make_camera(_translate(0.5 * n, 6.0, -1.5 * n) @ _rotate(0.35, (1, 0, 0)), aspect, 0.6, 0.0, 1.0, 2.0 * n)
+
+
+def _add_lattice_terrain(b, n, seed, ground, quads):
+    """The terrain mesh in its own space: an (n+1)^2 heightfield on the integer lattice (heights 0, 1/4 .. 2; two triangles per
+    cell), two COINCIDENT quads at y = 4 over [2, 6]^2 (exact ties; material `quads`), two axis-aligned walls x = 0 and z = n
+    (zero-thickness boxes), a collinear triangle, a triangle with two equal vertices (det == 0 for every ray) and a needle."""
+    rng = np.random.default_rng(seed)
+    h = rng.integers(0, 9, size=(n + 1, n + 1)) * 0.25
+    t = np.arange(n + 1, dtype=np.float64)
+    x, z = np.meshgrid(t, t, indexing="xy")
+    pos = np.stack([x, h, z], axis=-1).reshape(-1, 3)
+    uv = np.stack([x / n, z / n], axis=-1).reshape(-1, 2)
+    idx = (np.arange(n)[:, None] * (n + 1) + np.arange(n)[None, :]).reshape(-1)
+    a, b_, c, d = idx, idx + 1, idx + n + 2, idx + n + 1
+    faces = np.concatenate([np.stack([a, d, c], axis=1), np.stack([a, c, b_], axis=1)], axis=1).reshape(-1, 3)
+    up, east = (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)
+    b.add_mesh(pos, [up] * len(pos), [east] * len(pos), uv, faces, ground)
+    for _ in range(2):
+        b.add_quad([(2, 4, 2), (6, 4, 2), (6, 4, 6), (2, 4, 6)], (0, -1, 0), east, quads)
+    b.add_quad([(0, 0, 0), (0, 0, n), (0, 4, n), (0, 4, 0)], (1, 0, 0), (0, 0, 1), ground)
+    b.add_quad([(0, 0, n), (n, 0, n), (n, 4, n), (0, 4, n)], (0, 0, -1), east, ground)
+    flat = [(0, 0), (1, 0), (1, 1)]
+    b.add_mesh([(1, 3, 1), (2, 3, 2), (3, 3, 3)], [up] * 3, [east] * 3, flat, [(0, 1, 2)], ground)              # collinear
+    b.add_mesh([(5, 3, 1), (5, 3, 1), (6, 3, 2)], [up] * 3, [east] * 3, flat, [(0, 1, 2)], ground)              # two equal vertices
+    b.add_mesh([(1, 3.5, 6), (7, 3.5, 6), (7, 3.5, 6.0078125)], [up] * 3, [east] * 3, flat, [(0, 1, 2)], ground)   # needle
+
+
+def lattice_terrain(n=8, seed=7):
+    """2 n^2 + 11 triangles (139 for n = 8); the coincident quads are the emitter, so the scene is valid for a render."""
+    b = SceneBuilder()
+    ground = b.matte(b.spectrum_srgb_nonlinear(0.72, 0.64, 0.5))
+    light = b.matte(b.spectrum_grey(0.8), emittance=b.spectrum_d65(1.0, D65_RGB))
+    _add_lattice_terrain(b, n, seed, ground, light)
+    return b.build(_lattice_camera(n), name="lattice_terrain_%d" % n)
+
+
+def lattice_grid(n=400, seed=7):
+    """lattice_terrain at n x n cells (400 -> 320 011 triangles): past the 65 536 nodes from which the upload quantizes the tree."""
+    return lattice_terrain(n, seed)
+
+
+def _exact_transform(rows, translation):
+    """A 4x4 from a 3x3 of exact entries (0, +-1, +-2, +-1/2: quarter turns and power-of-two scales) and an integer translation."""
+    m = np.eye(4)
+    m[:3, :3] = rows
+    m[:3, 3] = translation
+    return m
+
+
+def lattice_instanced(n=8, seed=7):
+    """The lattice terrain (its quads matte here: instanced triangles must not emit) and a unit box as two meshes, placed six times
+    with EXACT matrices — quarter turns, scales 2 and 1/2, integer translations — so that the local rays are exact too; two
+    placements of the terrain coincide (ties across instances), and loose walls and a loose emitter stand next to them."""
+    b = SceneBuilder()
+    ground = b.matte(b.spectrum_srgb_nonlinear(0.72, 0.64, 0.5))
+    grey = b.matte(b.spectrum_grey(0.5))
+    light = b.matte(b.spectrum_grey(0.8), emittance=b.spectrum_d65(1.0, D65_RGB))
+    b.add_quad([(-8, 0, -8), (-8, 0, 24), (-8, 8, 24), (-8, 8, -8)], (1, 0, 0), (0, 0, 1), ground)          # loose walls x = -8, z = 24
+    b.add_quad([(-8, 0, 24), (24, 0, 24), (24, 8, 24), (-8, 8, 24)], (0, 0, -1), (1, 0, 0), ground)
+    b.add_quad([(2, 12, 2), (6, 12, 2), (6, 12, 6), (2, 12, 6)], (0, -1, 0), (1, 0, 0), light)             # loose emitter above everything
+    first_t = b.num_triangles()
+    _add_lattice_terrain(b, n, seed, ground, grey)
+    n_t = b.num_triangles() - first_t
+    first_b = b.num_triangles()
+    b.add_box(grey)
+    n_b = b.num_triangles() - first_b
+    ident = [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
+    turn_y = [[0, 0, 1], [0, 1, 0], [-1, 0, 0]]           # quarter turn about y
+    turn_x = [[1, 0, 0], [0, 0, -1], [0, 1, 0]]           # quarter turn about x
+    placements = [(first_t, n_t, _exact_transform(ident, (0, 0, 0))),
+                  (first_t, n_t, _exact_transform(ident, (0, 0, 0))),                                 # coincides with the first
+                  (first_t, n_t, _exact_transform(np.array(turn_y) * 0.5, (12, 1, 8))),                # half size, turned
+                  (first_t, n_t, _exact_transform(turn_x, (0, 6, 12))),                                # stood on its side
+                  (first_b, n_b, _exact_transform(np.array(ident) * 2.0, (4, 3, 4))),                  # a 2-box over the first terrain
+                  (first_b, n_b, _exact_transform(np.array(turn_y) * 2.0, (14, 6, 2)))]
+    for first, num, m in placements:
+        k = b.add_instance(first, num, m)
+        inv = b.instances[k]["world_to_local"].astype(np.float64).reshape(4, 4).T
+        assert (inv @ m == np.eye(4)).all() and (inv * 4 == np.round(inv * 4)).all(), "instance matrices must invert exactly"
+    return b.build(_lattice_camera(n), name="lattice_instanced_%d" % n)
+
+
+def quad_deck(layers=4096):
+    """`layers` coincident copies of one 4 x 4 quad at y = 1 (8 192 triangles): every box of every tree over it is the same box,
+    so a ray through the quad enters every child of every node — the traversal stack grows with the tree's depth, past the part
+    the kernels keep in LDS — and tests every triangle: all of them tie, and the last one must win.  Layer 0 is the emitter."""
+    b = SceneBuilder()
+    light = b.matte(b.spectrum_grey(0.8), emittance=b.spectrum_d65(1.0, D65_RGB))
+    grey = b.matte(b.spectrum_grey(0.5))
+    corners = np.array([(0, 1, 0), (4, 1, 0), (4, 1, 4), (0, 1, 4)], np.float64)
+    uv = [(0, 0), (1, 0), (1, 1), (0, 1)]
+    b.add_quad(corners, (0, -1, 0), (1, 0, 0), light)
+    k = layers - 1
+    faces = (np.array([(0, 1, 2), (0, 2, 3)])[None] + 4 * np.arange(k)[:, None, None]).reshape(-1, 3)
+    b.add_mesh(np.tile(corners, (k, 1)), [(0, -1, 0)] * (4 * k), [(1, 0, 0)] * (4 * k), uv * k, faces, grey)
+    return b.build(_lattice_camera(4), name="quad_deck_%d" % layers)
