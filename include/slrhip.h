@@ -998,6 +998,68 @@ typedef struct slrhip_modulate_desc {
 } slrhip_modulate_desc;
 int slrhip_modulate(slrhip_ctx* ctx, const slrhip_modulate_desc* desc, void* stream);
 
+/* ---- the environment light from device memory ----------------------------------------------------------------------------------------
+ * Replaces or adds the environment sphere of the UPLOADED scene from texels that are already on the device, and leaves everything else
+ * of the scene as it is: no descriptor check, no tree build, no table copied again.  The importance map (slrhip_envmap::importance) and
+ * the sampling tables are built where the texels are.
+ *
+ * The contract.  From the call on the context renders exactly what a fresh slrhip_upload_scene of the same description renders with
+ *   env = {width, height, texels, scale, width / 4, height / 4, slrhip_env_importance(texels)}
+ * where `texels` are the texels as STORED (below): the frame, the counters and every later call match in every bit.  The definitions are
+ * the reference's and are stated once, for host and device, in slr_amd/csrc/pt_envmap.h; all float32, every operation IEEE-rounded on its
+ * own, except where double is stated:
+ *   importance : a map cell is a 4x4 block of texels.  Per component, Image2D::areaAverage (Core/Image.cpp:19-120): a compensated sum
+ *                (s = 0, comp = 0; per texel: val = 1.0f * texel; ci = val - comp; t = s + ci; comp = (t - s) - ci; s = t) over the 16
+ *                texels in the order of (x, y) offsets (0,0) (3,0) (0,3) (3,3) (1,0) (1,3) (2,0) (2,3) (0,1) (3,1) (0,2) (3,2) (1,1)
+ *                (2,1) (1,2) (2,2), then (float)(binary16)(s / 16.0f), round to nearest even, subnormals kept.  RGB mode
+ *                (image_textures.cpp:81-108,131): Y = (0.222485f * a0 + 0.716905f * a1) + 0.060610f * a2 on the three averages.
+ *                Spectral mode, averages (u, v, s): x = (float)(0.0491440520940413 u - 0.02361291916573777 v + 0.13292069743203658),
+ *                y = (float)(0.022853819546830627 u + 0.05077639329371236 v - 0.006895157122499944) in double; X = x s, Y = y s,
+ *                Z = (s - X) - Y; XYZ_to_sRGB (Spectrum.h:59-64) in double rounded to float; the same luminance.
+ *   tables     : row[x] = (float)(sinRow[y] * (double)importance[y][x]) with the DOUBLE sinRow[y] = sin(M_PI * (y + 0.5f) / map_height),
+ *                evaluated on the host and copied (at most 64 KiB); RegularConstantContinuous1D (Core/distributions.cpp:127-147) over
+ *                each row and then over the rows' integrals: a sequential float32 Kahan sum of PDF[i] / n in index order, then PDF[i]
+ *                and CDF[i + 1] divided by the total.  This is what slrhip_upload_scene does with the importance it is given.
+ *   STORED     : the library COPIES the texels into its own array; the caller's buffer is free once the stream has passed the call.
+ *                SLRHIP_ENV_STORE_HALF rounds every component as given to binary16 first; then, in a SPECTRAL context,
+ *                SLRHIP_ENV_TEXELS_RGB converts every texel (r, g, b) -> (u, v, s) as slrhip_env_texels_to_uvs does.
+ *
+ * Ordering.  The work is ordered on `stream`.  slrhip_render blocks until its passes are done, so no render is in flight when the call is
+ * made; feature, albedo and query calls never read the environment.  The accumulation is not touched: samples rendered after the call
+ * see the new light, and a caller who wants a clean frame calls slrhip_render_begin.
+ *
+ * Graphs and allocation.  The call is NOT capturable in a graph: it copies sinRow from the host and may allocate.  It allocates only
+ * when the map is larger than what the context holds, and it allocates the new arrays BEFORE it lets go of the old ones: a failed
+ * allocation returns SLRHIP_ERR_OUT_OF_MEMORY and leaves the previous environment rendering as before.  The importance map stays on the
+ * device (width / 4 x height / 4 floats) for slrhip_debug_environment.
+ *
+ * Errors.  SLRHIP_ERR_INVALID_ARGUMENT, with nothing changed: a null context or descriptor; a width or height that is not a multiple
+ * of 4 in 4 .. 32768; a null or misaligned (16 bytes) `texels`; unknown flag bits; a nonzero `reserved`; a NaN, infinite or negative
+ * `scale`.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.  SLRHIP_ERR_UNSUPPORTED in a SPECTRAL context whose scene was uploaded
+ * without slrhip_scene_desc::upsampling (a scene without environment or image textures may name the tables for this purpose).       */
+#define SLRHIP_ENV_TEXELS_RGB 1u   /* the texels are linear (r,g,b) radiance; a SPECTRAL context converts them per texel to (u,v,s)
+                                    * (slrhip_env_texels_to_uvs); an RGB context ignores the bit                                  */
+#define SLRHIP_ENV_STORE_HALF 2u   /* round every component of the texels as given to binary16 first, as the reference's RGBA16F
+                                    * image would hold them (beyond 65504: infinity, as there)                                    */
+typedef struct slrhip_environment_desc {
+    uint32_t width, height;        /* multiples of 4, 4 .. 32768; the importance map is width/4 x height/4 */
+    const float* texels;           /* DEVICE, [height][width][3], 16-byte aligned; without TEXELS_RGB: what slrhip_envmap::texels holds for the mode */
+    float scale;                   /* slrhip_envmap::scale */
+    uint32_t flags;                /* SLRHIP_ENV_* */
+    uint32_t reserved[2];          /* 0 */
+} slrhip_environment_desc;
+int slrhip_set_environment(slrhip_ctx* ctx, const slrhip_environment_desc* desc, void* stream);
+
+/* The same preprocessing on the HOST (pure; no device is touched), with the functions the kernels call.
+ * importance[(height/4)][(width/4)] = what slrhip_envmap::importance must hold for `texels` ([height][width][3]; mode RGB: (r,g,b),
+ * mode SPECTRAL: (u,v,s)).  width, height: multiples of 4, 4 .. 32768.  num_floats: room at importance.                      */
+int slrhip_env_importance(int32_t mode, const float* texels, uint32_t width, uint32_t height, float* importance, size_t num_floats);
+/* (r,g,b) -> (u,v,s) as the spectral build stores an RGB image (Upsampling::sRGB_to_uvs, Illuminant, BasicTypes/Spectrum.h:148-171;
+ * x = y = (float)(1.0 / 3.0) for a black texel), binary16-rounded; rgb and uvs may be the same array.
+ * Both return SLRHIP_ERR_INVALID_ARGUMENT, with nothing written, for a null pointer, a size that is not a multiple of 4 or is out of
+ * range, another mode, or too little room.                                                                                          */
+int slrhip_env_texels_to_uvs(const float* rgb, size_t num_texels, float* uvs);
+
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */
 enum { SLRHIP_SPECTRUMTYPE_REFLECTANCE = 0, SLRHIP_SPECTRUMTYPE_ILLUMINANT = 1, SLRHIP_SPECTRUMTYPE_IOR = 2 };

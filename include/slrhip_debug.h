@@ -53,6 +53,19 @@ int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t s
  * slrhip_last_error_string.  The pointers are only compared, never followed.  No GPU is touched.                                  */
 int slrhip_debug_modulate_check(const slrhip_modulate_desc* desc);
 
+/* The argument checks of slrhip_set_environment on a descriptor (slr_amd/csrc/render_plan.h, environmentRefusal), evaluated on the HOST
+ * with the function the entry point calls: SLRHIP_OK if the descriptor would pass, else SLRHIP_ERR_INVALID_ARGUMENT with the reason in
+ * slrhip_last_error_string.  The pointer is only compared, never followed.  No GPU is touched.                                      */
+int slrhip_debug_environment_check(const slrhip_environment_desc* desc);
+
+/* The environment of the context's scene, read back to HOST memory.  what: 0 the stored texels (width * height * 3 floats), 1 the
+ * importance map (map_width * map_height), 2 the top PDF (map_height), 3 the top CDF (map_height + 1), 4 the row PDFs
+ * (map_height * map_width), 5 the row CDFs (map_height * (map_width + 1)).  num_floats: room at host_dst, at least that many.
+ * Synchronises.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene; SLRHIP_ERR_INVALID_ARGUMENT for a null argument, a scene without an
+ * environment, an unknown `what`, too little room, and for what == 1 when the environment came from slrhip_upload_scene (the host
+ * path keeps no map).                                                                                                              */
+int slrhip_debug_environment(slrhip_ctx* ctx, uint32_t what, float* host_dst, size_t num_floats);
+
 /* The caller's samples through the fold: host_samples is [passes][height][width][components] float32 (HOST memory), passes 1 .. 64.
  * The shard's pixels are reordered with the context's own pixel list into a result window (pass-major, as the render kernels
  * write it; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's

@@ -182,6 +182,17 @@ class ModulateDesc(C.Structure):
                 ("albedo_passes", C.c_uint32), ("floor", C.c_float), ("reserved", C.c_uint32)]
 
 
+# slrhip_set_environment's flags (SLRHIP_ENV_*)
+ENV_TEXELS_RGB = 1      # the texels are linear (r, g, b): a spectral context converts them per texel to (u, v, s); an RGB context ignores it
+ENV_STORE_HALF = 2      # round every component to binary16 first, as the reference's RGBA16F image holds them
+
+
+class EnvironmentDesc(C.Structure):
+    """slrhip_environment_desc: texels is a DEVICE pointer (an integer address), [height][width][3] float32, 16-byte aligned."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("texels", C.c_void_p), ("scale", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # Context.denoise's default sigma_distance: the accepted relative change of the camera distance per pixel of tap offset
 # (DESIGN.md records how it was picked on the Cornell scenes)
 DENOISE_SIGMA_DISTANCE = 0.1
@@ -279,7 +290,9 @@ class Scene:
                                             self._table_arrays[1].ctypes.data, self._table_arrays[2].ctypes.data)
         return self._tables
 
-    def desc(self, mode=MODE_RGB):
+    def desc(self, mode=MODE_RGB, upsampling=False):
+        """The ctypes descriptor.  upsampling=True names the Meng-15 tables in spectral mode even if the scene does not need them
+        yet: Context.set_environment can then give it an environment."""
         d = SceneDesc()
         d.vertices, d.num_vertices = self.vertices.ctypes.data, len(self.vertices)
         d.triangles, d.num_triangles = self.triangles.ctypes.data, len(self.triangles)
@@ -290,7 +303,7 @@ class Scene:
         env = self.env_uvs if (mode == MODE_SPECTRAL and self.env_uvs is not None) else self.env
         d.env = C.pointer(env) if env is not None else None
         texels = self.texture_texels_uvs if mode == MODE_SPECTRAL else self.texture_texels
-        d.upsampling = C.pointer(self.upsampling_tables()) if ((env is not None or len(texels)) and mode == MODE_SPECTRAL) else None
+        d.upsampling = C.pointer(self.upsampling_tables()) if ((env is not None or len(texels) or upsampling) and mode == MODE_SPECTRAL) else None
         d.textures, d.num_textures = (self.textures.ctypes.data if len(self.textures) else None), len(self.textures)
         d.texture_texels, d.num_texture_texels = (texels.ctypes.data if len(texels) else None), len(texels)
         d.instances, d.num_instances = (self.instances.ctypes.data if len(self.instances) else None), len(self.instances)

@@ -20,6 +20,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_denoise", "slrhip_denoise_scratch_bytes", "slrhip_tonemap", "slrhip_tonemap_bytes",
            "slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate", "slrhip_debug_modulate_check",
            "slrhip_clamp_begin", "slrhip_resolve_clamp", "slrhip_read_clamp", "slrhip_clamp_summary", "slrhip_clamp_sample", "slrhip_debug_fold",
+           "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -117,6 +118,14 @@ def load_library():
                            ("slrhip_debug_fold", [C.c_void_p, C.c_void_p, C.c_uint32])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
+    # (and one from before the environment from device memory lacks these five)
+    for name, argtypes in (("slrhip_set_environment", [C.c_void_p, C.POINTER(abi.EnvironmentDesc), C.c_void_p]),
+                           ("slrhip_env_importance", [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_env_texels_to_uvs", [C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_debug_environment_check", [C.POINTER(abi.EnvironmentDesc)]),
+                           ("slrhip_debug_environment", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
@@ -206,6 +215,7 @@ class Context:
         self.components = self.lib.slrhip_components(self.handle)
         self.settings = None
         self.shard = (0, 1)
+        self._env_size = None                     # (width, height, map width, map height) of the scene's environment, for debug_environment
 
     def close(self):
         if getattr(self, "handle", None):
@@ -215,9 +225,61 @@ class Context:
     def __del__(self):
         self.close()
 
-    def upload_scene(self, scene):
-        desc = scene.desc(self.mode)
+    def upload_scene(self, scene, upsampling=False):
+        """slrhip_upload_scene.  upsampling=True: a spectral context also gets the Meng-15 tables of a scene that does not need
+        them yet, so that set_environment can give it an environment later."""
+        desc = scene.desc(self.mode, upsampling) if upsampling else scene.desc(self.mode)
+        self._env_size = None
         _check(self.lib, self.lib.slrhip_upload_scene(self.handle, C.byref(desc)), "slrhip_upload_scene")
+        if desc.env:
+            e = desc.env.contents
+            self._env_size = (e.width, e.height, e.map_width, e.map_height)
+
+    # ---- the environment light from device memory (slrhip_set_environment) ----
+    def set_environment_into(self, device_ptr, width, height, scale, flags=0, stream=None):
+        """slrhip_set_environment over a DEVICE pointer (an integer address): [height][width][3] float32 texels, 16-byte aligned,
+        copied by the library in order on `stream`; returns at once."""
+        d = abi.EnvironmentDesc(width, height, device_ptr, scale, flags, (C.c_uint32 * 2)(0, 0))
+        _check(self.lib, self.lib.slrhip_set_environment(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_set_environment")
+        self._env_size = (width, height, width // 4, height // 4)
+
+    def set_environment(self, texels, scale, rgb=False, store_half=False, stream=None):
+        """Replaces (or adds) the environment sphere of the uploaded scene (slrhip_set_environment): texels [H, W, 3] float32, what
+        slrhip_envmap::texels holds for the context's mode, or with rgb=True linear (r, g, b) that a spectral context converts to
+        (u, v, s); store_half=True rounds them to binary16 first.  The importance map and the sampling tables are built on the
+        device.  A torch CUDA tensor (contiguous) is passed without a copy and read in order on `stream` (default:
+        torch.cuda.current_stream()); a numpy array is copied to the device first, and that call synchronises."""
+        flags = (abi.ENV_TEXELS_RGB if rgb else 0) | (abi.ENV_STORE_HALF if store_half else 0)
+        if isinstance(texels, np.ndarray):
+            a = np.ascontiguousarray(texels, np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("texels: a [height, width, 3] array expected")
+            with DeviceBlocks() as dev:
+                self.set_environment_into(dev.put(a), a.shape[1], a.shape[0], scale, flags, stream)
+                self.synchronize()                     # the staging block is freed on the way out
+            return
+        import torch
+        if not (isinstance(texels, torch.Tensor) and texels.is_cuda and texels.dtype == torch.float32 and texels.dim() == 3
+                and texels.shape[2] == 3 and texels.is_contiguous()):
+            raise ValueError("texels: a contiguous [height, width, 3] float32 CUDA tensor (or a numpy array) expected")
+        if texels.device.index != self.device:
+            raise SlrHipError("set_environment: the tensor is on device %r, the context on device %d" % (texels.device.index, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.set_environment_into(texels.data_ptr(), texels.shape[1], texels.shape[0], scale, flags, s)
+
+    def debug_environment(self, what):
+        """Diagnostic (slrhip_debug_environment): one array of the scene's environment as a numpy array.  what: 0 the stored texels
+        [H, W, 3], 1 the importance map [mh, mw] (set_environment's only), 2 the top PDF [mh], 3 the top CDF [mh + 1], 4 the row
+        PDFs [mh, mw], 5 the row CDFs [mh, mw + 1].  Synchronises."""
+        if self._env_size is None:
+            raise SlrHipError("debug_environment: the scene has no environment")
+        w, h, mw, mh = self._env_size
+        shape = {0: (h, w, 3), 1: (mh, mw), 2: (mh,), 3: (mh + 1,), 4: (mh, mw), 5: (mh, mw + 1)}.get(what)
+        if shape is None:
+            raise ValueError("what: 0 .. 5 expected")
+        out = np.empty(shape, np.float32)
+        _check(self.lib, self.lib.slrhip_debug_environment(self.handle, what, out.ctypes.data, out.size), "slrhip_debug_environment")
+        return out
 
     def render_begin(self, settings, shard=(0, 1)):
         _check(self.lib, self.lib.slrhip_render_begin(self.handle, C.byref(settings), abi.Shard(*shard)), "slrhip_render_begin")
@@ -701,6 +763,34 @@ class Context:
         self.render_begin(settings, shard)
         self.render(0, spp)
         return self.read_framebuffer()
+
+
+def env_importance(texels, mode=abi.MODE_RGB):
+    """The importance map of an environment image [H, W, 3] float32 ((r, g, b) for abi.MODE_RGB, (u, v, s) for abi.MODE_SPECTRAL), on
+    the host with the functions the kernels of set_environment call (slrhip_env_importance): [H / 4, W / 4] float32 =
+    what slrhip_envmap::importance must hold."""
+    lib = load_library()
+    t = np.ascontiguousarray(texels, np.float32)
+    if t.ndim != 3 or t.shape[2] != 3:
+        raise ValueError("texels: a [height, width, 3] array expected")
+    h, w, _ = t.shape
+    out = np.empty((h // 4, w // 4), np.float32)
+    if lib.slrhip_env_importance(mode, t.ctypes.data, w, h, out.ctypes.data, out.size) != 0:
+        raise ValueError("env_importance: width and height must be multiples of 4 in 4 .. 32768, mode abi.MODE_RGB or abi.MODE_SPECTRAL")
+    return out
+
+
+def env_texels_to_uvs(rgb):
+    """(r, g, b) -> (u, v, s) per texel as the reference's spectral build stores an RGB image, binary16-rounded, on the host with
+    the function set_environment(rgb=True) calls on the device (slrhip_env_texels_to_uvs): an array of the shape given."""
+    lib = load_library()
+    t = np.ascontiguousarray(rgb, np.float32)
+    if t.ndim < 1 or t.shape[-1] != 3:
+        raise ValueError("rgb: an array of [..., 3] expected")
+    out = np.empty_like(t)
+    if lib.slrhip_env_texels_to_uvs(t.ctypes.data, t.size // 3, out.ctypes.data) != 0:
+        raise ValueError("env_texels_to_uvs: bad arguments")
+    return out
 
 
 def clamp_sample(values, limit, flags=0):

@@ -124,6 +124,12 @@ void Scene::setEnvironment(const float* texels, uint32_t width, uint32_t height,
     m_env.map_width = mapWidth; m_env.map_height = mapHeight;
     m_hasEnv = true;
 }
+bool Scene::setEnvironment(const float* texels, uint32_t width, uint32_t height, float scale, int mode) {
+    std::vector<float> importance((size_t)(width / 4) * (height / 4));
+    if (slrhip_env_importance(mode, texels, width, height, importance.data(), importance.size()) != SLRHIP_OK) return false;
+    setEnvironment(texels, width, height, scale, importance.data(), width / 4, height / 4);
+    return true;
+}
 static slrhip_texture makeTexture(uint32_t kind, float ox, float oy, float sx, float sy) {
     slrhip_texture t;
     std::memset(&t, 0, sizeof(t));

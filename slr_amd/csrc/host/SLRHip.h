@@ -76,6 +76,10 @@ public:
     // `scale` of IBLEmission, and the quarter-resolution luminance map ImageSpectrumTexture::createIBLImportanceMap would build.
     void setEnvironment(const float* texels, uint32_t width, uint32_t height, float scale, const float* importance, uint32_t mapWidth,
                         uint32_t mapHeight);
+    // The same with the map built here (slrhip_env_importance: quarter resolution, width and height multiples of 4).  `mode` says what
+    // the texels are: (r, g, b) for SLRHIP_MODE_RGB, (u, v, s) for SLRHIP_MODE_SPECTRAL (slrhip_env_texels_to_uvs makes them).  Returns
+    // false, with the scene unchanged, for a size or mode the export refuses.
+    bool setEnvironment(const float* texels, uint32_t width, uint32_t height, float scale, int mode = SLRHIP_MODE_RGB);
     // Checkerboard textures of libSLR (Textures/checker_board_textures.h) over an OffsetAndScale2DMapping (Core/textures.h:32-42).
     // addCheckerSpectrumTexture returns the VALUE for a material's spectrum slot (SLRHIP_TEXTURE_REF); the other two return the
     // texture index for addMaterial's normalMap / alphaMap (BumpSingleSurfaceObject, Triangle's alpha texture).

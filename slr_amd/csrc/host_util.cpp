@@ -10,6 +10,7 @@
 #include "../../include/slrhip.h"
 #include "cmf16_table.h"
 #include "pt_clamp.h"
+#include "pt_envmap.h"
 #include "pt_luminance.h"
 #include "pt_tonemap.h"
 #include "cmf_2deg_table.h"
@@ -284,6 +285,38 @@ int slrhip_clamp_sample(int32_t components, const float* in, float limit, uint32
     if (yIn) *yIn = a;
     if (yOut) *yOut = b;
     return (int)what;
+}
+
+// The importance map of an environment image, as slrhip_set_environment builds it on the device (pt_envmap.h: the same functions).
+int slrhip_env_importance(int32_t mode, const float* texels, uint32_t width, uint32_t height, float* importance, size_t numFloats) {
+    if (!texels || !importance || (mode != SLRHIP_MODE_RGB && mode != SLRHIP_MODE_SPECTRAL)) return SLRHIP_ERR_INVALID_ARGUMENT;
+    if (width < 4 || height < 4 || width > 32768 || height > 32768 || width % 4 || height % 4) return SLRHIP_ERR_INVALID_ARGUMENT;
+    const uint32_t mw = width / 4, mh = height / 4;
+    if (numFloats < (size_t)mw * mh) return SLRHIP_ERR_INVALID_ARGUMENT;
+    for (uint32_t my = 0; my < mh; ++my) {
+        for (uint32_t mx = 0; mx < mw; ++mx) {
+            float avg[3];
+            for (int c = 0; c < 3; ++c) {
+                float block[16];
+                for (uint32_t y = 0; y < 4; ++y)
+                    for (uint32_t x = 0; x < 4; ++x) block[4 * y + x] = texels[((size_t)(4 * my + y) * width + 4 * mx + x) * 3 + c];
+                avg[c] = slrhip::envAreaAverage(block);
+            }
+            importance[(size_t)my * mw + mx] = mode == SLRHIP_MODE_RGB ? slrhip::envImportanceRGB(avg[0], avg[1], avg[2])
+                                                                       : slrhip::envImportanceUVS(avg[0], avg[1], avg[2]);
+        }
+    }
+    return SLRHIP_OK;
+}
+
+// (r, g, b) -> (u, v, s) per texel, as halves (pt_envmap.h: the function k_env_store calls).  In place is fine: a texel is read whole first.
+int slrhip_env_texels_to_uvs(const float* rgb, size_t numTexels, float* uvs) {
+    if (!rgb || !uvs) return SLRHIP_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < numTexels; ++i) {
+        const float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+        slrhip::envRgbToUvs(r, g, b, uvs[3 * i], uvs[3 * i + 1], uvs[3 * i + 2]);
+    }
+    return SLRHIP_OK;
 }
 
 int slrhip_tonemap_bgr8(const float* fb, int32_t width, int32_t height, int32_t components, float scale, uint8_t* dst,

@@ -239,6 +239,17 @@ const char* modulateRefusal(const slrhip_modulate_desc& d) {
     return nullptr;
 }
 
+const char* environmentRefusal(const slrhip_environment_desc& d) {
+    if (d.reserved[0] != 0 || d.reserved[1] != 0) return "reserved must be 0";
+    if (d.flags & ~(SLRHIP_ENV_TEXELS_RGB | SLRHIP_ENV_STORE_HALF)) return "unknown flag bits";
+    if (d.width < 4 || d.height < 4 || d.width > 32768 || d.height > 32768 || d.width % 4 || d.height % 4)
+        return "width and height must be multiples of 4 in 4 .. 32768";
+    if (!d.texels) return "null texels";
+    if ((uintptr_t)d.texels & 15u) return "misaligned texels (16 bytes)";
+    if (!(d.scale >= 0.0f) || !(d.scale <= 3.402823466e+38f)) return "scale must be finite and >= 0";
+    return nullptr;
+}
+
 } // namespace slrhip
 
 extern "C" size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format) {

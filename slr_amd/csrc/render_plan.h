@@ -89,5 +89,8 @@ size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format);
 const char* tonemapRefusal(const slrhip_tonemap_desc& d);
 // The argument checks of slrhip_modulate on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
 const char* modulateRefusal(const slrhip_modulate_desc& d);
+// The argument checks of slrhip_set_environment on the descriptor (the pointer is only compared, never followed): nullptr if the
+// call goes ahead, else what is wrong with it.  What depends on the context (no scene, no upsampling tables) is the entry point's.
+const char* environmentRefusal(const slrhip_environment_desc& d);
 
 } // namespace slrhip

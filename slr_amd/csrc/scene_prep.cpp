@@ -11,6 +11,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "pt_envmap.h"
+
 namespace slrhip {
 namespace {
 
@@ -456,21 +458,14 @@ void prepareEnvironment(const slrhip_scene_desc& d, PreparedScene& p) {
     p.envRowCDF.assign((size_t)(mw + 1) * mh, 0.0f);
     p.envTopPDF.resize(mh);
     p.envTopCDF.assign(mh + 1, 0.0f);
-    // RegularConstantContinuous1D ctor, distributions.cpp:127-147
-    auto build1D = [](float* PDF, float* CDF, uint32_t n) -> float {
-        KahanF sum;
-        CDF[0] = 0.0f;
-        for (uint32_t i = 0; i < n; ++i) { sum.add(PDF[i] / n); CDF[i + 1] = sum.result; }
-        for (uint32_t i = 0; i < n; ++i) { PDF[i] /= sum.result; CDF[i + 1] /= sum.result; }
-        return sum.result;
-    };
+    // the steps are pt_envmap.h's, shared with the kernels of slrhip_set_environment
     for (uint32_t y = 0; y < mh; ++y) {
         float* row = p.envRowPDF.data() + (size_t)y * mw;
-        for (uint32_t x = 0; x < mw; ++x)
-            row[x] = (float)(std::sin(M_PI * (y + 0.5f) / mh) * e.importance[(size_t)y * mw + x]);
-        p.envTopPDF[y] = build1D(row, p.envRowCDF.data() + (size_t)y * (mw + 1), mw);
+        const double sinRow = envSinRow(y, mh);
+        for (uint32_t x = 0; x < mw; ++x) row[x] = envRowValue(sinRow, e.importance[(size_t)y * mw + x]);
+        p.envTopPDF[y] = envBuild1D(row, p.envRowCDF.data() + (size_t)y * (mw + 1), mw);
     }
-    build1D(p.envTopPDF.data(), p.envTopCDF.data(), mh);
+    envBuild1D(p.envTopPDF.data(), p.envTopCDF.data(), mh);
 }
 
 // --- spectral mode with an environment map or image textures: the Meng-15 tables to look texels up at run time ----------------
@@ -553,7 +548,8 @@ int prepareScene(const slrhip_scene_desc& d, const slrhip_config& config, Prepar
     PREP_TRY(prepareTriangles(d, facts, p, err));
     prepareTexcoords(d, facts, p);
     prepareEnvironment(d, p);
-    if ((d.env || anyImageTexture) && spectral) prepareUpsampling(d, p);
+    // (also for a scene that names the tables without needing them yet: slrhip_set_environment can then give it an environment)
+    if (spectral && (d.upsampling || d.env || anyImageTexture)) prepareUpsampling(d, p);
     p.camera = prepareCamera(d.camera);
     packShadeTables(spectral, p);
     return SLRHIP_OK;

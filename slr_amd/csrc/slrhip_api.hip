@@ -158,6 +158,7 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     HIP_TRY(ctx->queryError.alloc(1));
     HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));
     bindScene(ctx, d, p, numNodes, quantized);
+    ctx->envOwnMap = false;
     ctx->bvhDepth = depth;
     ctx->bvhLeafRefs = leafRefs;
     ctx->haveScene = true;

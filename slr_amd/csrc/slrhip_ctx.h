@@ -107,6 +107,9 @@ struct slrhip_ctx {
     DevArray<float> lightPMF, lightCDF;
     DevArray<float4> shadeTables;
     DevArray<float> envTexels, envTopPDF, envTopCDF, envRowPDF, envRowCDF;
+    DevArray<float> envImportance;                // slrhip_set_environment: the importance map it built (the upload's comes from the host and is not kept)
+    DevArray<double> envSinRow;                   // ... and the rows' sines, copied from the host
+    bool envOwnMap = false;                       // the environment is slrhip_set_environment's: envImportance belongs to it
     DevArray<uint8_t> gridCells;
     DevArray<float> pointUV, pointSpectrum;
     slrhip::DevScene scene;

@@ -24,6 +24,9 @@ detail passes the filter.  `--albedo FILE.npy` writes the mean first-hit albedo 
 `--device-tonemap` tone-maps every BMP above on the device (Context.frame_image, slrhip_tonemap): the frame is resolved into device
 memory (or is the denoiser's output there) and only the 8-bit rows are copied back, in place of a read-back of the floats and the
 host loop of slrhip_tonemap_bgr8.
+`--environment FILE.npy [--environment-scale S]` lights the scene with a lat-long image ([H][W][3] linear RGB): it is rounded to
+binary16 and handed to the scene with the importance map of slrhip_env_importance (with `--spectral` also as (u, v, s) texels,
+slrhip_env_texels_to_uvs), so a scene lit only by its environment renders.
 """
 import argparse
 import ctypes as C
@@ -162,7 +165,25 @@ def build_parser():
     ap.add_argument("--drop-nonfinite", action="store_true", help="replace a sample whose luminance is NaN or infinite by zero")
     ap.add_argument("--clamp-map", default=None, metavar="FILE.npy",
                     help="with --clamp or --drop-nonfinite: write the per-pixel clamp records [4, height, width]: clamped, dropped, removed, largest")
+    ap.add_argument("--environment", default=None, metavar="FILE.npy",
+                    help="light the scene with this lat-long image: [H][W][3] linear RGB radiance, H and W multiples of 4 (row 0 = +Y)")
+    ap.add_argument("--environment-scale", type=float, default=1.0, metavar="S", help="with --environment: the radiance scale")
     return ap
+
+
+def environment_from_file(path, scale, spectral):
+    """--environment: the tuple load_scene(environment=...) takes.  The image is rounded to binary16, as the reference's RGBA16F image
+    holds it; the importance map (and, for --spectral, the (u, v, s) texels and their importance map) come from the library's host
+    exports slrhip_env_importance / slrhip_env_texels_to_uvs."""
+    rgb = np.asarray(np.load(path), np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] % 4 or rgb.shape[1] % 4:
+        raise ValueError("--environment: a [height, width, 3] array with height and width multiples of 4 expected, not %r" % (rgb.shape,))
+    rgb = rgb.astype(np.float16).astype(np.float32)
+    env = (rgb, float(scale), binding.env_importance(rgb, abi.MODE_RGB))
+    if spectral:
+        uvs = binding.env_texels_to_uvs(rgb)
+        env = env + (uvs, binding.env_importance(uvs, abi.MODE_SPECTRAL))
+    return env
 
 
 def clamp_begin(ctx, args):
@@ -203,8 +224,15 @@ def main(argv=None):
     if args.clamp_map and args.clamp is None and not args.drop_nonfinite:
         ap.error("--clamp-map goes with --clamp or --drop-nonfinite")
 
+    if not args.environment_scale >= 0 or args.environment_scale == float("inf"):
+        ap.error("--environment-scale must be finite and >= 0")
     try:
-        scene, settings, renderer = scene_language.load_scene(args.scene)
+        environment = environment_from_file(args.environment, args.environment_scale, args.spectral) if args.environment else None
+    except (OSError, ValueError) as e:
+        print("failed to read the environment image: %s" % e, file=sys.stderr)
+        return -1
+    try:
+        scene, settings, renderer = scene_language.load_scene(args.scene, environment=environment)
     except scene_language.SceneLanguageError as e:
         print("failed to read the scene: %s" % e, file=sys.stderr)
         return -1                                                            # main.cpp:39-42
