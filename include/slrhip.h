@@ -33,7 +33,8 @@ extern "C" {
                             * 7: the measured-slower traversal / shading schedules, their flags and the measurement exports are gone
                             *    (TRACE_BATCH, TRACE_POOL, SPECTRAL_QUAD, QUAD_LAYOUT, slrhip_trace_rays_timed, slrhip_debug_read_rays);
                             *    kernel classes of slrhip_profile = {TRACE, SHADE, TAIL}: a wavefront iteration is two launches;
-                            *    slrhip_bsdf_queries moved to slrhip_debug.h.  The number is frozen here: later additions append.   */
+                            *    slrhip_bsdf_queries moved to slrhip_debug.h.  The number is frozen here: later additions append.
+                            *    Appended since: SLRHIP_FLAG_NO_PRIMARY_PASS (bit 8; the primary pass is on by default).           */
 
 /* ---- status codes -------------------------------------------------------------- */
 enum {
@@ -350,7 +351,12 @@ typedef struct slrhip_profile {
 } slrhip_profile;
 
 /* config.flags */
-#define SLRHIP_FLAG_TAIL_KERNEL 128u    /* with a FIXED slot count (slrhip_config::stripes > 0): also hand the last <= 2^18 live slots of a render
+#define SLRHIP_FLAG_NO_PRIMARY_PASS 256u /* turn the primary pass OFF.  By default the camera ray of every sample of a result window is traced by one
+                                         * pass before the window's iterations and a slot shades its new sample's first hit in the launch that
+                                         * starts it; with this flag a new sample's camera ray goes through the slot state and the traversal
+                                         * launch of the next iteration, as it did before.  Same samples, same counters, same frame to the last
+                                         * bit; the comparator of the tests.  (SLRHIP_FLAG_COUNT_TRAVERSAL also keeps the pass off.)          */
+#define SLRHIP_FLAG_TAIL_KERNEL 128u   /* with a FIXED slot count (slrhip_config::stripes > 0): also hand the last <= 2^18 live slots of a render
                                          * window (never more than an eighth of the slots) to the tail kernel — one launch instead of the
                                          * last wavefront iterations.  Same samples, same frame to the last bit (the sensor adds a pixel's
                                          * samples in pass order whoever rendered them).  Always on with the automatic slot count

@@ -42,7 +42,19 @@ int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shard_index
                              uint32_t num_passes, uint64_t budget_bytes, uint32_t* plan, uint32_t* windows, uint32_t max_windows,
                              uint32_t* num_windows, uint32_t* pixels, uint32_t max_pixels);
 
-/* The blocks of a slrhip_render_adaptive call (slr_amd/csrc/render_plan.h, planAdaptiveBlocks), evaluated on the HOST with the
+/* The primary pass of a result window (slr_amd/csrc/render_plan.h, planPrimary), evaluated on the HOST with the very function the render
+ * calls: a window of `num_passes` passes over `num_pixels` pixels in a context with slrhip_config::flags `config_flags`; `scene_class`
+ * bit 0: the scene has instanced meshes, bit 1: the context is spectral, bit 2: the scene has an environment light (the last two keep the
+ * pass off).  plan[0] = 1 if the pass runs (0: off, and the rest is 0), plan[1] = passes per launch
+ * (num_pixels x plan[1] < 2^31), plan[2] = launches, plan[3] = 1 if the int32 instance plane is allocated.  No GPU is touched.          */
+int slrhip_debug_primary_plan(uint32_t num_pixels, uint32_t num_passes, uint32_t config_flags, int32_t scene_class, uint32_t* plan);
+
+/* How many samples since slrhip_render_begin took their first hit from the primary pass's record (counted on the device by the kernels
+ * that start samples): equal to slrhip_counters::samples when the pass is on, 0 when it is off — a silently disabled pass cannot pass
+ * for a working one.  Synchronises.                                                                                                 */
+int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples);
+
+/* The blocks of a slrhip_render_adaptive call(slr_amd/csrc/render_plan.h, planAdaptiveBlocks), evaluated on the HOST with the
  * function the call asks for its next block: blocks[k] = passes of block k for the first `max_blocks` blocks, *num_blocks = their number (0 for a
  * triple the entry point refuses).  No GPU is touched.                                                                          */
 int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t spp_max, uint32_t* blocks, uint32_t max_blocks,

@@ -21,7 +21,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate", "slrhip_debug_modulate_check",
            "slrhip_clamp_begin", "slrhip_resolve_clamp", "slrhip_read_clamp", "slrhip_clamp_summary", "slrhip_clamp_sample", "slrhip_debug_fold",
            "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
-           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -128,6 +128,10 @@ def load_library():
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
+    # (and one from before the primary pass lacks these two)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_primary_plan"):
+        lib.slrhip_debug_primary_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p]
+        lib.slrhip_debug_primary_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -320,6 +324,12 @@ class Context:
         c = abi.Counters()
         _check(self.lib, self.lib.slrhip_get_counters(self.handle, C.byref(c)), "slrhip_get_counters")
         return c
+
+    def primary_samples(self):
+        """Diagnostic (slrhip_debug_primary_samples): samples since render_begin whose first hit came from the primary pass's record."""
+        n = C.c_uint64()
+        _check(self.lib, self.lib.slrhip_debug_primary_samples(self.handle, C.byref(n)), "slrhip_debug_primary_samples")
+        return n.value
 
     def profile(self):
         p = abi.Profile()

@@ -91,7 +91,8 @@ enum { T_EXT_RAYS = 0, T_SHADOW_RAYS = 1, T_NODES_CLOSEST = 2, T_TRIS_CLOSEST = 
        T_WS_STEPS = 7, T_WS_IDLE_SPINS = 8, T_WS_CYCLES = 9, T_WS_IDLE_CYCLES = 10, T_WS_REFILLS = 11, T_WS_PRODUCER_WAITS = 12,
        T_WS_NODE_BLOCKS = 13, T_WS_TRI_BLOCKS = 14, T_WS_ACTIVE_LANES = 15,
        T_SAMPLES = 16,          // finished samples accumulated into pixels, summed from the slots' headers at the end of a render call
-       T_KINDS = 17 };
+       T_PRIMARY_STARTS = 17,   // samples that took their first hit from the primary pass's record (k_shade's fused start, k_tail)
+       T_KINDS = 18 };
 // device error word bits (PathBuffers::errorWord): set by any kernel path that gives up or drops work
 enum : uint32_t { ERR_RING_SPACE = 1u, ERR_RING_RELEASE = 2u, ERR_CONSUMER_IDLE = 4u, ERR_STACK_OVERFLOW = 8u, ERR_QUEUE_OVERFLOW = 16u };
 static const uint32_t kTotalStride = 16;                   // 64-bit words: one 128-byte line
@@ -116,7 +117,11 @@ struct PathBuffers {
     // spectral four (the sixteen bins of SpectrumStorage) — written once by the slot whose path was that sample; then the
     // sensor itself: per pixel the Kahan sum and its compensation (CompensatedSum, BasicTypes/CompensatedSum.h:24-30), kept
     // across the render calls of one slrhip_render_begin.
+    // While a sample has not finished, its entry holds the primary pass's record of its camera ray instead ({triangle, t, b1, b2}:
+    // the whole RGB entry, the first float4 of a spectral one; RenderParams::primary) and primaryInstance[entry] the instance of
+    // that hit (instanced scenes only, else nullptr).
     float4* results;
+    int32_t* primaryInstance;
     float4* fbSum;
     float4* fbComp;
     float4* nee;                  // pending next-event contribution
@@ -181,6 +186,9 @@ struct RenderParams {
     uint32_t spectral;            // 0 = RGB (3 components), 1 = 16 wavelength samples
     uint32_t injectError;         // SLRHIP_FLAG_TEST_DEVICE_ERROR: the reset kernel raises the device error word
     uint32_t tailSlots;           // enter tail mode once at most this many slots are live; 0 = never
+    uint32_t primary;             // 1: the window's camera rays were traced by the primary pass (launchPrimary) before its first iteration:
+                                  // a sample starts from its record, in the launch that starts it (k_shade), and no slot is ever
+                                  // left in ST_FIRST_HIT by k_shade; 0: startSample leaves the camera ray to k_trace_ws
 };
 
 // Work distribution.  An item is one sample, a (pixel, pass) pair.  The unit that is dealt out is a RUN: runLength consecutive
@@ -268,6 +276,12 @@ void launchTraceBatch(const DevScene& sc, const float4* org, const float4* dir, 
 void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, uint32_t blocks, bool count,
                    hipStream_t stream);
 int traceWsBlocksPerCU(bool quantizedTree);
+// The primary pass of a render window (pt_trace_ws.hip, k_primary_ws): the camera ray of every sample of the passes
+// [firstPass, firstPass + numPasses) of the window (relative to rp.sppBegin) through the wave-specialised consumer, made on the spot
+// by the producer wave; the hit record goes to the sample's entry of the result window (PathBuffers::results, primaryInstance),
+// errors to the render's error word, the ray count to T_EXT_RAYS.  numPixels x numPasses < 2^31 (render_plan.h, planPrimary).
+void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
+                   hipStream_t stream);
 // ray queries (slrhip_intersect_rays / slrhip_test_visibility) through the same consumer: rays = n slrhip_ray records (2 x float4);
 // visible == nullptr: closest hit into hits (slrhip_hit) and, if given, instances; else visibility into visible.  n < 2^31.
 void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,

@@ -10,7 +10,9 @@
 //                    here is finished in the same launch: weight * C goes to the sample's entry of the result window
 //                    (writeResult; sensor->add itself, in pass order, is k_fold's), the wave's queue hands the slot its next
 //                    (pixel, pass), and the new samples of the workgroup are started by its FIRST lanes, compacted
-//                    (Job::kernel's camera half, :100-120: the 50-draw stream seeding runs on full waves).
+//                    (Job::kernel's camera half, :100-120: the 50-draw stream seeding runs on full waves).  With the primary
+//                    pass (RenderParams::primary; launchPrimary, pt_kernels.h) those lanes also take the camera ray's hit from
+//                    the pass's record and shade it in the same launch: the slot leaves with its first bounce in flight.
 //   k_trace_ws       every slot with a ray in flight (state flag) + the shadow-ray queue, one launch (pt_trace_ws.hip)
 //
 // (Rounds 1-2 ran the restart as a third kernel, k_regen, over a queue of finished slots, and kept the pixel's accumulator in
@@ -124,12 +126,15 @@ struct PushLds {
     uint32_t count[4];
     uint32_t base;
 };
-__device__ __forceinline__ void blockPush(PushLds& pl, bool emit, uint32_t slot, uint32_t* queue, uint32_t* counters /* set being filled */,
-                                          uint32_t shardCapacity, uint32_t* errorWord) {
+// A lane hands in up to two slots: its own (`emit`, `slot`) and the one whose new sample it started and shaded in the same launch
+// (`emitB`, `slotB`; k_shade's fused start) — still one reservation per workgroup.  A slot emits at most one shadow ray per launch
+// (a path that ended emitted none), so a region still holds every slot of its blocks.
+__device__ __forceinline__ void blockPush(PushLds& pl, bool emit, uint32_t slot, bool emitB, uint32_t slotB, uint32_t* queue,
+                                          uint32_t* counters /* set being filled */, uint32_t shardCapacity, uint32_t* errorWord) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t shard = blockIdx.x % kShards;
-    const uint64_t m = __ballot(emit);
-    if (lane == 0) pl.count[wave] = (uint32_t)__popcll(m);
+    const uint64_t m = __ballot(emit), mB = __ballot(emitB);
+    if (lane == 0) pl.count[wave] = (uint32_t)__popcll(m) + (uint32_t)__popcll(mB);
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint32_t total = pl.count[0] + pl.count[1] + pl.count[2] + pl.count[3];
@@ -137,10 +142,12 @@ __device__ __forceinline__ void blockPush(PushLds& pl, bool emit, uint32_t slot,
         if (pl.base + total > shardCapacity) atomicOr(errorWord, ERR_QUEUE_OVERFLOW);     // cannot happen: a region holds every slot of its blocks
     }
     __syncthreads();
-    if (emit) {
+    if (emit || emitB) {
         uint32_t off = pl.base;
         for (uint32_t w = 0; w < wave; ++w) off += pl.count[w];
-        queue[(size_t)shard * shardCapacity + off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = slot;
+        const uint64_t below = (1ull << lane) - 1ull;
+        if (emit) queue[(size_t)shard * shardCapacity + off + (uint32_t)__popcll(m & below)] = slot;
+        if (emitB) queue[(size_t)shard * shardCapacity + off + (uint32_t)__popcll(m) + (uint32_t)__popcll(mB & below)] = slotB;
     }
 }
 
@@ -861,31 +868,54 @@ __device__ __forceinline__ Spec16 storageAddend(const Spec16& val, float wlOffse
 // Job::kernel's camera half (PathTracingRenderer.cpp:100-120): seeds the sample's stream, draws in source (left-to-right)
 // order and leaves the slot with a camera ray in flight; writes the slot's sample header (k_shade's compacted start lanes;
 // the tail kernel for the passes left when it takes over).
+// What the camera half leaves in registers: the stream after the camera draws, the sample header's values and the camera ray.
+struct SampleStart {
+    Rng rng;
+    uint32_t wl;
+    float wlOffset, camWeight;
+    V3 org, dir;
+};
 template <class S>
-__device__ __forceinline__ void startSample(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t slot, uint32_t pix,
-                                            uint32_t passOfWindow) {
+__device__ __forceinline__ SampleStart beginSample(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t pix, uint32_t passOfWindow) {
     // Job::kernel PathTracingRenderer.cpp:100-120, draws in source (left-to-right) order
     const uint32_t xy = pb.pixelXY[pix];
     const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
-    Rng rng;
-    const CameraDraws draws = drawCameraSample(rng, rp.rngSeed, px, py, rp.sppBegin + passOfWindow, rp.timeStart, rp.timeEnd);
+    SampleStart st;
+    const CameraDraws draws = drawCameraSample(st.rng, rp.rngSeed, px, py, rp.sppBegin + passOfWindow, rp.timeStart, rp.timeEnd);
     // createWithEqualOffsets: RGBTypes.h:37-45 (offset unused, PDF 1) / SpectrumTypes.h:54-64 (PDF N / 470)
-    const float wlOffset = draws.wlOffset;
-    const uint32_t wl = min((uint32_t)(uint16_t)(S::N * draws.uLambda), (uint32_t)(S::N - 1));
+    st.wlOffset = draws.wlOffset;
+    st.wl = min((uint32_t)(uint16_t)(S::N * draws.uLambda), (uint32_t)(S::N - 1));
     const float selectWLPDF = S::N == 3 ? 1.0f : S::N / (830.0f - 360.0f);
     // PerspectiveCamera::sample + PerspectiveIDF::sample (pt_camera.h)
     const CameraRay cam = sampleCameraRay(sc.camera, rp.imageWidth, rp.imageHeight, draws);
-    const V3 lensP = cam.org, lensN = cam.lensN, rayDir = cam.dir;
+    const V3 lensN = cam.lensN;
+    st.org = cam.org; st.dir = cam.dir;
     float dirPDF = sc.camera.imgPlaneDistance * sc.camera.imgPlaneDistance /
                    ((cam.dirLocalZ * cam.dirLocalZ * cam.dirLocalZ) * sc.camera.imgPlaneArea);
     // weight :126
-    float camWeight = absDot(rayDir, lensN) / (sc.camera.areaPDF * dirPDF * selectWLPDF);
-    pb.flags[slot] = F_MAKE((uint32_t)ST_FIRST_HIT, 0u, wl, 0u, 0u, 0u);
-    pb.rng[(size_t)slot * pb.hdrStride] = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
+    st.camWeight = absDot(st.dir, lensN) / (sc.camera.areaPDF * dirPDF * selectWLPDF);
+    return st;
+}
+template <class S>
+__device__ __forceinline__ void startSample(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t slot, uint32_t pix,
+                                            uint32_t passOfWindow) {
+    const SampleStart st = beginSample<S>(sc, pb, rp, pix, passOfWindow);
+    pb.flags[slot] = F_MAKE((uint32_t)ST_FIRST_HIT, 0u, st.wl, 0u, 0u, 0u);
+    pb.rng[(size_t)slot * pb.hdrStride] = make_uint4(st.rng.s0, st.rng.s1, st.rng.s2, st.rng.s3);
     // alpha = 1, pdfPrev = 0 and sp = 0 are implied by ST_FIRST_HIT (see SpAcc): 48 B (RGB) / 196 B (spectral) not written
-    pb.hdr[(size_t)slot * pb.hdrStride] = make_uint4(pix, __float_as_uint(camWeight), __float_as_uint(wlOffset), passOfWindow);
-    pb.rayOrg[(size_t)slot * pb.rayStride] = make_float4(lensP.x, lensP.y, lensP.z, 0.0f);
-    pb.rayDir[(size_t)slot * pb.rayStride] = make_float4(rayDir.x, rayDir.y, rayDir.z, INFINITY);
+    pb.hdr[(size_t)slot * pb.hdrStride] = make_uint4(pix, __float_as_uint(st.camWeight), __float_as_uint(st.wlOffset), passOfWindow);
+    pb.rayOrg[(size_t)slot * pb.rayStride] = make_float4(st.org.x, st.org.y, st.org.z, 0.0f);
+    pb.rayDir[(size_t)slot * pb.rayStride] = make_float4(st.dir.x, st.dir.y, st.dir.z, INFINITY);
+}
+
+// The pre-traced first hit of sample (pix, passOfWindow) of the window: the primary pass's record in the sample's entry of the
+// result window (launchPrimary, pt_kernels.h), and the instance where the scene has instances.
+template <class S>
+__device__ __forceinline__ void loadPrimaryRecord(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t pix, uint32_t passOfWindow,
+                                                  float4& h, int32_t& inst) {
+    const size_t entry = (size_t)passOfWindow * rp.numPixels + pix;
+    h = pb.results[entry * (S::N == 3 ? 1u : 4u)];
+    inst = sc.instances ? pb.primaryInstance[entry] : -1;
 }
 
 // The finished sample's contribution, weight * C of sensor->add(p.x, p.y, wls, weight * C) (PathTracingRenderer.cpp:126-130) as
@@ -923,7 +953,12 @@ struct StartLds {
 #ifndef SLR_SHADE_EARLY
 #define SLR_SHADE_EARLY 1          // 0 (variant builds): the slot's state records are requested after the table barrier
 #endif
-template <class S, bool LDS_TABLES, bool MF, bool MULTI = false, bool TEX = false>
+// PRIMARY: the instantiation for windows with a primary pass (RenderParams::primary; launchShade picks it): the fused start below.
+// It is a template argument and not a branch on rp.primary because the second trip costs registers whether or not it runs: one kernel
+// for both took k_shade<RGB, glossy> from 163 to 181 VGPRs and the spectral kernels to 190 - 220 B more scratch, and renders WITHOUT
+// the pass (spectral, environment light: render_plan.h) ran 13 - 14 % slower than before.  Without PRIMARY the
+// kernel is what it was.  Built for the RGB kernels only: the plan keeps the pass off in spectral contexts.
+template <class S, bool LDS_TABLES, bool MF, bool MULTI = false, bool TEX = false, bool PRIMARY = false>
 __global__ __launch_bounds__(kShadeBlock)
 __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_SPECTRAL_GLOSSY : SLR_WAVES_SPECTRAL)))) void k_shade(DevScene sc, PathBuffers pb, RenderParams rp, uint32_t parity) {
     __shared__ ShadeLds<S::N != 3> lds;
@@ -965,18 +1000,36 @@ __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_S
     const float* lightPMF = LDS_TABLES ? lds.lightPMF : sc.lightPMF;
     const float* lightCDF = LDS_TABLES ? lds.lightCDF : sc.lightCDF;
 
+    // Two trips through ONE inlined visit.  Trip 0: this lane's own slot.  Trip 1 (PRIMARY instantiations only): the samples the workgroup
+    // starts in this launch, on its first lanes — the camera half in registers, the camera ray's hit from the primary pass's record,
+    // then the very visit a slot in ST_FIRST_HIT gets: the slot leaves the launch with its first bounce in flight instead of
+    // spending an iteration, and a trip through the slot state, on its camera ray.  Every exit from the loop is uniform over the workgroup.
+    // The two trips are UNROLLED (two copies of the visit's code): kept as a loop, the register allocation of k_shade<RGB, lds> went
+    // from 120 VGPRs to 200 (the visit's inputs as loop-carried values; 141 unrolled) and the headline frame from 300 ms to 364 ms —
+    // measured, DESIGN.md 7.17.
+    bool shadow0 = false, shadow1 = false;         // the shadow rays of the two trips: one reservation for both, after the loop
+    uint32_t curSlot = slot, curVis = vis;
+    bool curActive = state0 == ST_FIRST_HIT || state0 == ST_NEXT_HIT || state0 == ST_FINISH;
+    uint4 curHdr = make_uint4(0u, 0u, 0u, 0u);     // trip 1: the new sample's header, from registers
+#pragma clang loop unroll(full)
+    for (uint32_t trip = 0; trip < 2u; ++trip) {
     bool emitExt = false, emitShadow = false, pathEnded = false;
     S radiance;
-    if (state0 == ST_FIRST_HIT || state0 == ST_NEXT_HIT || state0 == ST_FINISH)
-        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true>(sc, pb, rp, lds, lightPMF, lightCDF, slot, in, flags, vis, radiance, emitExt, emitShadow, pathEnded);
+    if (curActive)
+        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true>(sc, pb, rp, lds, lightPMF, lightCDF, curSlot, in, flags, curVis, radiance, emitExt, emitShadow, pathEnded);
 
     // ---- a path that ended: its contribution goes to the result window, in the same launch ------------------------------------
     if (pathEnded) {
-        const uint4 hdr = pb.hdr[(size_t)slot * pb.hdrStride];
-        writeResult<S>(pb, rp, slot, flags, hdr, S::N == 3, radiance);
+        const uint4 hdr = trip == 0u ? pb.hdr[(size_t)curSlot * pb.hdrStride] : curHdr;
+        writeResult<S>(pb, rp, curSlot, flags, hdr, S::N == 3, radiance);
+        // a path that ends in its first visit (a miss, a zero BSDF sample): the slot takes its next sample in the next launch
+        if (trip != 0u) pb.flags[curSlot] = F_MAKE((uint32_t)ST_REGEN, 0u, 0u, 0u, 0u, 0u);
     }
-    // ---- stream compaction of the shadow rays (extension rays need no queue: the traversal kernel reads the state flag) ----------
-    blockPush(pushLds, emitShadow, slot, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
+    if (trip != 0u) { shadow1 = emitShadow; break; }
+    shadow0 = emitShadow;
+    // ---- stream compaction of the shadow rays (extension rays need no queue: the traversal kernel reads the state flag); with the
+    //      fused start, after the second trip ----------
+    if (!PRIMARY) blockPush(pushLds, emitShadow, slot, false, 0u, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
     if (rp.countSlots) {
         const uint64_t ma = __ballot(emitExt || emitShadow || pathEnded);
         if (lane == 0 && ma) atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_SLOT_VISITS, blockIdx.x % kShards)], (unsigned long long)__popcll(ma));
@@ -1014,9 +1067,36 @@ __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_S
         // the live count: one atomic per workgroup and launch, on one of kShards lines (PathBuffers::idleShards)
         if (threadIdx.x == 0 && start.wentIdle) atomicAdd(&pb.idleShards[(blockIdx.x % kShards) * kCounterStride], start.wentIdle);
         const uint32_t n = start.waveBase[0] + start.waveBase[1] + start.waveBase[2] + start.waveBase[3];
-        if (threadIdx.x < n)
-            startSample<S>(sc, pb, rp, blockIdx.x * kShadeBlock + start.lane[threadIdx.x], start.pix[threadIdx.x], start.pass[threadIdx.x]);
+        if (!PRIMARY) {
+            // no primary pass (RenderParams::primary): the camera ray goes through the slot state and k_trace_ws
+            if (threadIdx.x < n)
+                startSample<S>(sc, pb, rp, blockIdx.x * kShadeBlock + start.lane[threadIdx.x], start.pix[threadIdx.x], start.pass[threadIdx.x]);
+            break;
+        }
+        if (n == 0u) break;
+        curActive = threadIdx.x < n;
+        if (curActive) {
+            curSlot = blockIdx.x * kShadeBlock + start.lane[threadIdx.x];
+            const uint32_t pix = start.pix[threadIdx.x], pass = start.pass[threadIdx.x];
+            // the record first: its round trip is hidden behind the seeding of the stream
+            loadPrimaryRecord<S>(sc, pb, rp, pix, pass, in.h, in.hitInstance);
+            const SampleStart st = beginSample<S>(sc, pb, rp, pix, pass);
+            curHdr = make_uint4(pix, __float_as_uint(st.camWeight), __float_as_uint(st.wlOffset), pass);
+            pb.hdr[(size_t)curSlot * pb.hdrStride] = curHdr;
+            // the rest of what startSample writes stays in registers: the visit below stores the state of the first bounce
+            in.r4 = make_uint4(st.rng.s0, st.rng.s1, st.rng.s2, st.rng.s3);
+            in.alpha = S(1.0f); in.pdfPrev = 0.0f;
+            in.o4 = make_float4(st.org.x, st.org.y, st.org.z, 0.0f);
+            in.d4 = make_float4(st.dir.x, st.dir.y, st.dir.z, INFINITY);
+            in.wlOffset = S::N == 3 ? 0.0f : st.wlOffset;
+            flags = F_MAKE((uint32_t)ST_FIRST_HIT, 0u, st.wl, 0u, 0u, 0u);
+            curVis = 0u;
+        }
+        if (threadIdx.x == 0)       // the read-out of slrhip_debug_primary_samples: one atomic (no return) per workgroup and launch, on one of kShards lines
+            atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_PRIMARY_STARTS, blockIdx.x % kShards)], (unsigned long long)n);
     }
+    }
+    if (PRIMARY) blockPush(pushLds, shadow0, slot, shadow1, curSlot, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
 }
 
 // Start of a render window: every slot wants a sample (ST_REGEN), the queues are at their beginning.  `clearSensor`: the first

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(SLR
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t slot = kTailNone;
-    uint32_t extRays = 0, shadowRays = 0, wentIdle = 0;
+    uint32_t extRays = 0, shadowRays = 0, wentIdle = 0, primaryStarts = 0;
     bool listDrained = false;                                  // wave-uniform: the cursor is past the end of the list
     TravCount cnt = {0, 0};
     uint32_t* stack = tlds.stack + threadIdx.x;
@@ -86,7 +86,18 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(SLR
         }
         // ---- one bounce: the two rays of this slot, then the logic visit -----------------------------------------------------
         const float4 o = pb.rayOrg[(size_t)slot * pb.rayStride];
-        if (state != ST_FINISH) {
+        if (rp.primary && state == ST_FIRST_HIT) {
+            // a sample this kernel started (k_shade leaves none in this state then): its camera ray was traced, and counted, by the
+            // window's primary pass — the record instead of a traversal
+            const uint4 hdr = pb.hdr[(size_t)slot * pb.hdrStride];
+            float4 h;
+            int32_t inst;
+            loadPrimaryRecord<S>(sc, pb, rp, hdr.x, hdr.w, h, inst);
+            pb.hit[slot] = h;
+            if (pb.hitInstance) pb.hitInstance[slot] = inst;
+            ++primaryStarts;
+        }
+        else if (state != ST_FINISH) {
             const float4 d = pb.rayDir[(size_t)slot * pb.rayStride];
             HitRec hit;
             // (the instance steps are compiled in for every scene: they cost a test per leaf reference here, and the tail kernel is
@@ -124,8 +135,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(SLR
         __syncthreads();
         return red[0] + red[1] + red[2] + red[3];
     };
-    const uint32_t e = blockSum(extRays), sh = blockSum(shadowRays), idleNow = blockSum(wentIdle);
+    const uint32_t e = blockSum(extRays), sh = blockSum(shadowRays), idleNow = blockSum(wentIdle), prim = blockSum(primaryStarts);
     if (threadIdx.x == 0) {
+        if (prim) atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_PRIMARY_STARTS, blockIdx.x % kShards)], (unsigned long long)prim);
         if (e) atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_EXT_RAYS, blockIdx.x % kShards)], (unsigned long long)e);
         if (sh) atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_SHADOW_RAYS, blockIdx.x % kShards)], (unsigned long long)sh);
         if (idleNow) atomicAdd(&pb.tailIdled[0], idleNow);      // the host checks it against the list length, then clears the live count

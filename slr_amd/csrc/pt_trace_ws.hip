@@ -790,8 +790,9 @@ void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams
 // workgroup is resident and the chunks of one workgroup are its share).  makeRay(i, o, d) loads or computes ray i; a chunk's rays
 // are made before the wait for ring space, so that their loads overlap it.  Every index is a ray: no state flags, no queue.
 // tag = kShadowBit for visibility queries.
+// Returns the rays appended (wave-uniform).
 template <class LDS, class MakeRay>
-__device__ __forceinline__ void wsProduceIndexed(uint32_t n, uint32_t tag, uint32_t* errorWord, LDS& lds, WsDebug& dbg, const MakeRay& makeRay) {
+__device__ __forceinline__ uint32_t wsProduceIndexed(uint32_t n, uint32_t tag, uint32_t* errorWord, LDS& lds, WsDebug& dbg, const MakeRay& makeRay) {
     const uint32_t lane = threadIdx.x;
     const uint32_t chunk = kSub * 64;
     const uint32_t numChunks = (n + chunk - 1) / chunk;           // n < 2^31: c * chunk + 127 stays inside 32 bits
@@ -812,6 +813,7 @@ __device__ __forceinline__ void wsProduceIndexed(uint32_t n, uint32_t tag, uint3
         WS_STORE(&lds.tail, tailLocal, __ATOMIC_RELEASE);
     }
     WS_STORE(&lds.done, 1u, __ATOMIC_RELEASE);
+    return tailLocal;
 }
 
 template <int NC, bool QUANT, bool INST>
@@ -969,6 +971,88 @@ void launchFeatureTrace(const DevScene& sc, const FeatureParams& fp, int numCUs,
 void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream) {
     launchFeatureTrace(sc, fp, numCUs, stream);
     hipLaunchKernelGGL(k_feature_fold, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, sc, fp, sums, idsPass);
+}
+
+// ---- primary pass of a render window (launchPrimary, pt_kernels.h): the feature pass's producer, the path tracer's own hit record ----
+// A camera ray is a function of (pixel, pass, seed) alone, so the first segment of every sample of a window is traced here, before
+// the window's first iteration, instead of making a round trip through the slot state (startSample -> k_trace_ws -> k_shade).  A ring
+// entry is a sample of the launch, index = pass of the launch x pixels + pixel; finish writes {triangle, t, b1, b2} — what
+// WsRenderIO writes to PathBuffers::hit — to the sample's entry of the result window, which nobody else touches until the sample
+// finishes (writeResult), and the instance to its plane.  `stride`: float4 per entry (RGB 1, spectral 4: the record is the first).
+struct PrimaryParams {
+    FeatureParams fp;             // the camera arguments of the launch; records = the launch's first entry; errorWord = the render's
+    int32_t* instances;           // the launch's first entry of PathBuffers::primaryInstance, or nullptr
+    uint64_t* totals;
+    uint32_t stride;
+};
+struct WsPrimaryIO {
+    const DevScene& sc;
+    const PrimaryParams& pp;
+    uint32_t* const& errorWord;
+    __device__ WsPrimaryIO(const DevScene& s, const PrimaryParams& p) : sc(s), pp(p), errorWord(p.fp.errorWord) {}
+    __device__ __forceinline__ void worldRay(uint32_t slot, float4& o, float4& d) const {
+        uint32_t xy;
+        featureCameraRay(sc.camera, pp.fp, slot, o, d, xy);
+    }
+    template <bool INST>
+    __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
+        ntStore4(pp.fp.records + (size_t)slot * pp.stride, make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2));
+        if (INST) __builtin_nontemporal_store(hitInst, pp.instances + slot);
+    }
+};
+
+template <int NC, bool QUANT, bool INST>
+__global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_primary_ws(DevScene sc, PrimaryParams pp, uint32_t n, uint32_t refill) {
+    __shared__ WsLds<NC> lds;
+    if (threadIdx.x == 0) { lds.tail = 0; lds.reserved = 0; lds.released = 0; lds.done = 0; }
+    __syncthreads();
+    WsCounts cnt;
+    WsDebug dbg;
+    if (threadIdx.x < 64) {
+        const uint32_t rays = wsProduceIndexed(n, 0u, pp.fp.errorWord, lds, dbg, [&](uint32_t i, float4& o, float4& d) { uint32_t xy; featureCameraRay(sc.camera, pp.fp, i, o, d, xy); });
+        // Scene::intersect of PathTracingRenderer.cpp:147, counted where it is traced: one atomic per workgroup
+        if (threadIdx.x == 0 && rays) atomicAdd((unsigned long long*)&pp.totals[totalIndex(T_EXT_RAYS, blockIdx.x % kShards)], (unsigned long long)rays);
+    }
+    else wsConsume<false, NC, QUANT, false, INST>(sc, WsPrimaryIO(sc, pp), lds, refill, 0u, cnt, dbg);       // no staged top nodes (numTop = 0)
+}
+
+template <int NC>
+static void launchPrimaryWsT(const DevScene& sc, const PrimaryParams& pp, uint32_t n, uint32_t blocks, hipStream_t stream) {
+    const dim3 grid(blocks), block(64 * (NC + 1));
+    // the query kernels' tree choice (launchQueryWsT), which is k_trace_ws's apart from the variant builds' eight-wide tree
+    if (sc.instances) hipLaunchKernelGGL((k_primary_ws<NC, false, true>), grid, block, 0, stream, sc, pp, n, g_refill);
+    else if (sc.nodesQ) hipLaunchKernelGGL((k_primary_ws<NC, true, false>), grid, block, 0, stream, sc, pp, n, g_refill);
+    else hipLaunchKernelGGL((k_primary_ws<NC, false, false>), grid, block, 0, stream, sc, pp, n, g_refill);
+}
+
+void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
+                   hipStream_t stream) {
+    const bool quant = sc.nodesQ != nullptr && !sc.instances;
+    const uint32_t n = rp.numPixels * numPasses;
+    if (n == 0) return;
+    PrimaryParams pp{};
+    pp.stride = rp.spectral ? 4u : 1u;
+    const size_t first = (size_t)firstPass * rp.numPixels;
+    pp.fp.pixelXY = pb.pixelXY; pp.fp.records = pb.results + first * pp.stride; pp.fp.errorWord = pb.errorWord;
+    pp.fp.numPixels = rp.numPixels; pp.fp.numPasses = numPasses; pp.fp.passBegin = rp.sppBegin + firstPass;
+    pp.fp.rngSeed = rp.rngSeed; pp.fp.timeStart = rp.timeStart; pp.fp.timeEnd = rp.timeEnd;
+    pp.fp.imageWidth = rp.imageWidth; pp.fp.imageHeight = rp.imageHeight;
+    pp.instances = pb.primaryInstance ? pb.primaryInstance + first : nullptr;
+    pp.totals = pb.totals;
+    const uint32_t chunks = (n + kSub * 64 - 1) / (kSub * 64);
+    // Consumers per producer.  Where k_trace_ws runs 7 (small trees) this pass runs 3: its producer wave seeds a stream and samples the
+    // camera for every ray, a camera ray needs few nodes, and with 7 consumers the producer was the limit (headline frame: 306 ms
+    // with 7, 294.5 ms with 3).  Quantized (large) trees and instanced scenes keep k_trace_ws's choice: not measured.
+    static const int envNc = [] { const char* e = tuningEnv("SLRHIP_PRIMARY_NC"); return e ? atoi(e) : 0; }();      // measurement builds: 3 / 7 / 15
+    const int ncTrace = wsConsumers(quant);
+    const int nc = envNc == 3 || envNc == 7 || envNc == 15 ? envNc : (ncTrace == 7 && !sc.instances ? 3 : ncTrace);
+    const size_t lds = nc == 15 ? sizeof(WsLds<15>) : nc == 7 ? sizeof(WsLds<7>) : sizeof(WsLds<3>);
+    const uint32_t perCU = (uint32_t)std::min(nc == 15 ? 2 : nc == 7 ? 4 : 8, (int)(163840 / lds));      // traceWsBlocksPerCU's rule for this NC
+    (void)traceWsBlocksPerCU(quant);                                                                   // (reads the refill override once)
+    const uint32_t blocks = std::max(1u, std::min((uint32_t)numCUs * perCU, chunks));
+    if (nc == 15) launchPrimaryWsT<15>(sc, pp, n, blocks, stream);
+    else if (nc == 7) launchPrimaryWsT<7>(sc, pp, n, blocks, stream);
+    else launchPrimaryWsT<3>(sc, pp, n, blocks, stream);
 }
 
 // slrhip_camera_rays: the producer's half alone, written out in the public slrhip_ray format; one lane per pixel of the shard

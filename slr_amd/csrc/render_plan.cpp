@@ -123,6 +123,19 @@ WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthO
     return w;
 }
 
+PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment) {
+    PrimaryPlan p;
+    if ((configFlags & (SLRHIP_FLAG_NO_PRIMARY_PASS | SLRHIP_FLAG_COUNT_TRAVERSAL)) != 0 || numPixels == 0 || sppCount == 0 ||
+        numPixels > kPrimaryMaxSamples)
+        return p;
+    if (spectral || environment) return p;      // measured slower with the pass: boxes_spectral 838 -> 850 ms, ibl 283 -> 330 ms per frame
+    p.on = true;
+    p.passesPerLaunch = std::min(sppCount, kPrimaryMaxSamples / numPixels);
+    p.numLaunches = (sppCount + p.passesPerLaunch - 1) / p.passesPerLaunch;
+    p.instanceEntries = instanced ? (uint64_t)numPixels * sppCount : 0u;
+    return p;
+}
+
 // The end of the window (pt_tail_kernels.h): once at most tailSlots slots are alive the traversal kernel raises the tail-mode word
 // instead of tracing, the rest of the block of iterations is no-ops, and the tail kernel finishes every remaining path and sample
 // in one launch.  The image does not depend on who finishes a sample (the sensor adds in pass order).  On with the automatic slot

@@ -54,6 +54,22 @@ struct WindowPlan {
 // One window of `sppCount` passes; `runLengthOverride` (0 = none) replaces kDefaultRunLength as the longest run.
 WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthOverride);
 
+// The primary pass of a window (pt_kernels.h launchPrimary): the camera ray of every sample of the window traced before its first
+// iteration, the hit record kept in the sample's entry of the result window.  Off with SLRHIP_FLAG_NO_PRIMARY_PASS, and with
+// SLRHIP_FLAG_COUNT_TRAVERSAL: the nodes and triangles per ray are counted by the wavefront kernels, and they are properties of the
+// rays, not of the schedule.  A launch numbers its samples in 31 bits, so the window's passes go in groups of passesPerLaunch.
+const uint32_t kPrimaryMaxSamples = 0x7FFFFFFFu;        // ring indices of one launch (pt_trace_ws.hip, wsProduceIndexed)
+struct PrimaryPlan {
+    bool on = false;
+    uint32_t passesPerLaunch = 0;              // numPixels x passesPerLaunch <= kPrimaryMaxSamples
+    uint32_t numLaunches = 0;                  // ceil(sppCount / passesPerLaunch)
+    uint64_t instanceEntries = 0;              // int32 entries of PathBuffers::primaryInstance: numPixels x sppCount in instanced scenes, else 0
+};
+// Two classes of render keep the pass off because it measured slower there: spectral contexts (`spectral`) and
+// scenes with an environment light (`environment`: many camera rays leave the scene, their paths end in the fused visit and the
+// slot waits for the next launch).
+PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment);
+
 // RenderParams::tailSlots of a window: 0 = the tail kernel stays off.  `asked`: the caller's flag or the automatic slot count;
 // `envTail`: SLRHIP_TAIL_SLOTS (-1 = unset, 0 = off, n = the bound); `available`: the tail kernel exists for this scene and the
 // build does not count traversal steps; never more than numSlots / `divisor` (SLR_TAIL_DIVISOR of slrhip_api.hip).

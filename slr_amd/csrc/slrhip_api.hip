@@ -315,6 +315,15 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     const WindowPlan window = planWindow(rp.numPixels, sppCount, runLengthOverride());
     rp.sppBegin = sppBegin; rp.sppCount = sppCount;
     rp.workItems = window.workItems; rp.runLength = window.runLength; rp.numRuns = window.numRuns;
+    // the primary pass of the window (render_plan.cpp, planPrimary); its instance plane is allocated before anything is queued
+    const PrimaryPlan primary = planPrimary(rp.numPixels, sppCount, ctx->config.flags, ctx->scene.instances != nullptr, rp.spectral != 0,
+                                            ctx->scene.hasEnv != 0);
+    rp.primary = primary.on ? 1u : 0u;
+    pb.primaryInstance = nullptr;
+    if (primary.instanceEntries) {
+        HIP_TRY(ctx->primaryInstance.alloc((size_t)primary.instanceEntries));
+        pb.primaryInstance = ctx->primaryInstance.ptr;
+    }
     // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
     // it is asked for zero passes
     launchResetSlots(pb, rp, ctx->firstRenderCall, stream);
@@ -336,6 +345,21 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     }
     static const char* iterLogPath = getenv("SLRHIP_ITER_LOG");
     std::vector<IterationTimes> iterLog;
+
+    // The primary pass: every camera ray of the window, on the caller's stream after the reset (which clears the error word) and
+    // before the iterations; a launch takes as many whole passes as stay under 2^31 samples.  With SLRHIP_FLAG_TIME_KERNELS its
+    // launches and event time are booked under SLRHIP_KERNEL_TRACE (read once the window's stream work is complete, below).
+    struct PrimaryTimer {
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        ~PrimaryTimer() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
+    } primaryTimer;
+    if (primary.on) {
+        if (timeKernels) { HIP_TRY(hipEventCreate(&primaryTimer.t0)); HIP_TRY(hipEventCreate(&primaryTimer.t1)); HIP_TRY(hipEventRecord(primaryTimer.t0, stream)); }
+        for (uint32_t first = 0; first < sppCount; first += primary.passesPerLaunch)
+            launchPrimary(ctx->scene, pb, rp, first, std::min(primary.passesPerLaunch, sppCount - first), ctx->numCUs, stream);
+        if (timeKernels) HIP_TRY(hipEventRecord(primaryTimer.t1, stream));
+        HIP_TRY(hipGetLastError());
+    }
 
     // The block of kCheckEvery iterations is the same sequence of launches every time (the parity alternates inside it and is
     // back to 0 at its end), so it is captured ONCE per window into a hipGraph and replayed: one submission per block instead
@@ -382,7 +406,13 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
         if (it > maxIterations) return fail(SLRHIP_ERR_HIP, "slrhip_render: iteration bound exceeded (internal error)");
     }
     ctx->iterations += it;
-    launchCountSamples(pb, rp, s);       // samples rendered in this window, counted on the device (T_SAMPLES)
+    if (primary.on && timeKernels) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, primaryTimer.t0, primaryTimer.t1));       // complete: the loop above waited for work queued after it
+        ctx->profMs[SLRHIP_KERNEL_TRACE] += ms;
+        ctx->profLaunches[SLRHIP_KERNEL_TRACE] += primary.numLaunches;
+    }
+    launchCountSamples(pb, rp, s);     // samples rendered in this window, counted on the device (T_SAMPLES)
     const ClampParams clamp = clampParams(ctx);                                          // slrhip_clamp_begin: every sample through the clamp first
     if (active) launchFoldIndexed(pb, rp, ctx->stats.records.ptr, active->index, clamp, s);       // the same, scattered to the list's pixels of the shard
     else launchFold(pb, rp, ctx->stats.on ? ctx->stats.records.ptr : nullptr, clamp, s);       // sensor->add, in pass order (+ the noise records)
@@ -639,6 +669,17 @@ int slrhip_get_profile(slrhip_ctx* ctx, slrhip_profile* out) {
         out->nodes[1] = t[T_NODES_SHADOW]; out->triangles[1] = t[T_TRIS_SHADOW];
         out->slot_visits = t[T_SLOT_VISITS];
     }
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): samples whose first hit came from the primary pass's record, as the kernels counted them.
+int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples) {
+    if (!ctx || !samples) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_samples: null argument");
+    *samples = 0;
+    if (!ctx->haveRender) return SLRHIP_OK;
+    uint64_t t[T_KINDS];
+    if (const int rc = readTotals(ctx, t)) return rc;
+    *samples = t[T_PRIMARY_STARTS];
     return SLRHIP_OK;
 }
 

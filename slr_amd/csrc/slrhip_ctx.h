@@ -129,6 +129,7 @@ struct slrhip_ctx {
     DevArray<float> pdfPrev;
     DevArray<uint4> hdr;
     DevArray<int32_t> hitInstance;
+    DevArray<int32_t> primaryInstance;            // instanced scenes: the instance plane of the primary pass, one entry per sample of the window (renderWindow)
     DevArray<uint32_t> flags, visible, shadowQueue, tailList, queueCount, activeSlots, blockDead;
     DevArray<uint64_t> totals;
     DevArray<float> resolveScratch;

@@ -142,6 +142,14 @@ int slrhip_debug_render_plan(int32_t width, int32_t height, uint32_t shardIndex,
     return SLRHIP_OK;
 }
 
+// Diagnostic (include/slrhip_debug.h): the primary pass of a window as renderWindow plans it.
+int slrhip_debug_primary_plan(uint32_t numPixels, uint32_t numPasses, uint32_t configFlags, int32_t sceneClass, uint32_t* plan) {
+    if (!plan) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_plan: null argument");
+    const PrimaryPlan p = planPrimary(numPixels, numPasses, configFlags, (sceneClass & 1) != 0, (sceneClass & 2) != 0, (sceneClass & 4) != 0);
+    plan[0] = p.on ? 1u : 0u; plan[1] = p.passesPerLaunch; plan[2] = p.numLaunches; plan[3] = p.instanceEntries ? 1u : 0u;
+    return SLRHIP_OK;
+}
+
 int slrhip_bsdf_queries(slrhip_ctx* ctx, uint32_t material, uint32_t n, const float* queries, float wl_offset, float u_lambda, float* out) {
     if (!ctx || !queries || !out) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_bsdf_queries: null argument");
     if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_bsdf_queries: no scene uploaded");
