@@ -1066,6 +1066,58 @@ int slrhip_env_importance(int32_t mode, const float* texels, uint32_t width, uin
  * range, another mode, or too little room.                                                                                          */
 int slrhip_env_texels_to_uvs(const float* rgb, size_t num_texels, float* uvs);
 
+/* ---- moving instances and the camera without a scene upload ----------------------------------------------------------------------------
+ * A second frame of the same scene with something moved: new StaticTransforms for TransformedSurfaceObjects that exist
+ * (Core/SurfaceObject.cpp:303-392, Transform.h:38-87) and a new PerspectiveCamera (Cameras/PerspectiveCamera.cpp:15-24), with no
+ * descriptor check, no copy of the geometry and no tree build.
+ *
+ * slrhip_set_instance_transforms gives the instances [first_instance, first_instance + count) of the UPLOADED scene the matrices of
+ * `device_src`: DEVICE memory, 16-byte aligned, `count` records.  Both matrices are the caller's, column-major, as in slrhip_instance
+ * (the reference inverts in float, so the inverse is a scene input).  Meshes, triangle ranges and the number of instances stay.
+ *
+ * The contract.  From the call on, the context renders, answers ray queries and fills feature buffers exactly as a fresh context does
+ * that uploaded the scene with the new matrices: every bit of the frame, of the hits and of the counters.  The top-level tree keeps
+ * its SHAPE and gets new child boxes (a refit on the device, bottom-up); hits do not depend on the tree's shape because the tie rule
+ * among equal distances is a rule on (instance, triangle) pairs.  Speed does depend on it: after large motion the tree fits the scene
+ * badly and rays visit more nodes (DESIGN.md has the measured factor); a caller for whom that matters uploads the scene again.
+ *
+ * A record is checked on the device as slrhip_upload_scene checks an instance: every entry finite, bottom rows 0 0 0 1.  A record
+ * that fails leaves ITS instance exactly as it was (matrices and box), the others of the call move, and SLRHIP_INSTANCE_BAD_TRANSFORM
+ * is set in a status word that slrhip_instances_status reads and clears (it waits for `stream`).
+ *
+ * Ordering.  The call allocates nothing, copies nothing from the host and does not synchronise; its launches are ordered on `stream`.
+ * A render, query or feature pass enqueued after it on the same stream sees the new placement; the caller's buffer is free once the
+ * stream has passed the call.  slrhip_render blocks until its passes are done, so no render is in flight when the call is made.
+ * NOTHING accumulated is reset: the frame, the feature buffers, the albedo and the statistics since slrhip_render_begin stay, and
+ * samples rendered after the call see the new placement.  Starting the new frame is the caller's slrhip_render_begin.
+ *
+ * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, count == 0, a misaligned
+ * pointer (16 bytes), a range beyond slrhip_scene_desc::num_instances.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.
+ * SLRHIP_ERR_UNSUPPORTED for a scene without instances.  Not covered: adding or removing instances, instances that emit, moving
+ * loose triangles, a rebuild of the top level.                                                                                     */
+#define SLRHIP_INSTANCE_BAD_TRANSFORM 1u   /* a record of a call had a non-finite entry or a bottom row other than 0 0 0 1; its instance did not move */
+typedef struct slrhip_instance_transform {
+    float local_to_world[16];
+    float world_to_local[16];
+} slrhip_instance_transform;               /* 128 B, column-major */
+int slrhip_set_instance_transforms(slrhip_ctx* ctx, const slrhip_instance_transform* device_src, uint32_t first_instance, uint32_t count,
+                                   void* stream);
+/* The SLRHIP_INSTANCE_* bits of the calls since the last read, then cleared; waits for `stream`.  0 before any scene.              */
+int slrhip_instances_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
+
+/* The world box the top-level tree holds for an instance: the box of the eight corners of the mesh's local box [mesh_lo, mesh_hi]
+ * taken through local_to_world (StaticTransform x BoundingBox3D, Transform.h:54-65), padded per axis by
+ * 1e-5f * max(1, |lo|, |hi|).  On the HOST (pure), with the function the upload and the kernel call.  lo, hi: 3 floats each.        */
+int slrhip_instance_world_box(const float mesh_lo[3], const float mesh_hi[3], const float local_to_world[16], float out_lo[3],
+                              float out_hi[3]);
+
+/* Replaces the camera of the UPLOADED scene: the same host arithmetic as slrhip_upload_scene's camera constants, written into the
+ * context and nothing else; no device call is made.  Launches enqueued after the call see the new camera (slrhip_render,
+ * slrhip_camera_rays, the feature and albedo passes); nothing accumulated is reset — starting the new frame is the caller's
+ * slrhip_render_begin.  The image size is slrhip_render_begin's, so `aspect` should agree with it as it does at upload.
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.                                  */
+int slrhip_set_camera(slrhip_ctx* ctx, const slrhip_camera* camera);
+
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */
 enum { SLRHIP_SPECTRUMTYPE_REFLECTANCE = 0, SLRHIP_SPECTRUMTYPE_ILLUMINANT = 1, SLRHIP_SPECTRUMTYPE_IOR = 2 };

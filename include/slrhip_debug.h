@@ -78,6 +78,28 @@ int slrhip_debug_environment_check(const slrhip_environment_desc* desc);
  * path keeps no map).                                                                                                              */
 int slrhip_debug_environment(slrhip_ctx* ctx, uint32_t what, float* host_dst, size_t num_floats);
 
+/* The argument checks of slrhip_set_instance_transforms (slr_amd/csrc/render_plan.h, instanceUpdateRefusal), evaluated on the HOST with
+ * the function the entry point calls, for a context that holds a scene (have_scene != 0) of `num_instances` instances or none: SLRHIP_OK
+ * if the call would go ahead, else the code it returns, with the reason in slrhip_last_error_string.  The pointer is only compared,
+ * never followed.  No GPU is touched.                                                                                               */
+int slrhip_debug_instance_update_check(int32_t have_scene, uint32_t num_instances, const void* device_src, uint32_t first_instance,
+                                       uint32_t count);
+
+/* The top level of the context's instanced scene, read back to HOST memory as 32-bit words.  what:
+ *   0  the top-level QNodes, 32 words each: minx[4] miny[4] minz[4] maxx[4] maxy[4] maxz[4] (floats), child[4], pad[4]
+ *   1  32 words: [0] levels of the top-level tree, [1] its nodes, [2] all nodes of the scene (the mesh trees follow the top level),
+ *      [3] instances, [4] distinct meshes, [5] the widest level one workgroup of the refit takes (wider levels: a launch each),
+ *      [8 .. 8 + levels] the first node of each level, then [1] again
+ *   2  the DevInstance records, 36 words each: local_to_world[16], world_to_local[16] (floats), root node, first triangle,
+ *      triangle count, mesh
+ *   3  the instances' world boxes, 8 words each: lo[3], 0, hi[3], 0 (floats)
+ *   4  every QNode of the scene (what 0's layout)
+ *   5  the meshes' local boxes (what 3's layout)
+ * num_words: room at host_dst, at least that many.  Synchronises.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene,
+ * SLRHIP_ERR_UNSUPPORTED for a scene without instances, SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too
+ * little room.                                                                                                                      */
+int slrhip_debug_top_level(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
+
 /* The caller's samples through the fold: host_samples is [passes][height][width][components] float32 (HOST memory), passes 1 .. 64.
  * The shard's pixels are reordered with the context's own pixel list into a result window (pass-major, as the render kernels
  * write it; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's

@@ -31,6 +31,9 @@ spectrum_dtype = np.dtype([("kind", "<u4"), ("rgb", "<f4", 3), ("u", "<f4"), ("v
 texture_dtype = np.dtype([("kind", "<u4"), ("offset", "<f4", 2), ("scale", "<f4", 2), ("spectrum", "<i4", 2), ("value", "<f4", 2),
                           ("reserved", "<u4", 3)])
 instance_dtype = np.dtype([("first_triangle", "<u4"), ("num_triangles", "<u4"), ("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16)])
+# slrhip_set_instance_transforms: one 128-byte slrhip_instance_transform per moved instance (a [n, 32] float32 array has the same bytes)
+instance_transform_dtype = np.dtype([("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16)])
+INSTANCE_BAD_TRANSFORM = 1      # slrhip_instances_status: a record was not finite or not affine; its instance did not move
 TEX_CHECKER_SPECTRUM, TEX_CHECKER_FLOAT, TEX_CHECKER_NORMAL, TEX_IMAGE_SPECTRUM = 0, 1, 2, 3
 # ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): one [n, 8] float32 row per slrhip_ray, one [n, 4]
 # row per slrhip_hit (column 0 holds the triangle index's bits)

@@ -21,6 +21,8 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_render_albedo", "slrhip_resolve_albedo", "slrhip_read_albedo", "slrhip_modulate", "slrhip_debug_modulate_check",
            "slrhip_clamp_begin", "slrhip_resolve_clamp", "slrhip_read_clamp", "slrhip_clamp_summary", "slrhip_clamp_sample", "slrhip_debug_fold",
            "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
+           "slrhip_set_instance_transforms", "slrhip_instances_status", "slrhip_instance_world_box", "slrhip_set_camera",
+           "slrhip_debug_instance_update_check", "slrhip_debug_top_level",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -124,6 +126,15 @@ def load_library():
                            ("slrhip_env_texels_to_uvs", [C.c_void_p, C.c_size_t, C.c_void_p]),
                            ("slrhip_debug_environment_check", [C.POINTER(abi.EnvironmentDesc)]),
                            ("slrhip_debug_environment", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before instances and the camera could move lacks these six)
+    for name, argtypes in (("slrhip_set_instance_transforms", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_instances_status", [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+                           ("slrhip_instance_world_box", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                           ("slrhip_set_camera", [C.c_void_p, C.POINTER(abi.Camera)]),
+                           ("slrhip_debug_instance_update_check", [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
+                           ("slrhip_debug_top_level", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
@@ -284,6 +295,66 @@ class Context:
         out = np.empty(shape, np.float32)
         _check(self.lib, self.lib.slrhip_debug_environment(self.handle, what, out.ctypes.data, out.size), "slrhip_debug_environment")
         return out
+
+    # ---- moving instances and the camera without a scene upload (slrhip_set_instance_transforms / slrhip_set_camera) ----
+    def set_instance_transforms_into(self, device_ptr, first, count, stream=None):
+        """slrhip_set_instance_transforms over a DEVICE pointer (an integer address): `count` 128-byte records, 16-byte aligned, read in
+        order on `stream`; returns at once."""
+        _check(self.lib, self.lib.slrhip_set_instance_transforms(self.handle, device_ptr, first, count, self._stream_handle(stream)),
+               "slrhip_set_instance_transforms")
+
+    def set_instance_transforms(self, transforms, first=0, stream=None):
+        """New matrices for the instances [first, first + n) of the uploaded scene (slrhip_set_instance_transforms): transforms is
+        [n, 32] float32 — per row local_to_world then world_to_local, column-major — or n records of abi.instance_transform_dtype or
+        abi.instance_dtype (its two matrices are taken).  The top-level tree is refitted on the device; nothing accumulated is reset.
+        A torch CUDA tensor (contiguous [n, 32] float32) is passed without a copy and read in order on `stream` (default:
+        torch.cuda.current_stream()); a numpy array is copied to the device first, and that call synchronises.  A record that is
+        not finite or not affine leaves its instance where it was: see instances_status."""
+        if isinstance(transforms, np.ndarray):
+            a = transforms
+            if a.dtype == abi.instance_dtype:
+                a = np.concatenate([a["local_to_world"], a["world_to_local"]], axis=1)
+            elif a.dtype == abi.instance_transform_dtype:
+                a = np.ascontiguousarray(a).view(np.float32)
+            a = np.ascontiguousarray(a, np.float32).reshape(-1, 32)
+            with DeviceBlocks() as dev:
+                self.set_instance_transforms_into(dev.put(a) if len(a) else None, first, len(a), stream)
+                self.synchronize()                     # the staging block is freed on the way out
+            return
+        import torch
+        if not (isinstance(transforms, torch.Tensor) and transforms.is_cuda and transforms.dtype == torch.float32 and transforms.dim() == 2
+                and transforms.shape[1] == 32 and transforms.is_contiguous()):
+            raise ValueError("transforms: a contiguous [n, 32] float32 CUDA tensor (or a numpy array) expected")
+        if transforms.device.index != self.device:
+            raise SlrHipError("set_instance_transforms: the tensor is on device %r, the context on device %d" % (transforms.device.index, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.set_instance_transforms_into(transforms.data_ptr(), first, transforms.shape[0], s)
+
+    def instances_status(self, stream=None):
+        """The abi.INSTANCE_* bits of the set_instance_transforms calls since the last read, then cleared (slrhip_instances_status);
+        waits for `stream` (a torch stream, a raw handle; default: the null stream)."""
+        bits = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_instances_status(self.handle, C.byref(bits), self._stream_handle(stream)), "slrhip_instances_status")
+        return bits.value
+
+    def set_camera(self, camera):
+        """Replaces the camera of the uploaded scene (slrhip_set_camera; an abi.Camera): later launches see it, nothing is reset."""
+        _check(self.lib, self.lib.slrhip_set_camera(self.handle, C.byref(camera)), "slrhip_set_camera")
+
+    def debug_top_level(self):
+        """Diagnostic (slrhip_debug_top_level): the top level of the instanced scene as a dict of numpy arrays — levels (first node of
+        each level, then the number of top-level nodes), group_nodes (the widest level the refit takes in one workgroup), nodes
+        [all nodes, 32] uint32 (QNode words; the first top_nodes are the top level), instances [n, 36] uint32 (DevInstance words),
+        boxes [n, 2, 4] float32 (lo, hi), mesh_boxes [m, 2, 4] float32.  Synchronises."""
+        def read(what, words, dtype=np.uint32):
+            out = np.zeros(words, dtype)
+            _check(self.lib, self.lib.slrhip_debug_top_level(self.handle, what, out.ctypes.data, out.size), "slrhip_debug_top_level")
+            return out
+        head = read(1, 32)
+        levels, top, total, n, meshes = (int(v) for v in head[:5])
+        return dict(levels=head[8:8 + levels + 1].copy(), top_nodes=top, group_nodes=int(head[5]), nodes=read(4, total * 32).reshape(total, 32),
+                    instances=read(2, n * 36).reshape(n, 36), boxes=read(3, n * 8, np.float32).reshape(n, 2, 4),
+                    mesh_boxes=read(5, meshes * 8, np.float32).reshape(meshes, 2, 4))
 
     def render_begin(self, settings, shard=(0, 1)):
         _check(self.lib, self.lib.slrhip_render_begin(self.handle, C.byref(settings), abi.Shard(*shard)), "slrhip_render_begin")
@@ -773,6 +844,19 @@ class Context:
         self.render_begin(settings, shard)
         self.render(0, spp)
         return self.read_framebuffer()
+
+
+def instance_world_box(mesh_lo, mesh_hi, local_to_world):
+    """The world box the top-level tree holds for an instance (slrhip_instance_world_box: the function the upload and the kernel of
+    set_instance_transforms call): (lo, hi), float32 [3] each, of the mesh's local box taken through the column-major matrix."""
+    lib = load_library()
+    lo, hi, m = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (mesh_lo, mesh_hi, local_to_world))
+    if len(lo) != 3 or len(hi) != 3 or len(m) != 16:
+        raise ValueError("instance_world_box: mesh_lo [3], mesh_hi [3], local_to_world [16] expected")
+    out_lo, out_hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    if lib.slrhip_instance_world_box(lo.ctypes.data, hi.ctypes.data, m.ctypes.data, out_lo.ctypes.data, out_hi.ctypes.data) != 0:
+        raise ValueError("instance_world_box: refused")
+    return out_lo, out_hi
 
 
 def env_importance(texels, mode=abi.MODE_RGB):

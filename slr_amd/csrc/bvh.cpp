@@ -8,6 +8,7 @@
 // opening the child with the largest surface area, emitted in breadth-first order so that the
 // first K nodes are the top of the tree (the part the traversal kernel stages in LDS).
 #include "bvh.h"
+#include "pt_instance.h"
 
 #include <sched.h>
 #include <stdio.h>
@@ -335,6 +336,7 @@ int buildQBVHPrims(const slrhip_vertex* verts, const slrhip_triangle* tris, cons
         out->nodes.push_back(qn);
         kidsOf.push_back({{0, 0, 0, 0}});
         out->depth = 1;
+        depthOf.push_back(1);
     }
     else {
         out->nodes.reserve(b.nodes.size() / 2 + 1);
@@ -387,6 +389,9 @@ int buildQBVHPrims(const slrhip_vertex* verts, const slrhip_triangle* tris, cons
     }
     auto tD = std::chrono::steady_clock::now();
     out->leafTris.resize(leafCursor);
+    out->levelFirst.clear();            // breadth-first order: depthOf never decreases
+    for (size_t qi = 0; qi < depthOf.size(); ++qi)
+        if (depthOf[qi] > out->levelFirst.size()) out->levelFirst.push_back((uint32_t)qi);
 
     auto fill = [&](size_t lo, size_t hi) {
         for (size_t qi = lo; qi < hi; ++qi) {
@@ -506,16 +511,6 @@ int buildQBVHPrims(const slrhip_vertex* verts, const slrhip_triangle* tris, cons
 }
 } // namespace
 
-// Matrix4x4 x Point3D (Matrix4x4.h:75-81), column-major m
-static void mulPointHost(const float* m, const float* p, float* o) {
-    float x = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12] * 1.0f;
-    float y = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13] * 1.0f;
-    float z = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14] * 1.0f;
-    float w = m[3] * p[0] + m[7] * p[1] + m[11] * p[2] + m[15] * 1.0f;
-    if (w != 1.0f) { float r = 1.0f / w; x *= r; y *= r; z *= r; }
-    o[0] = x; o[1] = y; o[2] = z;
-}
-
 int buildInstancedQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, uint32_t numTris, const slrhip_instance* instances, uint32_t numInstances,
                        QBVH* out, std::vector<DevInstance>* devInstances, std::string* err) {
     if (!verts || !tris || numTris == 0 || numTris > kLeafIndexMask || !instances || numInstances == 0 || numInstances > kLeafIndexMask) { *err = "bad arguments"; return 1; }
@@ -529,8 +524,9 @@ int buildInstancedQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, 
         if (in.num_triangles == 0 || (uint64_t)in.first_triangle + in.num_triangles > numTris) { *err = "instance names triangles out of range"; return 1; }
         for (int r = 0; r < 2; ++r) {
             const float* m = r ? in.world_to_local : in.local_to_world;
-            if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f) { *err = "instance transforms must be affine (bottom row 0 0 0 1)"; return 1; }
-            for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) { *err = "instance transform is not finite"; return 1; }
+            const int bad = instMatrixRefusal(m);          // pt_instance.h: the checks k_instance_place makes of a new placement
+            if (bad == 1) { *err = "instance transforms must be affine (bottom row 0 0 0 1)"; return 1; }
+            if (bad == 2) { *err = "instance transform is not finite"; return 1; }
         }
         uint32_t m = 0;
         for (; m < meshes.size(); ++m) if (meshes[m].first == in.first_triangle && meshes[m].count == in.num_triangles) break;
@@ -554,27 +550,19 @@ int buildInstancedQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, 
         }
         meshOf[k] = m;
     }
-    // bounds() of a TransformedSurfaceObject = StaticTransform x BoundingBox3D (Transform.h:54-65): the box of the eight transformed
-    // corners of the mesh's box; a hair of slack because the local-space traversal rounds differently from a world-space box test
+    // bounds() of a TransformedSurfaceObject: pt_instance.h, shared with the kernel that moves a placement
     std::vector<Box> instBoxes(numInstances);
     for (uint32_t k = 0; k < numInstances; ++k) {
         const Box& mb = meshes[meshOf[k]].box;
-        Box wb; wb.reset();
-        for (int c = 0; c < 8; ++c) {
-            const float p[3] = {(c & 4) ? mb.hi[0] : mb.lo[0], (c & 2) ? mb.hi[1] : mb.lo[1], (c & 1) ? mb.hi[2] : mb.lo[2]};
-            float q[3];
-            mulPointHost(instances[k].local_to_world, p, q);
-            wb.grow(q);
-        }
-        for (int a = 0; a < 3; ++a) {
-            const float pad = 1e-5f * std::fmax(1.0f, std::fmax(std::fabs(wb.lo[a]), std::fabs(wb.hi[a])));
-            wb.lo[a] -= pad; wb.hi[a] += pad;
-        }
-        instBoxes[k] = wb;
+        instanceWorldBox(mb.lo, mb.hi, instances[k].local_to_world, instBoxes[k].lo, instBoxes[k].hi);
     }
     std::vector<uint32_t> loose;
     for (uint32_t i = 0; i < numTris; ++i) if (!instanced[i]) loose.push_back(i);
     if (buildQBVHPrims(verts, tris, loose.data(), (uint32_t)loose.size(), instBoxes, out, false, false) != 0) { *err = "top-level tree build failed"; return 1; }
+    out->topNodes = (uint32_t)out->nodes.size();
+    out->instBoxes = instBoxes;
+    out->meshBoxes.clear();
+    for (const Mesh& mesh : meshes) out->meshBoxes.push_back(mesh.box);
     // the mesh trees go behind the top-level tree in the same arrays; their inner child indices and leaf packets are rebased
     uint32_t maxMeshDepth = 0;
     for (size_t m = 0; m < meshes.size(); ++m) {

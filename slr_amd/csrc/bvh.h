@@ -9,18 +9,6 @@
 
 namespace slrhip {
 
-struct QBVH {
-    std::vector<QNode> nodes;        // breadth-first; nodes[0] is the root
-    std::vector<QNodeQ> quantized;   // same nodes, 8-bit child boxes (quantizeNodes); empty unless asked for
-    std::vector<QNode8> nodes8;      // the same binary tree collapsed to eight-wide quantized nodes (buildQBVH's wide8 argument); same leaf packets
-    uint32_t depth8 = 0;
-    std::vector<LeafTri> leafTris;   // leaf packets, contiguous per leaf
-    uint32_t depth = 0;              // levels of 4-wide nodes
-    uint64_t spatialSplits = 0;      // spatial-split build only: splits in space, and leaf references (>= triangles: duplicates)
-    uint64_t references = 0;
-};
-
-// ---- binary builders: both produce BNode arrays + a primitive list that buildQBVH collapses to 4-wide nodes --------------------
 struct Box {
     float lo[3], hi[3];
     void reset() { for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; } }
@@ -32,6 +20,24 @@ struct Box {
         return 2.0f * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
     }
 };
+
+struct QBVH {
+    std::vector<QNode> nodes;        // breadth-first; nodes[0] is the root
+    std::vector<QNodeQ> quantized;   // same nodes, 8-bit child boxes (quantizeNodes); empty unless asked for
+    std::vector<QNode8> nodes8;      // the same binary tree collapsed to eight-wide quantized nodes (buildQBVH's wide8 argument); same leaf packets
+    uint32_t depth8 = 0;
+    std::vector<LeafTri> leafTris;   // leaf packets, contiguous per leaf
+    uint32_t depth = 0;              // levels of 4-wide nodes
+    std::vector<uint32_t> levelFirst;   // first node of each level of the tree built last (breadth-first: a level is a run of nodes); instanced: the top level's
+    // instanced builds (buildInstancedQBVH): what slrhip_set_instance_transforms refits the top level from
+    uint32_t topNodes = 0;           // nodes of the top-level tree, which come first in `nodes`
+    std::vector<Box> meshBoxes;      // local-space box of each distinct mesh, indexed by DevInstance::mesh
+    std::vector<Box> instBoxes;      // world box of each instance (pt_instance.h, instanceWorldBox)
+    uint64_t spatialSplits = 0;      // spatial-split build only: splits in space, and leaf references (>= triangles: duplicates)
+    uint64_t references = 0;
+};
+
+// ---- binary builders: both produce BNode arrays + a primitive list that buildQBVH collapses to 4-wide nodes --------------------
 
 struct BNode {
     Box box;

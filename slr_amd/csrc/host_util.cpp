@@ -11,6 +11,7 @@
 #include "cmf16_table.h"
 #include "pt_clamp.h"
 #include "pt_envmap.h"
+#include "pt_instance.h"
 #include "pt_luminance.h"
 #include "pt_tonemap.h"
 #include "cmf_2deg_table.h"
@@ -306,6 +307,13 @@ int slrhip_env_importance(int32_t mode, const float* texels, uint32_t width, uin
                                                                        : slrhip::envImportanceUVS(avg[0], avg[1], avg[2]);
         }
     }
+    return SLRHIP_OK;
+}
+
+// The world box of an instance, as buildInstancedQBVH and k_instance_place compute it (pt_instance.h: the same function).
+int slrhip_instance_world_box(const float* meshLo, const float* meshHi, const float* localToWorld, float* outLo, float* outHi) {
+    if (!meshLo || !meshHi || !localToWorld || !outLo || !outHi) return SLRHIP_ERR_INVALID_ARGUMENT;
+    slrhip::instanceWorldBox(meshLo, meshHi, localToWorld, outLo, outHi);
     return SLRHIP_OK;
 }
 

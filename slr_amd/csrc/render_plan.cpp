@@ -263,6 +263,17 @@ const char* environmentRefusal(const slrhip_environment_desc& d) {
     return nullptr;
 }
 
+int instanceUpdateRefusal(bool haveScene, uint32_t numInstances, const void* deviceSrc, uint32_t first, uint32_t count, const char** what) {
+    if (!deviceSrc) { *what = "null device_src"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if ((uintptr_t)deviceSrc & 15u) { *what = "misaligned device_src (16 bytes)"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (count == 0) { *what = "count must be >= 1"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (!haveScene) { *what = "no scene uploaded"; return SLRHIP_ERR_NO_SCENE; }
+    if (numInstances == 0) { *what = "the scene has no instances"; return SLRHIP_ERR_UNSUPPORTED; }
+    if (first >= numInstances || count > numInstances - first) { *what = "first_instance + count is beyond the scene's instances"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    *what = nullptr;
+    return SLRHIP_OK;
+}
+
 } // namespace slrhip
 
 extern "C" size_t slrhip_tonemap_bytes(uint32_t width, uint32_t height, uint32_t format) {

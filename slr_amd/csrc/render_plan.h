@@ -108,5 +108,8 @@ const char* modulateRefusal(const slrhip_modulate_desc& d);
 // The argument checks of slrhip_set_environment on the descriptor (the pointer is only compared, never followed): nullptr if the
 // call goes ahead, else what is wrong with it.  What depends on the context (no scene, no upsampling tables) is the entry point's.
 const char* environmentRefusal(const slrhip_environment_desc& d);
+// The argument checks of slrhip_set_instance_transforms against what the context holds (a scene or none, its number of instances; the
+// pointer is only compared, never followed): SLRHIP_OK if the call goes ahead, else the code it returns with *what = what is wrong.
+int instanceUpdateRefusal(bool haveScene, uint32_t numInstances, const void* deviceSrc, uint32_t first, uint32_t count, const char** what);
 
 } // namespace slrhip

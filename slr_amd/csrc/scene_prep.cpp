@@ -477,23 +477,6 @@ void prepareUpsampling(const slrhip_scene_desc& d, PreparedScene& p) {
     p.gridWidth = t->grid_width; p.gridHeight = t->grid_height;
 }
 
-// --- camera constants, PerspectiveCamera.cpp:15-24, :55 -------------------------------------------------------------------------
-DevCamera prepareCamera(const slrhip_camera& c) {
-    DevCamera cam;
-    std::memcpy(cam.mat, c.local_to_world, sizeof(cam.mat));
-    std::memcpy(cam.matInv, c.world_to_local, sizeof(cam.matInv));
-    cam.lensRadius = c.lens_radius;
-    cam.imgPlaneDistance = c.img_plane_distance;
-    cam.objPlaneDistance = c.obj_plane_distance;
-    cam.opHeight = 2.0f * cam.objPlaneDistance * std::tan(c.fov_y * 0.5f);
-    cam.opWidth = cam.opHeight * c.aspect;
-    cam.imgPlaneArea = (float)((double)(cam.opWidth * cam.opHeight) * std::pow((double)(cam.imgPlaneDistance / cam.objPlaneDistance), 2.0));
-    cam.areaPDF = cam.lensRadius > 0.0f ? (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius)) : 1.0f;
-    cam.sensitivity = c.sensitivity > 0 ? c.sensitivity
-                                        : (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius));
-    return cam;
-}
-
 // --- the tables the shade kernels stage in LDS, packed in the order of ShadeLds' segments (DevScene::shadeTables) ---------------
 void packShadeTables(bool spectral, PreparedScene& p) {
     p.tablesFit = p.materials.size() <= (size_t)kLdsMaterials && p.lightTris.size() <= (size_t)kLdsLights &&
@@ -520,6 +503,23 @@ void packShadeTables(bool spectral, PreparedScene& p) {
 }
 
 } // namespace
+
+// --- camera constants, PerspectiveCamera.cpp:15-24, :55 -------------------------------------------------------------------------
+DevCamera prepareCamera(const slrhip_camera& c) {
+    DevCamera cam;
+    std::memcpy(cam.mat, c.local_to_world, sizeof(cam.mat));
+    std::memcpy(cam.matInv, c.world_to_local, sizeof(cam.matInv));
+    cam.lensRadius = c.lens_radius;
+    cam.imgPlaneDistance = c.img_plane_distance;
+    cam.objPlaneDistance = c.obj_plane_distance;
+    cam.opHeight = 2.0f * cam.objPlaneDistance * std::tan(c.fov_y * 0.5f);
+    cam.opWidth = cam.opHeight * c.aspect;
+    cam.imgPlaneArea = (float)((double)(cam.opWidth * cam.opHeight) * std::pow((double)(cam.imgPlaneDistance / cam.objPlaneDistance), 2.0));
+    cam.areaPDF = cam.lensRadius > 0.0f ? (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius)) : 1.0f;
+    cam.sensitivity = c.sensitivity > 0 ? c.sensitivity
+                                        : (float)(1.0f / (M_PI * (double)cam.lensRadius * (double)cam.lensRadius));
+    return cam;
+}
 
 int checkTreeLimits(uint32_t depth, uint64_t numNodes, uint64_t numLeafTris, const char* tooDeep, std::string* err) {
     if (3 * depth + 1 > 64) return reject(err, SLRHIP_ERR_UNSUPPORTED, tooDeep);

@@ -54,6 +54,9 @@ struct PreparedScene {
 // Checks the descriptor and derives every host-side record.  Returns SLRHIP_OK, or an SLRHIP_ERR_* code with the message in *err.
 int prepareScene(const slrhip_scene_desc& d, const slrhip_config& config, PreparedScene* out, std::string* err);
 
+// The camera constants (PerspectiveCamera's constructor, libm on the host): slrhip_upload_scene's and slrhip_set_camera's.
+DevCamera prepareCamera(const slrhip_camera& c);
+
 // The traversal kernels' limits on a tree: 3 * depth + 1 entries on the 64-entry stack, nodes and leaf packets addressed with 32-bit
 // byte offsets.  Returns SLRHIP_OK, or SLRHIP_ERR_UNSUPPORTED with *err = "slrhip_upload_scene: " + what (depth) or the size message.
 int checkTreeLimits(uint32_t depth, uint64_t numNodes, uint64_t numLeafTris, const char* tooDeep, std::string* err);

@@ -143,6 +143,20 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     if (p.build != TreeBuild::Device) HIP_TRY(ctx->shadeTris.upload(p.shadeTris));
     HIP_TRY(ctx->lightTris.upload(p.lightTris));
     HIP_TRY(ctx->instances.upload(p.instances));
+    if (!p.instances.empty()) {
+        // what slrhip_set_instance_transforms works from: allocated here, so that the call allocates nothing
+        const auto boxes = [](const std::vector<Box>& v) {
+            std::vector<float4> out;
+            for (const Box& b : v) { out.push_back(make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f)); out.push_back(make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f)); }
+            return out;
+        };
+        HIP_TRY(ctx->meshBoxes.upload(boxes(p.bvh.meshBoxes)));
+        HIP_TRY(ctx->instBoxes.upload(boxes(p.bvh.instBoxes)));
+        HIP_TRY(ctx->instanceStatus.alloc(1));
+        HIP_TRY(hipMemset(ctx->instanceStatus.ptr, 0, sizeof(uint32_t)));
+        ctx->topLevelFirst = p.bvh.levelFirst;
+        ctx->topLevelFirst.push_back(p.bvh.topNodes);
+    }
     HIP_TRY(ctx->materials.upload(p.materials));
     HIP_TRY(ctx->materialsS.upload(p.materialsS));
     HIP_TRY(ctx->spectrumPool.upload(p.spectrumPool));

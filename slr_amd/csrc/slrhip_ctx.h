@@ -1,5 +1,5 @@
 // slrhip_ctx.h — the context behind the C ABI of include/slrhip.h and what its translation units share: slrhip_api.hip,
-// slrhip_buffers.hip, slrhip_image.hip, slrhip_diagnostics.hip.  Internal: not installed.
+// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_diagnostics.hip.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,6 +100,11 @@ struct slrhip_ctx {
     DevArray<slrhip::ShadeTri> shadeTris;
     DevArray<slrhip::LightTri> lightTris;
     DevArray<slrhip::DevInstance> instances;
+    // slrhip_set_instance_transforms: the meshes' local boxes and the instances' world boxes (lo, hi: two float4 each), its status
+    // word, and the top-level tree's extent in `nodes`: the first node of each level, then the number of top-level nodes
+    DevArray<float4> meshBoxes, instBoxes;
+    DevArray<uint32_t> instanceStatus;
+    std::vector<uint32_t> topLevelFirst;
     DevArray<slrhip::DevMaterial> materials;
     DevArray<slrhip::DevMaterialS> materialsS;
     DevArray<slrhip::DevSpectrum> spectra;
