@@ -369,7 +369,9 @@ typedef struct slrhip_profile {
                                          * the host build's 4-wide collapse, quantized nodes): 10 M triangles in a fraction of a second instead of
                                          * seconds on the host cores, at the price of a tree of lower quality (more nodes per ray; DESIGN.md has both
                                          * figures).  Same hits.  Automatic from 2^20 triangles on (SLRHIP_BVH=host in the environment keeps the host build);
-                                         * scenes with alpha-textured triangles, or fewer than 1024 triangles, always use the host build */
+                                         * The flag is a request, honoured only for a scene of AT LEAST 1024 triangles, WITHOUT alpha-textured triangles
+                                         * and WITHOUT instances; every other scene gets the host build, and the upload succeeds without a word.
+                                         * Which builder ran is in the summary of slrhip_debug_tree (include/slrhip_debug.h)              */
 #define SLRHIP_FLAG_TEST_DEVICE_ERROR 16u /* test hook: the next slrhip_render raises the device-side error word, so that the
                                          * error path (SLRHIP_ERR_HIP + message) can be exercised; renders nothing useful */
 #define SLRHIP_FLAG_TIME_KERNELS   1u   /* bracket every launch with HIP events (a few us per launch)        */

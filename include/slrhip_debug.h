@@ -100,6 +100,38 @@ int slrhip_debug_instance_update_check(int32_t have_scene, uint32_t num_instance
  * little room.                                                                                                                      */
 int slrhip_debug_top_level(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
 
+/* The tree builders (slr_amd/csrc/bvh.cpp, sbvh.cpp, bvh_device.hip), as the summary of the two read-outs below names them. */
+#define SLRHIP_TREE_HOST_SAH 0u              /* binned SAH over object partitions, on the host                                    */
+#define SLRHIP_TREE_HOST_SPATIAL_SPLITS 1u   /* the same with spatial splits (SLRHIP_FLAG_BVH_SPATIAL_SPLITS, SLRHIP_BVH=sbvh)   */
+#define SLRHIP_TREE_DEVICE 2u                /* LBVH on the GPU (SLRHIP_FLAG_BVH_DEVICE_BUILD where the scene allows it)          */
+#define SLRHIP_TREE_INSTANCED 3u             /* the two-level build of a scene with instances, on the host                        */
+
+/* The tree of the context's scene — any scene, instanced or not — read back to HOST memory as 32-bit words.  what:
+ *   0  the summary, 16 words: [0] the builder that ran (SLRHIP_TREE_*), [1] nodes, [2] levels as slrhip_counters::bvh_depth reports
+ *      them, [3] leaf references (LeafTri records), [4] triangles, [5] 1 if the quantized nodes are in use, [6] instances,
+ *      [7] nodes of the top level (instanced scenes; else 0), the rest 0
+ *   1  the QNode records, 32 words each (slrhip_debug_top_level's layout)
+ *   2  the QNodeQ records, 16 words each: origin[3], scale[3] (floats), qlo x, y, z, qhi x, y, z (one byte per child, child 0 lowest),
+ *      child[4]; SLRHIP_ERR_UNSUPPORTED when the quantized nodes are not in use
+ *   3  the LeafTri records, 12 words each: v0[3] (floats), triangle, e1[3], alpha record, e2[3], 0
+ *   4  the ShadeTri records, 24 words each: n0[3] (floats), material, n1[3], light, n2[3], 1 / area, t0[3], gn.x, t1[3], gn.y, t2[3], gn.z
+ *   5  the DevInstance records (slrhip_debug_top_level's what 2)        6  the instances' world boxes (its what 3)
+ * num_words: room at host_dst, at least that many.  Synchronises; changes nothing, slrhip_debug_top_level included.
+ * SLRHIP_ERR_NO_SCENE before slrhip_upload_scene, SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room. */
+int slrhip_debug_tree(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
+
+/* The tree the HOST builds for a scene descriptor in an RGB context with slrhip_config::flags `config_flags`, through the prepareScene
+ * that slrhip_upload_scene calls (slr_amd/csrc/scene_prep.h).  `what` and the layouts are slrhip_debug_tree's.  what = 0 prepares the
+ * scene and keeps the result for the calling thread; every other `what` copies from the result kept last (`desc` is not read then, and
+ * may be NULL), so a tree is built once however many arrays are read.  No GPU is touched.  Returns what slrhip_upload_scene would for the
+ * descriptor, with its message; SLRHIP_ERR_UNSUPPORTED, and a message that says so, for a descriptor whose tree prepareScene leaves to
+ * the device build; SLRHIP_ERR_NO_SCENE for what != 0 before a successful what = 0.                                                     */
+int slrhip_debug_host_tree(const slrhip_scene_desc* desc, uint32_t config_flags, uint32_t what, void* host_dst, size_t num_words);
+
+/* The host quantizer (slr_amd/csrc/bvh.cpp, quantizeNodes — the function the upload calls) on the caller's nodes: `n` QNode records in,
+ * `n` QNodeQ records out (the layouts above).  No GPU is touched.                                                                       */
+int slrhip_debug_quantize_nodes(const void* nodes, uint32_t n, void* nodes_q);
+
 /* The caller's samples through the fold: host_samples is [passes][height][width][components] float32 (HOST memory), passes 1 .. 64.
  * The shard's pixels are reordered with the context's own pixel list into a result window (pass-major, as the render kernels
  * write it; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's

@@ -33,7 +33,19 @@ texture_dtype = np.dtype([("kind", "<u4"), ("offset", "<f4", 2), ("scale", "<f4"
 instance_dtype = np.dtype([("first_triangle", "<u4"), ("num_triangles", "<u4"), ("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16)])
 # slrhip_set_instance_transforms: one 128-byte slrhip_instance_transform per moved instance (a [n, 32] float32 array has the same bytes)
 instance_transform_dtype = np.dtype([("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16)])
-INSTANCE_BAD_TRANSFORM = 1      # slrhip_instances_status: a record was not finite or not affine; its instance did not move
+# the tree read-outs (slrhip_debug_tree / slrhip_debug_host_tree / slrhip_debug_quantize_nodes): the records of slr_amd/csrc/device_types.h.
+# lo / hi are [axis][child]; qlo / qhi one byte per child; a leaf reference is LEAF_FLAG | count << 27 | first LeafTri (count 0: an instance)
+qnode_dtype = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("child", "<u4", 4), ("pad", "<u4", 4)])
+qnodeq_dtype = np.dtype([("origin", "<f4", 3), ("scale", "<f4", 3), ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("child", "<u4", 4)])
+leaftri_dtype = np.dtype([("v0", "<f4", 3), ("tri", "<u4"), ("e1", "<f4", 3), ("alpha", "<u4"), ("e2", "<f4", 3), ("pad", "<u4")])
+shadetri_dtype = np.dtype([("n0", "<f4", 3), ("material", "<u4"), ("n1", "<f4", 3), ("light", "<i4"), ("n2", "<f4", 3), ("area_pdf", "<f4"),
+                           ("t0", "<f4", 3), ("gnx", "<f4"), ("t1", "<f4", 3), ("gny", "<f4"), ("t2", "<f4", 3), ("gnz", "<f4")])
+devinstance_dtype = np.dtype([("local_to_world", "<f4", 16), ("world_to_local", "<f4", 16), ("root", "<u4"), ("first_triangle", "<u4"),
+                              ("num_triangles", "<u4"), ("mesh", "<u4")])
+INVALID_CHILD, LEAF_FLAG, LEAF_COUNT_SHIFT, LEAF_INDEX_MASK, MAX_LEAF_TRIS = 0xFFFFFFFF, 0x80000000, 27, (1 << 27) - 1, 4
+TREE_HOST_SAH, TREE_HOST_SPATIAL_SPLITS, TREE_DEVICE, TREE_INSTANCED = 0, 1, 2, 3
+TREE_BUILDERS = ("host SAH", "host spatial splits", "device", "instanced")
+INSTANCE_BAD_TRANSFORM = 1     # slrhip_instances_status: a record was not finite or not affine; its instance did not move
 TEX_CHECKER_SPECTRUM, TEX_CHECKER_FLOAT, TEX_CHECKER_NORMAL, TEX_IMAGE_SPECTRUM = 0, 1, 2, 3
 # ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): one [n, 8] float32 row per slrhip_ray, one [n, 4]
 # row per slrhip_hit (column 0 holds the triangle index's bits)

@@ -23,6 +23,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
            "slrhip_set_instance_transforms", "slrhip_instances_status", "slrhip_instance_world_box", "slrhip_set_camera",
            "slrhip_debug_instance_update_check", "slrhip_debug_top_level",
+           "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -135,6 +136,12 @@ def load_library():
                            ("slrhip_set_camera", [C.c_void_p, C.POINTER(abi.Camera)]),
                            ("slrhip_debug_instance_update_check", [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
                            ("slrhip_debug_top_level", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before the tree read-outs lacks these three)
+    for name, argtypes in (("slrhip_debug_tree", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_debug_host_tree", [C.POINTER(abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+                           ("slrhip_debug_quantize_nodes", [C.c_void_p, C.c_uint32, C.c_void_p])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
@@ -355,6 +362,12 @@ class Context:
         return dict(levels=head[8:8 + levels + 1].copy(), top_nodes=top, group_nodes=int(head[5]), nodes=read(4, total * 32).reshape(total, 32),
                     instances=read(2, n * 36).reshape(n, 36), boxes=read(3, n * 8, np.float32).reshape(n, 2, 4),
                     mesh_boxes=read(5, meshes * 8, np.float32).reshape(meshes, 2, 4))
+
+    def debug_tree(self, summary_only=False):
+        """Diagnostic (slrhip_debug_tree): the tree of the uploaded scene, whichever builder made it, as the dict _read_tree describes
+        (summary_only: without the arrays, and without a synchronisation).  tree["builder_name"] says which builder ran."""
+        return _read_tree(self.lib, lambda what, ptr, words: self.lib.slrhip_debug_tree(self.handle, what, ptr, words), "slrhip_debug_tree",
+                          summary_only)
 
     def render_begin(self, settings, shard=(0, 1)):
         _check(self.lib, self.lib.slrhip_render_begin(self.handle, C.byref(settings), abi.Shard(*shard)), "slrhip_render_begin")
@@ -844,6 +857,47 @@ class Context:
         self.render_begin(settings, shard)
         self.render(0, spp)
         return self.read_framebuffer()
+
+
+def _read_tree(lib, call, symbol, summary_only=False):
+    """The arrays of a tree read-out as numpy structured arrays (abi.*_dtype): builder (an abi.TREE_* value) and builder_name, num_nodes,
+    depth, leaf_references, num_triangles, quantized, num_instances, top_nodes; nodes, nodes_q (None unless quantized), leaf_tris,
+    shade_tris, instances, instance_boxes [n, 2, 4] float32 (lo, hi)."""
+    def read(what, count, dtype):
+        out = np.zeros(count, dtype)
+        _check(lib, call(what, out.ctypes.data, out.nbytes // 4), symbol)
+        return out
+    s = [int(v) for v in read(0, 16, np.uint32)]
+    tree = dict(builder=s[0], builder_name=abi.TREE_BUILDERS[s[0]], num_nodes=s[1], depth=s[2], leaf_references=s[3], num_triangles=s[4],
+                quantized=bool(s[5]), num_instances=s[6], top_nodes=s[7])
+    if summary_only:
+        return tree
+    tree["nodes"] = read(1, s[1], abi.qnode_dtype)
+    tree["nodes_q"] = read(2, s[1], abi.qnodeq_dtype) if s[5] else None
+    tree["leaf_tris"] = read(3, s[3], abi.leaftri_dtype)
+    tree["shade_tris"] = read(4, s[4], abi.shadetri_dtype)
+    tree["instances"] = read(5, s[6], abi.devinstance_dtype)
+    tree["instance_boxes"] = read(6, s[6] * 8, np.float32).reshape(s[6], 2, 4)
+    return tree
+
+
+def host_tree(scene, flags=0):
+    """Diagnostic (slrhip_debug_host_tree): the tree the host builds for `scene` (an abi.Scene) in an RGB context with config flags
+    `flags`, as the dict _read_tree describes.  No GPU is touched; raises SlrHipError (code 5) for a scene whose tree the upload leaves to
+    the device build."""
+    lib = load_library()
+    desc = scene.desc(abi.MODE_RGB)
+    return _read_tree(lib, lambda what, ptr, words: lib.slrhip_debug_host_tree(C.byref(desc) if what == 0 else None, flags, what, ptr, words),
+                      "slrhip_debug_host_tree")
+
+
+def quantize_nodes(nodes):
+    """Diagnostic (slrhip_debug_quantize_nodes): the host quantizer on abi.qnode_dtype records -> abi.qnodeq_dtype records.  No GPU."""
+    lib = load_library()
+    a = np.ascontiguousarray(nodes, abi.qnode_dtype)
+    out = np.zeros(len(a), abi.qnodeq_dtype)
+    _check(lib, lib.slrhip_debug_quantize_nodes(a.ctypes.data, len(a), out.ctypes.data), "slrhip_debug_quantize_nodes")
+    return out
 
 
 def instance_world_box(mesh_lo, mesh_hi, local_to_world):

@@ -23,6 +23,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <mutex>
 #include <queue>
 #include <thread>
@@ -197,8 +198,20 @@ struct Builder {
 } // namespace
 
 namespace {
-// what the device computes for a plane: fma(q, scale, origin), correctly rounded (double holds the exact sum)
-inline float dequant(uint32_t q, float scale, float origin) { return (float)((double)q * (double)scale + (double)origin); }
+// what the device computes for a plane: fma(q, scale, origin), rounded once (k_collapse_emit's dequantDev, the traversal's own fma)
+inline float dequant(uint32_t q, float scale, float origin) { return std::fma((float)q, scale, origin); }
+
+// The scale of one axis of a quantized node (shared, statement for statement, with k_collapse_emit of bvh_device.hip): origin +
+// 255 * scale must reach the top of the box under the device's rounding.  A box with bmax > bmin never gets scale 0 (the flat
+// branch): where the extent is a subnormal so small that the division rounds to 0, the scale starts at the smallest subnormal.  The
+// loop needs a step or two for finite boxes (the division is off by half an ulp, one ulp of scale moves the top by 255 of them);
+// the bound keeps a box outside the quantizer's domain (an infinite or NaN plane) from spinning, on the device as here.
+inline float quantScale(float bmin, float bmax) {
+    float sc = (bmax - bmin) / 255.0f;
+    if (sc == 0.0f && bmax > bmin) sc = std::numeric_limits<float>::denorm_min();
+    for (int guard = 0; guard < 64 && sc > 0.0f && dequant(255, sc, bmin) < bmax; ++guard) sc = std::nextafter(sc, INFINITY);
+    return sc;
+}
 }
 
 void quantizeNodes(QBVH* out) {
@@ -219,9 +232,7 @@ void quantizeNodes(QBVH* out) {
                     if (s.child[c] != kInvalidChild) { bmin = std::fmin(bmin, mins[a][c]); bmax = std::fmax(bmax, maxs[a][c]); }
                 if (!(bmin <= bmax)) { bmin = 0.0f; bmax = 0.0f; }
                 org[a] = bmin;
-                float sc = (bmax - bmin) / 255.0f;
-                // origin + 255 * scale must reach the top of the box under the device's rounding
-                while (sc > 0.0f && dequant(255, sc, bmin) < bmax) sc = std::nextafter(sc, INFINITY);
+                const float sc = quantScale(bmin, bmax);
                 scl[a] = sc;
                 for (int c = 0; c < 4; ++c) {
                     uint32_t l = 255, h = 0;                       // empty slot: inverted, never entered
@@ -472,9 +483,7 @@ int buildQBVHPrims(const slrhip_vertex* verts, const slrhip_triangle* tris, cons
                 float bmin = INFINITY, bmax = -INFINITY;
                 for (int c = 0; c < nk; ++c) { bmin = std::fmin(bmin, b.nodes[kids[c]].box.lo[a]); bmax = std::fmax(bmax, b.nodes[kids[c]].box.hi[a]); }
                 org[a] = bmin;
-                float sc = (bmax - bmin) / 255.0f;
-                while (sc > 0.0f && dequant(255, sc, bmin) < bmax) sc = std::nextafter(sc, INFINITY);
-                scl[a] = sc;
+                scl[a] = quantScale(bmin, bmax);
             }
             uint32_t* qlo[3] = {q.qlox, q.qloy, q.qloz};
             uint32_t* qhi[3] = {q.qhix, q.qhiy, q.qhiz};

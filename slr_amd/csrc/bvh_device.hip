@@ -278,7 +278,10 @@ __global__ void k_collapse_emit(BinTree t, int n, uint32_t numFrontier, uint32_t
             if (qn.child[c] != kInvalidChild) { bmin = fminf(bmin, mins[a][c]); bmax = fmaxf(bmax, maxs[a][c]); }
         if (!(bmin <= bmax)) { bmin = 0.0f; bmax = 0.0f; }
         org[a] = bmin;
+        // quantScale of bvh.cpp, statement for statement: a box with bmax > bmin never gets scale 0 (a subnormal extent whose division
+        // rounds to 0 starts at the smallest subnormal), and the same bound on the loop
         float sc = (bmax - bmin) / 255.0f;
+        if (sc == 0.0f && bmax > bmin) sc = __uint_as_float(1u);
         for (int guard = 0; guard < 64 && sc > 0.0f && dequantDev(255, sc, bmin) < bmax; ++guard) sc = __uint_as_float(__float_as_uint(sc) + 1u);      // nextafter upwards (sc > 0)
         scl[a] = sc;
         for (int c = 0; c < 4; ++c) {

@@ -51,6 +51,14 @@ struct PreparedScene {
     uint32_t tableEnd[6] = {};
 };
 
+// The builder behind a prepared scene's tree, as include/slrhip_debug.h numbers them (SLRHIP_TREE_*): 0 host SAH, 1 host with spatial
+// splits (the only build that counts references), 2 device, 3 instanced.
+inline uint32_t treeBuilderOf(const PreparedScene& p) {
+    if (p.build == TreeBuild::Instanced) return 3u;
+    if (p.build == TreeBuild::Device) return 2u;
+    return p.bvh.references ? 1u : 0u;
+}
+
 // Checks the descriptor and derives every host-side record.  Returns SLRHIP_OK, or an SLRHIP_ERR_* code with the message in *err.
 int prepareScene(const slrhip_scene_desc& d, const slrhip_config& config, PreparedScene* out, std::string* err);
 

@@ -175,6 +175,7 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     ctx->envOwnMap = false;
     ctx->bvhDepth = depth;
     ctx->bvhLeafRefs = leafRefs;
+    ctx->treeBuilder = treeBuilderOf(p);
     ctx->haveScene = true;
     return SLRHIP_OK;
 }

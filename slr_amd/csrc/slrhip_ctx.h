@@ -120,6 +120,7 @@ struct slrhip_ctx {
     slrhip::DevScene scene;
     uint32_t bvhDepth = 0;
     uint64_t bvhLeafRefs = 0;
+    uint32_t treeBuilder = 0;                     // SLRHIP_TREE_* (include/slrhip_debug.h): the builder behind the scene's tree, for slrhip_debug_tree
     double buildSeconds = 0.0;
 
     // render state

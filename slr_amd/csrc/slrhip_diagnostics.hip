@@ -1,5 +1,8 @@
 // slrhip_diagnostics.hip — the entry points of include/slrhip_debug.h, and the two function-level queries with host arrays in and
 // out (slrhip_trace_rays, slrhip_bsdf_queries): what the tests and tools call, never a renderer.
+#include <memory>
+
+#include "../../include/slrhip_debug.h"
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
@@ -147,6 +150,103 @@ int slrhip_debug_primary_plan(uint32_t numPixels, uint32_t numPasses, uint32_t c
     if (!plan) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_plan: null argument");
     const PrimaryPlan p = planPrimary(numPixels, numPasses, configFlags, (sceneClass & 1) != 0, (sceneClass & 2) != 0, (sceneClass & 4) != 0);
     plan[0] = p.on ? 1u : 0u; plan[1] = p.passesPerLaunch; plan[2] = p.numLaunches; plan[3] = p.instanceEntries ? 1u : 0u;
+    return SLRHIP_OK;
+}
+
+} // extern "C"
+
+// ---- the tree read-outs (include/slrhip_debug.h): one description of the arrays for the context's tree and the host-built one ----
+namespace {
+const uint32_t kTreeSummaryWords = 16, kTreeArrays = 7;
+struct TreeView {
+    uint32_t summary[kTreeSummaryWords];
+    const void* src[kTreeArrays];        // per `what` (0 unused); null = the array does not exist for this tree
+    size_t words[kTreeArrays];
+};
+void describeTree(TreeView& v, uint32_t builder, uint32_t numNodes, uint32_t depth, uint64_t leafRefs, uint32_t numTris, bool quantized,
+                  uint32_t numInstances, uint32_t topNodes) {
+    std::memset(&v, 0, sizeof(v));
+    const uint32_t s[8] = {builder, numNodes, depth, (uint32_t)leafRefs, numTris, quantized ? 1u : 0u, numInstances, topNodes};
+    std::copy(s, s + 8, v.summary);
+    const size_t words[kTreeArrays] = {kTreeSummaryWords, (size_t)numNodes * (sizeof(QNode) / 4), quantized ? (size_t)numNodes * (sizeof(QNodeQ) / 4) : 0,
+                                       (size_t)leafRefs * (sizeof(LeafTri) / 4), (size_t)numTris * (sizeof(ShadeTri) / 4),
+                                       (size_t)numInstances * (sizeof(DevInstance) / 4), (size_t)numInstances * 8u};
+    std::copy(words, words + kTreeArrays, v.words);
+}
+// the argument checks both read-outs share; *copyBytes = what to copy from v.src[what] (0: the summary was written, nothing to copy)
+int treeReadOut(const char* who, const TreeView& v, uint32_t what, void* hostDst, size_t numWords, size_t* copyBytes) {
+    *copyBytes = 0;
+    if (what >= kTreeArrays) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown `what`");
+    if (what == 2 && !v.summary[5]) return fail(SLRHIP_ERR_UNSUPPORTED, std::string(who) + ": the quantized nodes are not in use");
+    if (numWords < v.words[what]) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string(who) + ": host_dst too small");
+    if (what == 0) std::memcpy(hostDst, v.summary, sizeof(v.summary));
+    else *copyBytes = v.words[what] * 4u;
+    return SLRHIP_OK;
+}
+// the scene slrhip_debug_host_tree prepared last on this thread (what = 0), for its other read-outs
+thread_local std::unique_ptr<PreparedScene> t_hostTree;
+} // namespace
+
+extern "C" {
+
+// Diagnostic (include/slrhip_debug.h): the tree of the context's scene, whichever builder made it, to host memory.
+int slrhip_debug_tree(slrhip_ctx* ctx, uint32_t what, void* hostDst, size_t numWords) {
+    if (!ctx || !hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_tree: null argument");
+    if (!ctx->haveScene) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_debug_tree: no scene uploaded");
+    const DevScene& sc = ctx->scene;
+    TreeView v;
+    describeTree(v, ctx->treeBuilder, sc.numNodes, ctx->bvhDepth, ctx->bvhLeafRefs, (uint32_t)ctx->shadeTris.count, sc.nodesQ != nullptr,
+                 sc.numInstances, sc.numInstances && !ctx->topLevelFirst.empty() ? ctx->topLevelFirst.back() : 0u);
+    v.src[1] = ctx->nodes.ptr; v.src[2] = ctx->nodesQ.ptr; v.src[3] = ctx->leafTris.ptr; v.src[4] = ctx->shadeTris.ptr;
+    v.src[5] = ctx->instances.ptr; v.src[6] = ctx->instBoxes.ptr;
+    size_t bytes = 0;
+    if (const int rc = treeReadOut("slrhip_debug_tree", v, what, hostDst, numWords, &bytes)) return rc;
+    if (!bytes) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hostDst, v.src[what], bytes, hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the tree prepareScene builds on the host for a descriptor, without a context or a GPU.
+int slrhip_debug_host_tree(const slrhip_scene_desc* desc, uint32_t configFlags, uint32_t what, void* hostDst, size_t numWords) {
+    if (!hostDst || (what == 0 && !desc)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_host_tree: null argument");
+    if (what == 0) {
+        t_hostTree.reset();
+        std::unique_ptr<PreparedScene> p(new PreparedScene());
+        slrhip_config config;
+        std::memset(&config, 0, sizeof(config));
+        config.mode = SLRHIP_MODE_RGB; config.flags = configFlags;
+        std::string err;
+        if (const int rc = prepareScene(*desc, config, p.get(), &err)) return fail(rc, err);
+        if (p->build == TreeBuild::Device)
+            return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_debug_host_tree: slrhip_upload_scene leaves this scene's tree to the device build (bvh_device.hip); "
+                                                "the host builds none for it");
+        t_hostTree = std::move(p);
+    }
+    if (!t_hostTree) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_debug_host_tree: no tree prepared on this thread (call with what = 0 first)");
+    const PreparedScene& p = *t_hostTree;
+    std::vector<float> boxes;
+    for (const Box& b : p.bvh.instBoxes) boxes.insert(boxes.end(), {b.lo[0], b.lo[1], b.lo[2], 0.0f, b.hi[0], b.hi[1], b.hi[2], 0.0f});
+    TreeView v;
+    describeTree(v, treeBuilderOf(p), (uint32_t)p.bvh.nodes.size(), p.bvh.depth, p.bvh.leafTris.size(), (uint32_t)p.shadeTris.size(), p.quantized,
+                 (uint32_t)p.instances.size(), p.instances.empty() ? 0u : p.bvh.topNodes);
+    v.src[1] = p.bvh.nodes.data(); v.src[2] = p.bvh.quantized.data(); v.src[3] = p.bvh.leafTris.data(); v.src[4] = p.shadeTris.data();
+    v.src[5] = p.instances.data(); v.src[6] = boxes.data();
+    size_t bytes = 0;
+    if (const int rc = treeReadOut("slrhip_debug_host_tree", v, what, hostDst, numWords, &bytes)) return rc;
+    if (bytes) std::memcpy(hostDst, v.src[what], bytes);
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): quantizeNodes of bvh.cpp on the caller's nodes.
+int slrhip_debug_quantize_nodes(const void* nodes, uint32_t n, void* nodesQ) {
+    if ((n && !nodes) || (n && !nodesQ)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_quantize_nodes: null argument");
+    QBVH tree;
+    tree.nodes.resize(n);
+    if (n) std::memcpy(tree.nodes.data(), nodes, (size_t)n * sizeof(QNode));
+    quantizeNodes(&tree);
+    if (n) std::memcpy(nodesQ, tree.quantized.data(), (size_t)n * sizeof(QNodeQ));
     return SLRHIP_OK;
 }
 

@@ -399,6 +399,7 @@ def test_device_built_tree_gives_the_same_image(oracle_rgb):
             c = Context(stripes=1, flags=flags)
             try:
                 fb = c.render_image(sc, st, spp)
+                assert c.debug_tree(summary_only=True)["builder_name"] == ("host SAH" if label == "host" else "device"), (name, label)
                 k, p = c.counters(), c.profile()
                 out[label] = (fb, int(k.extension_rays), int(k.shadow_rays), int(k.samples), int(k.bvh_nodes), p.nodes[0] / p.rays[0], p.triangles[0] / p.rays[0], k.build_seconds)
                 if name == "grid640":
@@ -434,9 +435,12 @@ def test_spatial_split_tree_gives_the_same_image(oracle_rgb):
         c = Context(stripes=1, flags=flags)
         try:
             fb = c.render_image(sc, st, 8)
+            builder = "host SAH" if name == "sah" else "host spatial splits"
+            assert c.debug_tree(summary_only=True)["builder_name"] == builder, name
             k, p = c.counters(), c.profile()
             out[name] = (fb, int(k.extension_rays), int(k.shadow_rays), int(k.bvh_leaf_references), p.triangles[0] / p.rays[0], p.nodes[0] / p.rays[0])
             c.upload_scene(scene_from_golden(g))
+            assert c.debug_tree(summary_only=True)["builder_name"] == builder, name
             r = g["rays"]
             tri, dist, b0, b1 = c.trace_rays(r["org"], r["dir"], r["dist_min"], r["dist_max"])
             assert (tri == g["hits"]["triangle"]).all(), name

@@ -10,7 +10,8 @@ float64 evaluation, the scene generators, the families.  GPU (MI355X): slrhip_tr
 slrhip_intersect_rays and slrhip_test_visibility (k_query_ws: closest hit, any hit, the quantized and the instanced variants) on
 every tree the upload builds.
 
-Measured on the CPU (8 threads): the brute force takes 0.1 s on the 139-triangle terrain (6 532 rays), 0.1 s on the instanced
+Measured on the CPU (8 threads): the brute force takes 0.1 s on the 139-triangle terrain (6 532 rays), 0.6 s on the 1 069-triangle
+terrain the device build takes (6 271 rays: every k-th of its family), 0.1 s on the instanced
 scene (586 candidates), 0.6 s on the 8 192-triangle deck (1 516 rays) and 1.1 s on the 320 011-triangle grid (404 rays; 0.4 s more
 for the 121 base rays of its intervals)."""
 import functools
@@ -23,6 +24,7 @@ from slr_amd import abi, binding, scenes
 
 MISS = abi.MISS
 N = 8                                   # cells per side of the small lattice scenes
+N23 = 23                                # ... and of the terrain that is large enough for the device build
 GRID_N = 400
 GRID_COORDS = (-0.5, 0.0, 0.5, 57.0, 113.5, 200.0, 286.5, 343.0, 399.5, 400.0, 400.5)       # of the 801 half-lattice values
 
@@ -48,6 +50,10 @@ def case(name):
     if name == "terrain":
         sc = scenes.lattice_terrain(N)
         return Case(sc, *special_rays(sc, N), _bounds(sc))
+    if name == "terrain23":
+        # the smallest terrain the device build takes (1 069 triangles; below 1 024 the upload builds on the host whatever the flag says)
+        sc = scenes.lattice_terrain(N23)
+        return Case(sc, *every_kth(*special_rays(sc, N23), 8192), _bounds(sc))
     if name == "instanced":
         # the terrain's own box, where the 0 * inf arises at the root of the MESH's tree: the first two placements are the identity
         sc = scenes.lattice_instanced(N)
@@ -120,7 +126,7 @@ def test_grid_scene_is_the_terrain_at_400_cells():
     assert ((pos * 4 == np.round(pos * 4)).sum() == pos.size - 1) and pos.max() == GRID_N and pos.min() == 0.0
 
 
-@pytest.mark.parametrize("name", ["terrain", "instanced", "deck", "grid"])
+@pytest.mark.parametrize("name", ["terrain", "terrain23", "instanced", "deck", "grid"])
 def test_families_are_not_degenerate(name):
     c = case(name)
     assert_family_not_degenerate(c, name)
@@ -275,14 +281,17 @@ def assert_hits_equal_reference(ref, got, inst, what, exact=None):
             assert (inst[exact] == ref.cand_inst[ref.winner[exact]]).all(), (what, "tie rule, instance")
 
 
+# tree -> (case, config flags, the builder the summary of slrhip_debug_tree must name).  The device build takes scenes of at least
+# 1 024 triangles: terrain_device_build runs on the 1 069-triangle terrain (on the 139-triangle one the flag is not honoured and the
+# host build answers, which is what this entry tested, under this name, before the summary could tell).
 TREES = {
-    "terrain_host": ("terrain", 0),
-    "terrain_device_build": ("terrain", abi.FLAG_BVH_DEVICE_BUILD),
-    "terrain_spatial_splits": ("terrain", abi.FLAG_BVH_SPATIAL_SPLITS),
-    "instanced": ("instanced", 0),
-    "deck_host": ("deck", 0),
-    "deck_device_build": ("deck", abi.FLAG_BVH_DEVICE_BUILD),
-    "grid_quantized": ("grid", 0),
+    "terrain_host": ("terrain", 0, "host SAH"),
+    "terrain_device_build": ("terrain23", abi.FLAG_BVH_DEVICE_BUILD, "device"),
+    "terrain_spatial_splits": ("terrain", abi.FLAG_BVH_SPATIAL_SPLITS, "host spatial splits"),
+    "instanced": ("instanced", 0, "instanced"),
+    "deck_host": ("deck", 0, "host SAH"),
+    "deck_device_build": ("deck", abi.FLAG_BVH_DEVICE_BUILD, "device"),
+    "grid_quantized": ("grid", 0, "host SAH"),
 }
 
 
@@ -293,12 +302,13 @@ def test_every_entry_point_equals_the_brute_force(tree):
     ray.  The exact tie rule is asserted where it is provable: on the deck (every box is the same box, every triangle is tested:
     the last layer wins, triangle >= 8 190) and on the terrain's rays whose tie set lies in the two coincident quads (identical
     boxes, t exact for det = 16: the second quad wins).  grid_quantized: 404 rays against 320 011 triangles, 1.1 s of brute force."""
-    name, flags = TREES[tree]
+    name, flags, builder = TREES[tree]
     c = case(name)
     assert_family_not_degenerate(c, tree)
     ctx = binding.Context(flags=flags)
     try:
         ctx.upload_scene(c.sc)          # both builders take the deck (host tree: 10 levels of four-wide nodes, up to 31 stack entries)
+        assert ctx.debug_tree(summary_only=True)["builder_name"] == builder, tree
         if name == "grid":
             assert ctx.counters().bvh_nodes >= 65536          # the quantized tree
         batch, hits, inst, vis = device_answers(ctx, c.rows)
@@ -309,8 +319,9 @@ def test_every_entry_point_equals_the_brute_force(tree):
     if name == "deck":
         exact = ref.hit
         assert (ref.cand_tri[ref.winner[exact]] >= 8190).all()
-    elif name == "terrain":
-        exact = _tie_set_inside(ref, 128, 132)
+    elif name in ("terrain", "terrain23"):
+        quads = 2 * (N if name == "terrain" else N23) ** 2          # the two coincident quads follow the heightfield's triangles
+        exact = _tie_set_inside(ref, quads, quads + 4)
     assert_hits_equal_reference(ref, batch, None, tree + " slrhip_trace_rays", exact)
     assert_hits_equal_reference(ref, hits, inst, tree + " slrhip_intersect_rays", exact)
     wrong = np.nonzero((vis != 0) == ref.hit)[0]
