@@ -612,6 +612,79 @@ int slrhip_resolve_albedo(slrhip_ctx* ctx, float* device_dst, size_t num_floats,
 /* The same into HOST memory: resolves, waits for the device, and fails with SLRHIP_ERR_HIP if the feature error word is set.       */
 int slrhip_read_albedo(slrhip_ctx* ctx, float* host_dst, size_t num_floats, uint32_t* passes);
 
+/* ---- motion vectors: where was this sample's surface point on the previous frame's image? ------------------------------------------
+ * What temporal reprojection (slrhip_reproject below) fetches the previous frame's history along.  Its own calls, not a channel bit of
+ * slrhip_render_features: SLRHIP_FEATURE_ALL stays 63.  The call is STATELESS: the library keeps no previous frame; the caller names it,
+ * because the caller uploaded it (slrhip_set_instance_transforms, slrhip_set_camera).
+ *
+ * The definition, per (pixel, pass) of the shard.  Everything is float32, every operation IEEE-rounded on its own (no fused
+ * multiply-add), IEEE division and square root; stated once for host and device in slr_amd/csrc/pt_motion.h.
+ *   Ray, hit:   the camera ray and the closest hit of slrhip_render_features for that (pixel, pass): same seed, same draws, the alpha
+ *               test the render applies.  A miss (the environment sphere is a miss) adds nothing.
+ *   Point now:  P = org + dist * dir, per component, one multiply and one add.
+ *   mulPoint:   (M, p) -> per row r of the column-major M: ((M[r] p.x + M[4 + r] p.y) + M[8 + r] p.z) + M[12 + r] * 1.0f, rows 0 .. 3; if
+ *               the fourth, w, is not 1: x, y, z each times (1.0f / w).  (Matrix4x4.h:71-81; the traversal's own.)
+ *   Local:      an instanced hit: l = mulPoint(world_to_local_now, P); a loose triangle: l = P.
+ *   Placements: an instanced hit: P_now = mulPoint(local_to_world_now, l), P_prev = mulPoint(local_to_world_prev, l); a loose triangle:
+ *               P_now = P_prev = l.  Both points go through the same arithmetic on purpose: where nothing moved (matrices bit-equal,
+ *               cameras equal) the motion is exactly 0.0f, with no special case.
+ *   proj(cam, Q), the inverse of the camera sample through the lens CENTRE (depth of field is ignored):
+ *               q = mulPoint(cam.world_to_local, Q); valid if q.z > 0 and q.x, q.y, q.z are finite;
+ *               X = (0.5f - ((q.x / q.z) * objPlaneDistance) / opWidth) * (float)width
+ *               Y = (0.5f - ((q.y / q.z) * objPlaneDistance) / opHeight) * (float)height            evaluated as written,
+ *               with opHeight = 2.0f * obj_plane_distance * tanf(fov_y * 0.5f) and opWidth = opHeight * aspect from the host
+ *               arithmetic of slrhip_upload_scene's camera constants (PerspectiveCamera.cpp:15-24); slrhip_motion_camera returns them.
+ *   Result:     the sample is VALID if proj(cam_now, P_now) and proj(cam_prev, P_prev) are both valid;
+ *               m = proj(cam_prev, P_prev) - proj(cam_now, P_now), in pixels: a pixel centre p of this frame was at p + m;
+ *               z' = length(P_prev - C_prev) = sqrtf((dx dx + dy dy) + dz dz), C_prev = mulPoint(cam_prev.local_to_world, (0, 0, 0)):
+ *               the distance the previous frame's DISTANCE feature would have shown for the point.
+ *   Sum:        per pixel a float4 {sum m.x, sum m.y, sum z', number of valid samples} over the VALID samples: plain float32 sums in
+ *               pass order, one lane per pixel, like the feature channels.  sum / w is the mean over the valid samples.
+ *
+ * The contract mirrors slrhip_render_albedo's.  Cleared by slrhip_render_begin; independent of the shard split, of how ascending passes
+ * are cut into calls, of the tree kind and of scheduling; RGB and spectral contexts give equal buffers.  Stream-ordered and
+ * NON-BLOCKING.  The first motion call after a slrhip_render_begin allocates (the sums: 16 B per pixel; the record window, which is the
+ * feature pass's: 16 B per (pixel, pass), at most 64 passes) and is not capturable; later calls allocate nothing, copy nothing, do not
+ * synchronise and may be captured.  The record window is shared with the feature and the albedo passes: the three kinds of call of one
+ * context go on ONE stream (or the caller synchronises between them), and the first call of each kind after a slrhip_render_begin may
+ * MOVE the shared record window when it needs more room than the others sized it for: capture graphs after the first calls.
+ * EVERY motion call between two slrhip_render_begin calls must name the SAME previous frame (the same camera values, the same matrices):
+ * the sums of a pixel would otherwise mix vectors into two different frames.  The library cannot check this and does not.
+ * The previous camera is taken BY VALUE at the call; `previous_transforms` is read in order on `stream` and is free once the stream has
+ * passed the call.  Motion calls interleave freely with slrhip_render, feature and albedo calls: none changes a bit of another's
+ * result, of the counters or of the error words.  A traversal that gives up sets the FEATURE error word (slrhip_features_status);
+ * slrhip_read_motion fails on it as slrhip_read_features does.
+ * Errors: SLRHIP_ERR_INVALID_ARGUMENT for a null context or descriptor, a nonzero `reserved`, a misaligned (16 bytes)
+ * previous_transforms, previous_transforms on a scene without instances, a pass range beyond 2^32, a null or misaligned (4 bytes)
+ * destination or too little room; SLRHIP_ERR_NO_SCENE before slrhip_render_begin; spp_count == 0 does nothing.
+ * Not covered: the environment under camera rotation (a miss has no vector); motion of loose triangles (they are taken to stand
+ * still; only instances and the camera move); depth of field (the projection goes through the lens centre).                          */
+struct slrhip_instance_transform;                                    /* defined below, with slrhip_set_instance_transforms */
+typedef struct slrhip_motion_desc {
+    const slrhip_camera* previous_camera;                           /* HOST; NULL = the camera did not move */
+    const struct slrhip_instance_transform* previous_transforms;    /* DEVICE, 16-byte aligned, ALL instances of the scene, in order;
+                                                                       NULL = no instance moved (required NULL for a scene without instances) */
+    uint32_t reserved[2];                                           /* 0 */
+} slrhip_motion_desc;
+int slrhip_render_motion(slrhip_ctx* ctx, const slrhip_motion_desc* desc, uint32_t spp_begin, uint32_t spp_count, void* stream);
+/* The SUMS into DEVICE memory as [height][width][4] float32 {sum m.x, sum m.y, sum z', valid samples}, zeros outside the shard, so that
+ * shards add like the frame; num_floats: room at device_dst, at least width x height x 4.  Stream-ordered, non-blocking, allocates
+ * nothing; before the first motion call the sums are zeros.                                                                         */
+int slrhip_resolve_motion(slrhip_ctx* ctx, float* device_dst, size_t num_floats, void* stream);
+/* The same into HOST memory: resolves, waits for the device, and fails with SLRHIP_ERR_HIP if the feature error word is set.       */
+int slrhip_read_motion(slrhip_ctx* ctx, float* host_dst, size_t num_floats);
+
+/* The constants proj() takes of a camera, on the HOST (pure; no GPU is touched), from the arithmetic the upload uses: out[0 .. 15] the
+ * world_to_local matrix as used, out[16 .. 18] the lens centre mulPoint(local_to_world, (0, 0, 0)), out[19] opWidth, out[20] opHeight,
+ * out[21] objPlaneDistance, out[22], out[23] = 0.  So that a test can take the constants without restating tanf.                     */
+int slrhip_motion_camera(const slrhip_camera* camera, float out[24]);
+/* One sample through the function the kernel calls (pt_motion.h), on the HOST (pure).  now_record / prev_record: the 32 floats of a
+ * slrhip_instance_transform of the instance that was hit, now and in the previous frame; now_record NULL: a loose triangle
+ * (prev_record is not read); prev_record NULL: the instance did not move.  P: the hit point now.  out = {m.x, m.y, z', 1} for a valid
+ * sample, {0, 0, 0, 0} for one that is not.  SLRHIP_ERR_INVALID_ARGUMENT for a null camera, P or out.                                */
+int slrhip_motion_sample(const slrhip_camera* now_camera, const slrhip_camera* prev_camera, const float* now_record, const float* prev_record,
+                         uint32_t width, uint32_t height, const float P[3], float out[4]);
+
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
 
@@ -1005,6 +1078,85 @@ typedef struct slrhip_modulate_desc {
     uint32_t reserved;            /* 0 */
 } slrhip_modulate_desc;
 int slrhip_modulate(slrhip_ctx* ctx, const slrhip_modulate_desc* desc, void* stream);
+
+/* ---- temporal reprojection: blend the current frame into the previous frame's history --------------------------------------------------
+ * slrhip_denoise is the spatial half of SVGF; this is the temporal half.  The previous frame's accumulated colour is fetched along the
+ * motion vectors (slrhip_resolve_motion), tested against the current frame's guides, and blended with the current frame with a weight
+ * that falls with the length of the history.  Like the denoiser it is a PURE FUNCTION OF THE CALLER'S DEVICE BUFFERS: it reads nothing
+ * of the render state, needs no scene and no slrhip_render_begin; the context only names the device.
+ *
+ * The definition, per pixel p = (x, y), C = components.  Everything is float32, every operation IEEE-rounded on its own (no fused
+ * multiply-add), IEEE division and square root, floorf exact.
+ *   Rejected:  p is rejected if coverage_p <= 0 or n = motion_p.w <= 0 (no sample of the pixel has a vector; the environment is out of scope).
+ *   Position:  m = (motion_p.x / n, motion_p.y / n);  z_e = motion_p.z / n, the distance expected in the previous frame;
+ *              fx = (float)x + m.x;  x0 = floorf(fx);  tx = fx - x0;  y likewise.  The pixel centre is x + 0.5 and the bilinear footprint
+ *              of a position u starts at floorf(u - 0.5): the + 0.5 and the - 0.5 cancel.
+ *   Taps:      q = (x0 + (float)i, y0 + (float)j), the sums in float32; j is the OUTER loop and i the INNER loop over {0, 1}, and every sum
+ *              below adds in that order, starting from 0.0f.  b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty).  A tap with b == 0 adds
+ *              nothing and is not read.
+ *   Validity:  a tap q is valid if ALL of these hold:
+ *                it lies inside the image (0 <= q.x < width, 0 <= q.y < height; false for a NaN);
+ *                prev_coverage_q > 0;  prev_length_q > 0;
+ *                with ids: ids_p[1] == prev_ids_q[1] and ids_p[2] == prev_ids_q[2] (instance and material; triangle indices differ
+ *                  between neighbours by design);
+ *                with sigma_distance > 0: fabsf(prev_distance_q / prev_coverage_q - z_e) <= sigma_distance * z_e;
+ *                with normals: (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= min_normal_dot, n_p from normal_p and n_q from prev_normal_q as
+ *                  slrhip_denoise normalises: len = sqrtf((Nx Nx + Ny Ny) + Nz Nz); N / len component-wise (by division) if len > 0,
+ *                  else (0, 0, 0);
+ *                Y(prev_color_q), the expression of slrhip_sample_luminance on the tap's C components, is finite (fabsf(Y) <= FLT_MAX):
+ *                  a NaN or an infinity does not live on in the history.
+ *   History:   B = sum b over the valid taps.  If B <= 0 the pixel is rejected.  Otherwise hist[k] = (sum b * prev_color_q[k]) / B,
+ *              len = (sum b * prev_length_q) / B, vhist = (sum b * prev_variance_q) / B.
+ *   Blend:     N = fminf(len + 1.0f, max_history);  a = fmaxf(1.0f / N, min_alpha);
+ *              output[k] = (1.0f - a) * hist[k] + a * color[k];  output_length = N;
+ *              output_variance = (a * a) * variance_p + ((1.0f - a) * (1.0f - a)) * vhist.
+ *   Rejected:  output[k] = color[k];  output_length = 1;  output_variance = variance_p.
+ * Each pixel's sums are formed by one thread in the stated order: the result does not depend on scheduling.  The history length is a
+ * float plane so that it is fetched like the colour; a fresh sequence starts from prev_length = 0 everywhere.
+ *
+ * The call.  All pointers are DEVICE pointers, 4-byte aligned.  The current frame's inputs are the channels exactly as the resolve calls
+ * write them (SUMS for motion, coverage, distance, normal; means for the colour); the previous frame's are what the caller KEPT of the
+ * previous frame: its `output` and `output_length` of this call (or of what followed it), its coverage, distance, ids, normal.  Ordered on
+ * `stream`, non-blocking; it allocates nothing, copies nothing and does not synchronise, so it can be captured into a graph from the
+ * first call on.  The gather reads neighbours of the previous frame, so there is no in-place mode.
+ * SLRHIP_ERR_INVALID_ARGUMENT, with nothing written: a null context or descriptor; a zero size or width * height >= 2^31; components
+ * other than 3 or 16; a null color, motion, coverage, prev_color, prev_length, prev_distance, prev_coverage, output or output_length;
+ * a misaligned pointer (4 bytes); prev_variance without variance or variance without prev_variance, likewise ids / prev_ids and
+ * normal / prev_normal; output_variance without variance; a NaN max_history, min_alpha, sigma_distance or min_normal_dot;
+ * max_history < 1; min_alpha outside [0, 1]; a nonzero `reserved`; any output overlapping any input or another output (byte ranges).
+ * Not covered: reprojecting the environment under camera rotation (a pixel without a hit is rejected and starts again); motion of loose
+ * triangles (slrhip_render_motion takes them to stand still); moment-based temporal variance (the variance is blended, not estimated
+ * from the history's moments); bench.py, the C++ host mirror and the libSLR adapter (the motion pass and this call are reached through
+ * this header and the Python binding only).                                                                                       */
+typedef struct slrhip_reproject_desc {
+    uint32_t width, height;       /* >= 1 each; width * height < 2^31 */
+    uint32_t components;          /* 3 or 16 */
+    /* the current frame */
+    const float* color;           /* [H][W][C] per-pixel MEANS */
+    const float* variance;        /* [H][W] variance of the mean luminance, or NULL */
+    const float* motion;          /* [H][W][4] as slrhip_resolve_motion writes it */
+    const float* coverage;        /* [H][W] SLRHIP_FEATURE_COVERAGE */
+    const uint32_t* ids;          /* [H][W][3] SLRHIP_FEATURE_IDS, or NULL */
+    const float* normal;          /* [H][W][3] SUM of shading normals, or NULL */
+    /* the previous frame */
+    const float* prev_color;      /* [H][W][C] the accumulated history */
+    const float* prev_variance;   /* [H][W], or NULL (required if and only if variance is given) */
+    const float* prev_length;     /* [H][W] history length, as float; 0 = no history */
+    const float* prev_distance;   /* [H][W] SUM of distances */
+    const float* prev_coverage;   /* [H][W] */
+    const uint32_t* prev_ids;     /* [H][W][3]; required if and only if ids is given */
+    const float* prev_normal;     /* [H][W][3]; required if and only if normal is given */
+    /* outputs */
+    float* output;                /* [H][W][C] */
+    float* output_variance;       /* [H][W], or NULL; needs variance */
+    float* output_length;         /* [H][W] */
+    float max_history;            /* >= 1: the history length is capped here (a = 1 / N never falls below 1 / max_history) */
+    float min_alpha;              /* 0 .. 1: the least weight of the current frame */
+    float sigma_distance;         /* > 0: accepted relative difference of a tap's distance from z_e; <= 0: the test is off */
+    float min_normal_dot;         /* a tap needs n_p . n_q >= this; used only with normals */
+    uint32_t reserved[2];         /* 0 */
+} slrhip_reproject_desc;
+int slrhip_reproject(slrhip_ctx* ctx, const slrhip_reproject_desc* desc, void* stream);
 
 /* ---- the environment light from device memory ----------------------------------------------------------------------------------------
  * Replaces or adds the environment sphere of the UPLOADED scene from texels that are already on the device, and leaves everything else

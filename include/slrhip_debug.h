@@ -65,6 +65,17 @@ int slrhip_debug_adaptive_blocks(uint32_t spp_min, uint32_t spp_step, uint32_t s
  * slrhip_last_error_string.  The pointers are only compared, never followed.  No GPU is touched.                                  */
 int slrhip_debug_modulate_check(const slrhip_modulate_desc* desc);
 
+/* The argument checks of slrhip_reproject on a descriptor (slr_amd/csrc/render_plan.h, reprojectRefusal), evaluated on the HOST with the
+ * function the entry point calls: SLRHIP_OK if the call would go ahead, else SLRHIP_ERR_INVALID_ARGUMENT with the reason in
+ * slrhip_last_error_string.  The pointers are only compared, never followed.  No GPU is touched.                                  */
+int slrhip_debug_reproject_check(const slrhip_reproject_desc* desc);
+
+/* The argument checks of slrhip_render_motion (slr_amd/csrc/render_plan.h, motionRefusal), evaluated on the HOST with the function the
+ * entry point calls, for a context that has a render state (have_render != 0) or none and whose scene has `num_instances` instances:
+ * SLRHIP_OK if the call would go ahead, else the code it returns, with the reason in slrhip_last_error_string.  The descriptor's
+ * pointers are only compared, never followed.  No GPU is touched.                                                                   */
+int slrhip_debug_motion_check(int32_t have_render, uint32_t num_instances, const slrhip_motion_desc* desc, uint32_t spp_begin, uint32_t spp_count);
+
 /* The argument checks of slrhip_set_environment on a descriptor (slr_amd/csrc/render_plan.h, environmentRefusal), evaluated on the HOST
  * with the function the entry point calls: SLRHIP_OK if the descriptor would pass, else SLRHIP_ERR_INVALID_ARGUMENT with the reason in
  * slrhip_last_error_string.  The pointer is only compared, never followed.  No GPU is touched.                                      */

@@ -197,6 +197,29 @@ class ModulateDesc(C.Structure):
                 ("albedo_passes", C.c_uint32), ("floor", C.c_float), ("reserved", C.c_uint32)]
 
 
+class MotionDesc(C.Structure):
+    """slrhip_motion_desc: previous_camera is a HOST pointer (None: the camera did not move), previous_transforms a DEVICE pointer (an
+    integer address; None: no instance moved) to one 128-byte record per instance of the scene."""
+    _fields_ = [("previous_camera", C.POINTER(Camera)), ("previous_transforms", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+# Context.reproject's defaults: the history is capped at 32 frames; a tap is taken if its distance is within 10 % of the expected one
+# and its normal within about 25 degrees of the pixel's
+REPROJECT_MAX_HISTORY, REPROJECT_SIGMA_DISTANCE, REPROJECT_MIN_NORMAL_DOT = 32.0, 0.1, 0.9
+
+
+class ReprojectDesc(C.Structure):
+    """slrhip_reproject_desc: every pointer is a DEVICE pointer (an integer address, or None)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_uint32),
+                ("color", C.c_void_p), ("variance", C.c_void_p), ("motion", C.c_void_p), ("coverage", C.c_void_p), ("ids", C.c_void_p),
+                ("normal", C.c_void_p),
+                ("prev_color", C.c_void_p), ("prev_variance", C.c_void_p), ("prev_length", C.c_void_p), ("prev_distance", C.c_void_p),
+                ("prev_coverage", C.c_void_p), ("prev_ids", C.c_void_p), ("prev_normal", C.c_void_p),
+                ("output", C.c_void_p), ("output_variance", C.c_void_p), ("output_length", C.c_void_p),
+                ("max_history", C.c_float), ("min_alpha", C.c_float), ("sigma_distance", C.c_float), ("min_normal_dot", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # slrhip_set_environment's flags (SLRHIP_ENV_*)
 ENV_TEXELS_RGB = 1      # the texels are linear (r, g, b): a spectral context converts them per texel to (u, v, s); an RGB context ignores it
 ENV_STORE_HALF = 2      # round every component to binary16 first, as the reference's RGBA16F image holds them

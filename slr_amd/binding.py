@@ -23,6 +23,8 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
            "slrhip_set_instance_transforms", "slrhip_instances_status", "slrhip_instance_world_box", "slrhip_set_camera",
            "slrhip_debug_instance_update_check", "slrhip_debug_top_level",
+           "slrhip_render_motion", "slrhip_resolve_motion", "slrhip_read_motion", "slrhip_motion_camera", "slrhip_motion_sample", "slrhip_reproject",
+           "slrhip_debug_motion_check", "slrhip_debug_reproject_check",
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
@@ -136,6 +138,18 @@ def load_library():
                            ("slrhip_set_camera", [C.c_void_p, C.POINTER(abi.Camera)]),
                            ("slrhip_debug_instance_update_check", [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
                            ("slrhip_debug_top_level", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before motion vectors and temporal reprojection lacks these eight)
+    for name, argtypes in (("slrhip_render_motion", [C.c_void_p, C.POINTER(abi.MotionDesc), C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_resolve_motion", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+                           ("slrhip_read_motion", [C.c_void_p, C.c_void_p, C.c_size_t]),
+                           ("slrhip_motion_camera", [C.POINTER(abi.Camera), C.c_void_p]),
+                           ("slrhip_motion_sample", [C.POINTER(abi.Camera), C.POINTER(abi.Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p]),
+                           ("slrhip_reproject", [C.c_void_p, C.POINTER(abi.ReprojectDesc), C.c_void_p]),
+                           ("slrhip_debug_motion_check", [C.c_int32, C.c_uint32, C.POINTER(abi.MotionDesc), C.c_uint32, C.c_uint32]),
+                           ("slrhip_debug_reproject_check", [C.POINTER(abi.ReprojectDesc)])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     # (and one from before the tree read-outs lacks these three)
@@ -552,6 +566,95 @@ class Context:
         passes = C.c_uint32(0)
         return self._read_frame("slrhip_read_albedo", C.byref(passes)), passes.value
 
+    # ---- motion vectors (slrhip_render_motion / slrhip_resolve_motion / slrhip_read_motion) ----
+    def render_motion(self, spp, previous_camera=None, previous_transforms=None, spp_begin=0, stream=None):
+        """Motion passes [spp_begin, spp_begin + spp) of every pixel of the shard (slrhip_render_motion): where on the PREVIOUS frame's
+        image was the point each sample's camera ray hits now?  previous_camera: the abi.Camera of the previous frame (None: the
+        camera did not move; taken by value).  previous_transforms: the matrices ALL instances had in the previous frame (None: no
+        instance moved) — a numpy [n, 32] float32 array (or abi.instance_transform_dtype / abi.instance_dtype records), copied to
+        the device first (that call synchronises); or a contiguous [n, 32] float32 torch CUDA tensor or a device address (int), read
+        in order on `stream` without a copy.  Every call between two render_begin calls must name the same previous frame."""
+        cam = C.pointer(previous_camera) if previous_camera is not None else None
+
+        def call(ptr):
+            d = abi.MotionDesc(cam, ptr, (C.c_uint32 * 2)(0, 0))
+            _check(self.lib, self.lib.slrhip_render_motion(self.handle, C.byref(d), spp_begin, spp, self._stream_handle(stream)), "slrhip_render_motion")
+        if isinstance(previous_transforms, np.ndarray):
+            a = previous_transforms
+            if a.dtype == abi.instance_dtype:
+                a = np.concatenate([a["local_to_world"], a["world_to_local"]], axis=1)
+            elif a.dtype == abi.instance_transform_dtype:
+                a = np.ascontiguousarray(a).view(np.float32)
+            a = np.ascontiguousarray(a, np.float32).reshape(-1, 32)
+            with DeviceBlocks() as dev:
+                call(dev.put(a))
+                self.synchronize()                     # the staging block is freed on the way out
+            return
+        if previous_transforms is not None and not isinstance(previous_transforms, int):
+            t = previous_transforms
+            if not (t.is_cuda and t.dim() == 2 and t.shape[1] == 32 and t.is_contiguous() and t.element_size() == 4 and t.is_floating_point()):
+                raise ValueError("previous_transforms: a contiguous [n, 32] float32 CUDA tensor, a numpy array or a device address expected")
+            if t.device.index != self.device:
+                raise SlrHipError("render_motion: the tensor is on device %r, the context on device %d" % (t.device.index, self.device))
+            previous_transforms = t.data_ptr()
+        call(previous_transforms)
+
+    def motion_into(self, device_ptr, num_floats, stream=None):
+        """The motion SUMS into device memory at `device_ptr` ([height, width, 4] float32; slrhip_resolve_motion), ordered on `stream`."""
+        _check(self.lib, self.lib.slrhip_resolve_motion(self.handle, device_ptr, num_floats, self._stream_handle(stream)), "slrhip_resolve_motion")
+
+    def motion(self):
+        """The motion sums [height, width, 4] float32 {sum m.x, sum m.y, sum z', valid samples}, zeros outside the shard; [..., :3] /
+        [..., 3:] is the mean vector in pixels and the mean distance in the previous frame.  Synchronises, and raises if the feature
+        error word is set."""
+        out = np.zeros((self.settings.image_height, self.settings.image_width, 4), np.float32)
+        _check(self.lib, self.lib.slrhip_read_motion(self.handle, out.ctypes.data, out.size), "slrhip_read_motion")
+        return out
+
+    # ---- temporal reprojection (slrhip_reproject): a pure function of device buffers ----
+    def reproject_into(self, width, height, components, color, motion, coverage, prev_color, prev_length, prev_distance, prev_coverage, output,
+                       output_length, variance=None, ids=None, normal=None, prev_variance=None, prev_ids=None, prev_normal=None,
+                       output_variance=None, max_history=abi.REPROJECT_MAX_HISTORY, min_alpha=0.0, sigma_distance=abi.REPROJECT_SIGMA_DISTANCE,
+                       min_normal_dot=abi.REPROJECT_MIN_NORMAL_DOT, stream=None):
+        """slrhip_reproject over DEVICE pointers (integer addresses; None = not given): the current frame's color [H][W][C] means,
+        motion [H][W][4], coverage [H][W] (and variance [H][W], ids [H][W][3] uint32, normal [H][W][3]) and what was kept of the
+        previous frame (prev_color: the accumulated history, prev_length, prev_distance, prev_coverage, ...) -> output, output_length
+        and, if given, output_variance.  Ordered on `stream`, returns at once.  Needs no scene and no render_begin."""
+        d = abi.ReprojectDesc(width, height, components, color, variance, motion, coverage, ids, normal, prev_color, prev_variance, prev_length,
+                              prev_distance, prev_coverage, prev_ids, prev_normal, output, output_variance, output_length, max_history, min_alpha,
+                              sigma_distance, min_normal_dot, (C.c_uint32 * 2)(0, 0))
+        _check(self.lib, self.lib.slrhip_reproject(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_reproject")
+
+    def reproject(self, color, motion, coverage, prev_color, prev_length, prev_distance, prev_coverage, variance=None, ids=None, normal=None,
+                  prev_variance=None, prev_ids=None, prev_normal=None, **params):
+        """slrhip_reproject over HOST arrays (the shapes of reproject_into; ids as uint32): the arrays are copied to the device and the
+        result back: (output [H, W, C], length [H, W]) or, with a variance, (output, length, variance).  **params: max_history,
+        min_alpha, sigma_distance, min_normal_dot.  Synchronises."""
+        color = np.ascontiguousarray(color, np.float32)
+        if color.ndim != 3:
+            raise ValueError("color: a [height, width, components] array expected")
+        h, w, comps = color.shape
+        host = {"color": color, "motion": motion, "coverage": coverage, "prev_color": prev_color, "prev_length": prev_length,
+                "prev_distance": prev_distance, "prev_coverage": prev_coverage, "variance": variance, "ids": ids, "normal": normal,
+                "prev_variance": prev_variance, "prev_ids": prev_ids, "prev_normal": prev_normal}
+        shapes = {"color": (h, w, comps), "prev_color": (h, w, comps), "motion": (h, w, 4), "ids": (h, w, 3), "prev_ids": (h, w, 3),
+                  "normal": (h, w, 3), "prev_normal": (h, w, 3)}
+        with DeviceBlocks() as dev:
+            ptrs = {}
+            for name, a in host.items():
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, np.uint32 if name.endswith("ids") else np.float32)
+                if a.shape != shapes.get(name, (h, w)):
+                    raise ValueError("%s: shape %r expected" % (name, shapes.get(name, (h, w))))
+                ptrs[name] = dev.put(a)
+            output, length = dev.alloc(4 * h * w * comps), dev.alloc(4 * h * w)
+            out_variance = dev.alloc(4 * h * w) if variance is not None else None
+            self.reproject_into(w, h, comps, output=output, output_length=length, output_variance=out_variance, **ptrs, **params)
+            self.synchronize()
+            res = (dev.get(output, (h, w, comps)), dev.get(length, (h, w)))
+            return res + (dev.get(out_variance, (h, w)),) if variance is not None else res
+
     # ---- albedo demodulation (slrhip_modulate): a pure function of device buffers ----
     def modulate_into(self, width, height, components, op, color, albedo, albedo_passes, output, variance=None, output_variance=None,
                       floor=abi.MODULATE_FLOOR, stream=None):
@@ -911,6 +1014,29 @@ def instance_world_box(mesh_lo, mesh_hi, local_to_world):
     if lib.slrhip_instance_world_box(lo.ctypes.data, hi.ctypes.data, m.ctypes.data, out_lo.ctypes.data, out_hi.ctypes.data) != 0:
         raise ValueError("instance_world_box: refused")
     return out_lo, out_hi
+
+
+def motion_camera(camera):
+    """The constants the motion pass takes of an abi.Camera, from the upload's host arithmetic (slrhip_motion_camera): float32 [24] =
+    world_to_local [16], the lens centre [3], opWidth, opHeight, objPlaneDistance, 0, 0."""
+    lib = load_library()
+    out = np.zeros(24, np.float32)
+    if lib.slrhip_motion_camera(C.byref(camera), out.ctypes.data) != 0:
+        raise ValueError("motion_camera: refused")
+    return out
+
+
+def motion_sample(now_camera, prev_camera, now_record, prev_record, width, height, point):
+    """One sample's motion vector on the host, with the function the kernel calls (slrhip_motion_sample): now_record / prev_record
+    are the 32 floats of an instance's transform now and in the previous frame (None: a loose triangle / the instance did not move),
+    point the hit point now; float32 [4] = {m.x, m.y, z', 1}, or zeros for a sample that is not valid."""
+    lib = load_library()
+    recs = [None if r is None else np.ascontiguousarray(r, np.float32).reshape(32) for r in (now_record, prev_record)]
+    p, out = np.ascontiguousarray(point, np.float32).reshape(3), np.zeros(4, np.float32)
+    if lib.slrhip_motion_sample(C.byref(now_camera), C.byref(prev_camera), *(None if r is None else r.ctypes.data for r in recs), width, height,
+                                p.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("motion_sample: refused")
+    return out
 
 
 def env_importance(texels, mode=abi.MODE_RGB):

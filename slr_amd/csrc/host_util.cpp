@@ -13,7 +13,9 @@
 #include "pt_envmap.h"
 #include "pt_instance.h"
 #include "pt_luminance.h"
+#include "pt_motion.h"
 #include "pt_tonemap.h"
+#include "scene_prep.h"
 #include "cmf_2deg_table.h"
 
 namespace {
@@ -314,6 +316,26 @@ int slrhip_env_importance(int32_t mode, const float* texels, uint32_t width, uin
 int slrhip_instance_world_box(const float* meshLo, const float* meshHi, const float* localToWorld, float* outLo, float* outHi) {
     if (!meshLo || !meshHi || !localToWorld || !outLo || !outHi) return SLRHIP_ERR_INVALID_ARGUMENT;
     slrhip::instanceWorldBox(meshLo, meshHi, localToWorld, outLo, outHi);
+    return SLRHIP_OK;
+}
+
+// The constants the motion pass takes of a camera (pt_motion.h MotionCamera), from prepareCamera: the upload's host arithmetic.
+int slrhip_motion_camera(const slrhip_camera* camera, float* out) {
+    if (!camera || !out) return SLRHIP_ERR_INVALID_ARGUMENT;
+    const slrhip::DevCamera cam = slrhip::prepareCamera(*camera);
+    const slrhip::MotionCamera mc = slrhip::makeMotionCamera(cam.mat, cam.matInv, cam.opWidth, cam.opHeight, cam.objPlaneDistance);
+    std::memcpy(out, &mc, sizeof(mc));
+    return SLRHIP_OK;
+}
+
+// One sample's motion vector, as the fold kernel computes it (pt_motion.h: the same function).
+int slrhip_motion_sample(const slrhip_camera* nowCamera, const slrhip_camera* prevCamera, const float* nowRecord, const float* prevRecord,
+                         uint32_t width, uint32_t height, const float* P, float* out) {
+    if (!nowCamera || !prevCamera || !P || !out) return SLRHIP_ERR_INVALID_ARGUMENT;
+    slrhip::MotionCamera now, prev;
+    if (slrhip_motion_camera(nowCamera, reinterpret_cast<float*>(&now)) || slrhip_motion_camera(prevCamera, reinterpret_cast<float*>(&prev)))
+        return SLRHIP_ERR_INVALID_ARGUMENT;
+    slrhip::motionSample(now, prev, nowRecord, prevRecord, width, height, P, out);
     return SLRHIP_OK;
 }
 

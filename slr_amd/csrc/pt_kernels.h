@@ -323,7 +323,11 @@ void launchAlbedoResolve(const FeatureParams& fp, uint32_t components, const flo
 // slrhip_modulate (pt_albedo.hip): one launch on `stream`; the descriptor has passed modulateRefusal (render_plan.h)
 void launchModulate(const slrhip_modulate_desc& d, hipStream_t stream);
 
-// Per-pixel noise statistics (slrhip_statistics_begin; pt_stats.hip).  One record per pixel of the shard, updated by k_fold in
+// slrhip_reproject (pt_reproject.hip): one launch on `stream`; the descriptor has passed reprojectRefusal (render_plan.h)
+void launchReproject(const slrhip_reproject_desc& d, hipStream_t stream);
+// (the motion pass, slrhip_render_motion: launchFeatureTrace, then pt_motion.h's launchMotionFold)
+
+// Per-pixel noise statistics (slrhip_statistics_begin; pt_stats.hip). One record per pixel of the shard, updated by k_fold in
 // pass order: {mean, M2, n (uint32 bits), max} of the samples' luminance (float32 Welford).
 static const uint32_t kStatsBlock = 256;                   // threads per block of the summary's first stage
 static const uint32_t kStatsPixelsPerThread = 16;          // a block reduces kStatsBlock x kStatsPixelsPerThread consecutive pixels

@@ -252,6 +252,57 @@ const char* modulateRefusal(const slrhip_modulate_desc& d) {
     return nullptr;
 }
 
+// the layouts the Python mirrors (slr_amd/abi.py) restate
+static_assert(sizeof(slrhip_reproject_desc) == 168 && offsetof(slrhip_reproject_desc, color) == 16 && offsetof(slrhip_reproject_desc, prev_color) == 64 &&
+              offsetof(slrhip_reproject_desc, output) == 120 && offsetof(slrhip_reproject_desc, max_history) == 144 &&
+              offsetof(slrhip_reproject_desc, reserved) == 160, "slrhip_reproject_desc's layout");
+static_assert(sizeof(slrhip_motion_desc) == 24 && offsetof(slrhip_motion_desc, previous_transforms) == 8 && offsetof(slrhip_motion_desc, reserved) == 16,
+              "slrhip_motion_desc's layout");
+
+const char* reprojectRefusal(const slrhip_reproject_desc& d) {
+    if (d.reserved[0] != 0 || d.reserved[1] != 0) return "reserved must be 0";
+    if (d.components != 3 && d.components != 16) return "components must be 3 or 16";
+    const uint64_t pixels = (uint64_t)d.width * d.height;
+    if (pixels == 0 || pixels >= (1ull << 31)) return "width and height must be >= 1 and width * height < 2^31";
+    if (d.max_history != d.max_history || d.min_alpha != d.min_alpha || d.sigma_distance != d.sigma_distance || d.min_normal_dot != d.min_normal_dot)
+        return "a parameter is NaN";
+    if (!(d.max_history >= 1.0f)) return "max_history must be >= 1";
+    if (!(d.min_alpha >= 0.0f) || !(d.min_alpha <= 1.0f)) return "min_alpha must be 0 .. 1";
+    if (!d.color || !d.motion || !d.coverage) return "null color, motion or coverage";
+    if (!d.prev_color || !d.prev_length || !d.prev_distance || !d.prev_coverage) return "null prev_color, prev_length, prev_distance or prev_coverage";
+    if (!d.output || !d.output_length) return "null output or output_length";
+    if ((d.variance != nullptr) != (d.prev_variance != nullptr)) return "variance and prev_variance go together";
+    if ((d.ids != nullptr) != (d.prev_ids != nullptr)) return "ids and prev_ids go together";
+    if ((d.normal != nullptr) != (d.prev_normal != nullptr)) return "normal and prev_normal go together";
+    if (d.output_variance && !d.variance) return "output_variance needs variance";
+    const size_t plane = (size_t)pixels * sizeof(float), frame = plane * d.components;
+    struct Range { const void* p; size_t bytes; };
+    const Range inputs[13] = {{d.color, frame}, {d.variance, plane}, {d.motion, 4 * plane}, {d.coverage, plane}, {d.ids, 3 * plane}, {d.normal, 3 * plane},
+                              {d.prev_color, frame}, {d.prev_variance, plane}, {d.prev_length, plane}, {d.prev_distance, plane}, {d.prev_coverage, plane},
+                              {d.prev_ids, 3 * plane}, {d.prev_normal, 3 * plane}};
+    const Range outputs[3] = {{d.output, frame}, {d.output_variance, plane}, {d.output_length, plane}};
+    for (const Range& r : inputs) if ((uintptr_t)r.p & 3u) return "a misaligned pointer (4 bytes)";
+    for (const Range& r : outputs) if ((uintptr_t)r.p & 3u) return "a misaligned pointer (4 bytes)";
+    for (const Range& o : outputs)
+        for (const Range& in : inputs)
+            if (o.p && in.p && rangesOverlap(o.p, o.bytes, in.p, in.bytes)) return "an output overlaps an input";
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b)
+            if (outputs[a].p && outputs[b].p && rangesOverlap(outputs[a].p, outputs[a].bytes, outputs[b].p, outputs[b].bytes)) return "two outputs overlap";
+    return nullptr;
+}
+
+int motionRefusal(bool haveRender, uint32_t numInstances, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, const char** what) {
+    *what = nullptr;
+    if (!d) { *what = "null descriptor"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) { *what = "reserved must be 0"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if ((uintptr_t)d->previous_transforms & 15u) { *what = "misaligned previous_transforms (16 bytes)"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if ((uint64_t)sppBegin + sppCount > 0xFFFFFFFFull) { *what = "pass range beyond 2^32"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (!haveRender) { *what = "call slrhip_render_begin first"; return SLRHIP_ERR_NO_SCENE; }
+    if (d->previous_transforms && numInstances == 0) { *what = "previous_transforms given, but the scene has no instances"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    return SLRHIP_OK;
+}
+
 const char* environmentRefusal(const slrhip_environment_desc& d) {
     if (d.reserved[0] != 0 || d.reserved[1] != 0) return "reserved must be 0";
     if (d.flags & ~(SLRHIP_ENV_TEXELS_RGB | SLRHIP_ENV_STORE_HALF)) return "unknown flag bits";

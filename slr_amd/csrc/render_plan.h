@@ -105,6 +105,13 @@ size_t tonemapBytes(uint32_t width, uint32_t height, uint32_t format);
 const char* tonemapRefusal(const slrhip_tonemap_desc& d);
 // The argument checks of slrhip_modulate on the descriptor: nullptr if the call goes ahead, else what is wrong with it.
 const char* modulateRefusal(const slrhip_modulate_desc& d);
+// The argument checks of slrhip_reproject on the descriptor (the pointers are only compared, never followed): nullptr if the call goes
+// ahead, else what is wrong with it.
+const char* reprojectRefusal(const slrhip_reproject_desc& d);
+// The argument checks of slrhip_render_motion against what the context holds (a render state or none, the scene's number of instances;
+// the pointers are only compared, never followed, `d` may be null): SLRHIP_OK if the call goes ahead, else the code it returns with
+// *what = what is wrong.
+int motionRefusal(bool haveRender, uint32_t numInstances, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, const char** what);
 // The argument checks of slrhip_set_environment on the descriptor (the pointer is only compared, never followed): nullptr if the
 // call goes ahead, else what is wrong with it.  What depends on the context (no scene, no upsampling tables) is the entry point's.
 const char* environmentRefusal(const slrhip_environment_desc& d);

@@ -564,6 +564,7 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
     ctx->firstRenderCall = true;
     ctx->featChannels = 0; ctx->featPassEnd = 0;                              // the feature accumulation restarts (its arrays are kept for reuse)
     ctx->featErrorReady = false; ctx->albReady = false; ctx->albPasses = 0;   // ... and the albedo accumulation and the error word they share
+    ctx->motionReady = false;                                                 // ... and the motion accumulation
     ctx->stats.on = false; ctx->stats.clear = true;                           // statistics are per render (slrhip_statistics_begin); the records are kept, stale
     ctx->clamp.on = false; ctx->clamp.clear = true;                           // ... and so is the clamp (slrhip_clamp_begin)
     ctx->activePixels = plan.numPixels; ctx->activeList = -1;                 // every pixel is active again (slrhip_render_adaptive)

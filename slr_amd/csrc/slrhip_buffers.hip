@@ -1,5 +1,5 @@
 // slrhip_buffers.hip — the per-pixel buffers beside the framebuffer, on the context and the render loop of slrhip_api.hip: first-hit
-// features and camera rays, the albedo buffer, the noise statistics with slrhip_render_until, the sample clamp, adaptive sampling.
+// features and camera rays, the albedo buffer, the motion buffer, the noise statistics with slrhip_render_until, the sample clamp, adaptive sampling.
 #include <cmath>
 
 #include "slrhip_ctx.h"
@@ -284,6 +284,76 @@ int slrhip_read_albedo(slrhip_ctx* ctx, float* hostDst, size_t numFloats, uint32
     const size_t need = frameFloats(ctx->params);
     if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_albedo: destination too small");
     return readThroughScratch(ctx, hostDst, need, need, true, "slrhip_read_albedo", [&](float* scratch) { return slrhip_resolve_albedo(ctx, scratch, need, passes, nullptr); });
+}
+
+// ---- the motion buffer (slrhip_render_motion / slrhip_resolve_motion / slrhip_read_motion) -------------------------------------------
+// The traversal and the record window are the feature pass's; the fold and the sums are pt_motion.hip's; the sample is pt_motion.h's.
+int slrhip_render_motion(slrhip_ctx* ctx, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_motion: null context");
+    const char* what = nullptr;
+    if (const int rc = motionRefusal(ctx->haveRender, ctx->haveScene ? ctx->scene.numInstances : 0u, d, sppBegin, sppCount, &what))
+        return fail(rc, std::string("slrhip_render_motion: ") + what);
+    if (sppCount == 0) return SLRHIP_OK;
+    const RenderParams& rp = ctx->params;
+    if (rp.numPixels == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    if (!ctx->motionReady) {
+        // the first motion call since render_begin: the sums (cleared in stream order) and room in the record window, sized by the
+        // shard alone, so that no later call allocates whatever its pass count.  The window's arrays only ever grow.
+        const size_t pixels = rp.numPixels;
+        ctx->motionWindow = featureWindow(rp.numPixels, false);
+        HIP_TRY(ctx->motionSums.alloc(pixels));
+        if (const int rc = sizeFeatureRecords(ctx, std::max(ctx->featRecords.capacity, pixels * ctx->motionWindow), 0)) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->motionSums.ptr, 0, pixels * sizeof(float4), s));
+        if (const int rc = clearFeatureError(ctx, s)) return rc;
+        ctx->motionReady = true;
+    }
+    // both cameras by value, from the host arithmetic of the upload's camera constants; no previous camera: the current one
+    const DevCamera& cam = ctx->scene.camera;
+    MotionParams mp;
+    mp.now = makeMotionCamera(cam.mat, cam.matInv, cam.opWidth, cam.opHeight, cam.objPlaneDistance);
+    mp.prev = mp.now;
+    if (d->previous_camera) {
+        const DevCamera prev = prepareCamera(*d->previous_camera);
+        mp.prev = makeMotionCamera(prev.mat, prev.matInv, prev.opWidth, prev.opHeight, prev.objPlaneDistance);
+    }
+    mp.instances = ctx->scene.instances;
+    mp.prevTransforms = reinterpret_cast<const float4*>(d->previous_transforms);
+    mp.sums = ctx->motionSums.ptr;
+    for (uint32_t done = 0; done < sppCount; done += ctx->motionWindow) {
+        const uint32_t n = std::min(ctx->motionWindow, sppCount - done);
+        FeatureParams fp = featureParams(ctx, 0, sppBegin + done, n);
+        fp.b2 = nullptr;
+        launchFeatureTrace(ctx->scene, fp, ctx->numCUs, s);
+        launchMotionFold(cam, fp, mp, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_resolve_motion(slrhip_ctx* ctx, float* deviceDst, size_t numFloats, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_motion: null context");
+    if (!deviceDst || ((uintptr_t)deviceDst & 3u)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_motion: null or misaligned destination (4 bytes)");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_resolve_motion: call slrhip_render_begin first");
+    const RenderParams& rp = ctx->params;
+    const size_t need = (size_t)rp.imageWidth * rp.imageHeight * 4u;
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_resolve_motion: destination too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = (hipStream_t)streamPtr;
+    HIP_TRY(hipMemsetAsync(deviceDst, 0, need * sizeof(float), s));
+    if (rp.numPixels && ctx->motionReady) launchMotionResolve(featureParams(ctx, 0, 0, 0), ctx->motionSums.ptr, deviceDst, s);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+int slrhip_read_motion(slrhip_ctx* ctx, float* hostDst, size_t numFloats) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_motion: null context");
+    if (!hostDst) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_motion: null destination");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_read_motion: call slrhip_render_begin first");
+    const size_t need = (size_t)ctx->params.imageWidth * ctx->params.imageHeight * 4u;
+    if (numFloats < need) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_read_motion: destination too small");
+    return readThroughScratch(ctx, hostDst, need, need, true, "slrhip_read_motion", [&](float* scratch) { return slrhip_resolve_motion(ctx, scratch, need, nullptr); });
 }
 
 // ---- per-pixel noise statistics (slrhip_statistics_begin / slrhip_resolve_statistics / slrhip_statistics_summary / slrhip_render_until) ----

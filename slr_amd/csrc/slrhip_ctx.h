@@ -14,6 +14,7 @@
 #include "bvh.h"
 #include "pt_clamp.h"
 #include "pt_kernels.h"
+#include "pt_motion.h"
 #include "render_plan.h"
 #include "scene_prep.h"
 
@@ -154,6 +155,10 @@ struct slrhip_ctx {
     bool albReady = false;                        // sums allocated and cleared since render_begin
     uint32_t albWindow = 0;                       // passes per launch
     uint64_t albPasses = 0;                       // passes accumulated since render_begin
+    // the motion buffer (slrhip_render_motion): the sums are allocated by the first motion call after render_begin; the record window is the feature pass's
+    DevArray<float4> motionSums;                  // {sum m.x, sum m.y, sum z', valid samples} per pixel of the shard
+    bool motionReady = false;                     // sums allocated and cleared since render_begin
+    uint32_t motionWindow = 0;                    // passes per launch
     // per-pixel noise statistics: records {mean, M2, n, max}; the sample clamp: records {clamped, dropped (uint32 bits), removed, largest}
     slrhip::PixelRecords<slrhip::StatsTotals> stats;
     slrhip::PixelRecords<slrhip::ClampTotals> clamp;

@@ -87,6 +87,21 @@ int slrhip_debug_modulate_check(const slrhip_modulate_desc* d) {
     return SLRHIP_OK;
 }
 
+// Diagnostic (include/slrhip_debug.h): the argument checks of slrhip_reproject alone.
+int slrhip_debug_reproject_check(const slrhip_reproject_desc* d) {
+    if (!d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_reproject: null argument");
+    if (const char* what = reprojectRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_reproject: ") + what);
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the argument checks of slrhip_render_motion alone, for a context described by two numbers.
+int slrhip_debug_motion_check(int32_t haveRender, uint32_t numInstances, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount) {
+    const char* what = nullptr;
+    if (const int rc = motionRefusal(haveRender != 0, numInstances, d, sppBegin, sppCount, &what))
+        return fail(rc, std::string("slrhip_render_motion: ") + what);
+    return SLRHIP_OK;
+}
+
 // Diagnostic (include/slrhip_debug.h): the block lengths of a slrhip_render_adaptive call.
 int slrhip_debug_adaptive_blocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t* blocks, uint32_t maxBlocks, uint32_t* numBlocks) {
     if (!numBlocks || (maxBlocks && !blocks)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_adaptive_blocks: null argument");

@@ -1,5 +1,5 @@
 // slrhip_image.hip — the entry points that are pure functions of the caller's device buffers and read nothing of the render state:
-// the denoiser, the image export, albedo demodulation.  The argument checks are render_plan.cpp's; here are the launches.
+// the denoiser, the image export, albedo demodulation, temporal reprojection.  The argument checks are render_plan.cpp's; here are the launches.
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
@@ -48,6 +48,16 @@ int slrhip_modulate(slrhip_ctx* ctx, const slrhip_modulate_desc* d, void* stream
     if (const char* what = modulateRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_modulate: ") + what);
     HIP_TRY(hipSetDevice(ctx->device));
     launchModulate(*d, (hipStream_t)streamPtr);
+    HIP_TRY(hipGetLastError());
+    return SLRHIP_OK;
+}
+
+// Temporal reprojection: the argument checks (render_plan.cpp), one launch (pt_reproject.hip).  It reads nothing of the render state.
+int slrhip_reproject(slrhip_ctx* ctx, const slrhip_reproject_desc* d, void* streamPtr) {
+    if (!ctx || !d) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_reproject: null argument");
+    if (const char* what = reprojectRefusal(*d)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, std::string("slrhip_reproject: ") + what);
+    HIP_TRY(hipSetDevice(ctx->device));
+    launchReproject(*d, (hipStream_t)streamPtr);
     HIP_TRY(hipGetLastError());
     return SLRHIP_OK;
 }
