@@ -940,3 +940,136 @@ def quad_deck(layers=4096):
     faces = (np.array([(0, 1, 2), (0, 2, 3)])[None] + 4 * np.arange(k)[:, None, None]).reshape(-1, 3)
     b.add_mesh(np.tile(corners, (k, 1)), [(0, -1, 0)] * (4 * k), [(1, 0, 0)] * (4 * k), uv * k, faces, grey)
     return b.build(_lattice_camera(4), name="quad_deck_%d" % layers)
+
+
+# ---- feature mixes (tests/test_feature_mixes.py) ---------------------------------------------------------------------------
+# The scene classes the device code tells apart — instances, textures / bump / alpha, MultiBSDF, environment, glossy lobes,
+# tables in HBM — in ONE box, each switched by a name, so that the kernels' branches are run where the classes meet.
+FEATURES = frozenset(("inst", "tex", "multi", "env", "glossy", "many"))
+_MIX_ENV = {}
+
+
+def _mix_sphere_placements():
+    """The bump-mapped mesh (a unit UV sphere): rotation and NON-UNIFORM scale in every placement."""
+    return [_translate(-0.85, 0.62, -0.9) @ _rotate(0.5, (0, 1, 0)) @ np.diag([0.5, 0.6, 0.35, 1.0]),
+            _translate(0.3, 1.6, -1.4) @ _rotate(0.9, (1, 0, 1)) @ np.diag([0.6, 0.3, 0.45, 1.0]),
+            _translate(1.0, 0.47, 0.3) @ _rotate(-0.7, (0, 1, 0.3)) @ np.diag([0.35, 0.45, 0.55, 1.0])]
+
+
+def feature_mix_box_placements():
+    """The alpha-cut mesh (the unit cube [-0.5, 0.5]^3) of feature_mix: local-to-world of its three placements."""
+    return [_translate(-0.2, 0.6, 0.2) @ _rotate(0.6, (0, 1, 0)) @ np.diag([0.8, 1.1, 0.6, 1.0]),
+            _translate(0.95, 1.5, -1.0) @ _rotate(0.4, (1, 0, 0)) @ _rotate(-0.5, (0, 1, 0)) @ np.diag([0.7, 0.5, 0.9, 1.0]),
+            _translate(-0.95, 1.75, 0.4) @ _rotate(0.8, (0, 1, 1)) @ np.diag([0.5, 0.7, 0.4, 1.0])]
+
+
+def feature_mix(features, aspect=1.0, segments=10, rings=5):
+    """One box for every subset of FEATURES.  Loose: the red wall, the floor and the back wall of the Cornell box (no ceiling and
+    no right wall: paths escape), the emitting quad, and a sphere standing in front.  Two meshes, a UV sphere and a unit cube,
+    are placed three times each with rotation and non-uniform scale.  The floor reaches 4.5 past the box on its two open sides:
+    a direction out of a bump-mapped frame is not a unit vector (the frame's three unit vectors are not orthogonal), and one
+    with y <= -1 that ended on the environment would make the reference read past its importance table (theta / pi rounds to
+    1: distributions.cpp:181-184) — from a height below 2.5 and with a length of at most sqrt(3) such a ray meets the floor
+    within 3.6 of its origin.
+
+      inst    the placements are slrhip_instances (TransformedSurfaceObject); without it the same matrices are baked into loose
+              copies (the shading frames then differ: an instance takes its frame through local_to_world, a baked normal goes
+              through the inverse transpose)
+      tex     an image on the floor behind a mapping that wraps; the sphere mesh is bump-mapped (checker_normal) over a checker
+              reflectance; the cube is alpha-cut (checker_float(1, 0)) and wrapped in an image: rays pass its holes
+      multi   the sphere mesh carries mix(a, b; 0.4) — with tex the MULTI record carries the normal map and b's coefficient is
+              the checker; the cube carries sum(mix(c, Oren-Nayar; 0.4), specular aluminium), nested one level — with tex the
+              MULTI record carries the alpha map and c's coefficient is the image
+      glossy  the loose sphere is GGX titanium (alpha_g 0.1); with multi, a is GGX titanium (alpha_g 0.3).  Without glossy every
+              lobe is free of float libm (Lambert, Oren-Nayar, specular metal)
+      env     synthetic_sky(64, 32) as the environment, importance maps in both forms; the area light stays
+      many    a 6 x 6 patchwork in front of the back wall, each patch its own material, ten of them emitting: more than 32
+              materials and more than 16 emitting triangles"""
+    f = frozenset(features)
+    assert f <= FEATURES, sorted(f - FEATURES)
+    tex, multi, glossy = "tex" in f, "multi" in f, "glossy" in f
+    b = SceneBuilder()
+    red = b.matte(b.spectrum_srgb_nonlinear(0.75, 0.25, 0.25))
+    white = b.matte(b.spectrum_srgb_nonlinear(0.75, 0.75, 0.75))
+    if tex:
+        floor = b.matte(b.image_spectrum(*synthetic_image(16, 12, 5), offset=(0.125, -0.25), scale=(2.0, 3.0)))
+    else:
+        floor = white
+    b.add_quad([(-1.5, 0, 2.55), (-1.5, 0, -2.55), (-1.5, 2.5, -2.55), (-1.5, 2.5, 2.55)], (1, 0, 0), (0, 0, -1), red)
+    b.add_quad([(-1.5, 0, 7.0), (6.0, 0, 7.0), (6.0, 0, -2.55), (-1.5, 0, -2.55)], (0, 1, 0), (1, 0, 0), floor)
+    b.add_quad([(-1.5, 0, -2.55), (1.5, 0, -2.55), (1.5, 2.5, -2.55), (-1.5, 2.5, -2.55)], (0, 0, 1), (1, 0, 0), white)
+    light = b.matte(b.spectrum_srgb_nonlinear(0.9, 0.9, 0.9), emittance=b.spectrum_d65(4.0, D65_RGB))
+    b.add_quad([(-0.5, 2.499, -0.5), (0.5, 2.499, -0.5), (0.5, 2.499, 0.5), (-0.5, 2.499, 0.5)], (0, -1, 0), (1, 0, 0), light)
+    ti = (b.spectrum_ior("Titanium", 0, TITANIUM_ETA_RGB), b.spectrum_ior("Titanium", 1, TITANIUM_K_RGB))
+    front = b.microfacet_metal(ti[0], ti[1], 0.1) if glossy else b.matte(b.spectrum_srgb_nonlinear(0.6, 0.6, 0.65))
+    b.add_uv_sphere(segments, rings, front, _translate(0.3, 0.0, 1.5) @ _scale(0.5) @ _translate(0, 1, 0))
+    if "many" in f:
+        rng = np.random.default_rng(3)
+        for i in range(36):
+            emit = b.spectrum_d65(0.5 + 0.1 * i, D65_RGB) if i < 10 else -1
+            m = b.matte(b.spectrum_srgb_nonlinear(*[float(c) for c in rng.uniform(0.1, 0.9, 3)]), emittance=emit)
+            x, y = -1.35 + 0.45 * (i % 6), 0.1 + 0.4 * (i // 6)
+            b.add_quad([(x, y, -2.5), (x + 0.4, y, -2.5), (x + 0.4, y + 0.35, -2.5), (x, y + 0.35, -2.5)], (0, 0, 1), (1, 0, 0), m)
+    # the sphere mesh's material
+    orange, olive = b.spectrum_srgb_nonlinear(0.8, 0.45, 0.15), b.spectrum_srgb_nonlinear(0.2, 0.3, 0.2)
+    refl = b.checker_spectrum(orange, olive, (0.0, 0.0), (6.0, 3.0)) if tex else orange
+    if multi:
+        a = b.microfacet_metal(ti[0], ti[1], 0.3) if glossy else b.matte(b.spectrum_srgb_nonlinear(0.7, 0.7, 0.75), sigma=0.5)
+        ball = b.mixed(a, b.matte(refl), 0.4)
+    else:
+        ball = b.matte(refl, sigma=0.4)
+    if tex:
+        ball = b.with_maps(ball, normal_map=b.checker_normal(0.3, False, (0.0, 0.0), (6.0, 3.0)))
+    # the cube's material
+    skin = b.image_spectrum(*synthetic_image(8, 8, 6), scale=(2.0, 2.0)) if tex else b.spectrum_srgb_nonlinear(0.3, 0.5, 0.8)
+    if multi:
+        al = b.metal(b.spectrum_grey(0.6), b.spectrum_ior("Aluminium", 0, ALUMINIUM_ETA_RGB), b.spectrum_ior("Aluminium", 1, ALUMINIUM_K_RGB))
+        rough = b.matte(b.spectrum_srgb_nonlinear(0.7, 0.6, 0.3), sigma=0.6)
+        crate = b.summed(b.mixed(b.matte(skin), rough, 0.4), al)
+    else:
+        crate = b.matte(skin)
+    if tex:
+        crate = b.with_maps(crate, alpha_map=b.checker_float(1.0, 0.0, (0.0, 0.0), (3.0, 3.0)))
+    if "inst" in f:
+        first_s = b.num_triangles()
+        b.add_uv_sphere(segments, rings, ball, np.eye(4))
+        first_c = b.num_triangles()
+        b.add_box(crate, np.eye(4))
+        end = b.num_triangles()
+        for m in _mix_sphere_placements():
+            b.add_instance(first_s, first_c - first_s, m)
+        for m in feature_mix_box_placements():
+            b.add_instance(first_c, end - first_c, m)
+    else:
+        for m in _mix_sphere_placements():
+            b.add_uv_sphere(segments, rings, ball, m)
+        for m in feature_mix_box_placements():
+            b.add_box(crate, m)
+    env = None
+    if "env" in f:
+        if "sky" not in _MIX_ENV:
+            sky = synthetic_sky(64, 32)
+            uvs = sky_to_uvs(sky)
+            _MIX_ENV["sky"] = (sky, 4.0, ibl_importance(sky), uvs, ibl_importance_uvs(uvs))
+        env = _MIX_ENV["sky"]
+    return b.build(cornell_camera(aspect), env=env, name="feature_mix_" + "_".join(sorted(f)))
+
+
+def feature_mix_rays(n=512, seed=2025):
+    """[n, 8] slrhip_ray rows aimed at feature_mix's alpha-cut cubes: origins uniform inside the box, targets uniform inside the
+    world boxes of the cube's placements (in turn), so that most rays meet an instanced triangle and about half of those meet a
+    hole first; dist_min 1e-4, the last quarter with a finite dist_max between half and one and a half times the distance to the
+    target (some stop short of the cube, some end inside it)."""
+    r = np.random.default_rng(seed)
+    org = r.uniform([-1.4, 0.1, -2.4], [1.4, 2.4, 2.4], size=(n, 3))
+    corners = np.array([[x, y, z, 1.0] for x in (-0.5, 0.5) for y in (-0.5, 0.5) for z in (-0.5, 0.5)])
+    boxes = [(corners @ m.T)[:, :3] for m in feature_mix_box_placements()]
+    lo = np.array([boxes[i % len(boxes)].min(0) for i in range(n)])
+    hi = np.array([boxes[i % len(boxes)].max(0) for i in range(n)])
+    d = lo + (hi - lo) * r.uniform(0.0, 1.0, size=(n, 3)) - org
+    dist = np.linalg.norm(d, axis=1)
+    rows = np.zeros((n, 8), np.float32)
+    rows[:, 0:3], rows[:, 3], rows[:, 4:7], rows[:, 7] = org, 1e-4, d / dist[:, None], np.inf
+    q = n - n // 4
+    rows[q:, 7] = dist[q:] * r.uniform(0.5, 1.5, size=n - q)
+    return rows

@@ -54,7 +54,7 @@ def random_rays(rng, n):
     return rays
 
 
-def make(name, sc, lib, width, height, spp, serial_spp):
+def make(name, sc, lib, width, height, spp, serial_spp, rays=None):
     if lib is None:
         raise SystemExit("reference library for %s not built" % name)
     ref = lib.scene(sc)
@@ -64,7 +64,8 @@ def make(name, sc, lib, width, height, spp, serial_spp):
     rng = np.random.default_rng(1234)
     picks = np.stack([rng.integers(0, width, 64), rng.integers(0, height, 64), rng.integers(0, 8, 64)], axis=1)
     samples = np.stack([ref.sample(st, int(x), int(y), int(p)) for x, y, p in picks])
-    rays = random_rays(rng, 512)
+    if rays is None:
+        rays = random_rays(rng, 512)
     hits = ref.trace(rays)
     st_serial = ob.settings(width // 2, height // 2)
     fb_serial, _ = ref.render_serial(st_serial, serial_spp)
@@ -307,7 +308,31 @@ def main_round3(only):
         make("spectral_instanced", scenes.cornell_instanced(1.0, 10, 5), spec, 40, 40, 8, 2)
 
 
+def aimed_rays():
+    """scenes.feature_mix_rays as ray records: through the holes of the alpha-cut cubes, a quarter with a finite dist_max."""
+    rows = scenes.feature_mix_rays(512, 2025)
+    rays = np.zeros(len(rows), dtype=ob.ray_dtype)
+    rays["org"], rays["dist_min"], rays["dir"], rays["dist_max"] = rows[:, 0:3], rows[:, 3], rows[:, 4:7], rows[:, 7]
+    return rays
+
+
+def main_mixes(only):
+    """Feature mixes (scenes.feature_mix): the libm-free mix of instances, textures and MultiBSDFs, and the mix of all six
+    features, both builds of the reference; frame size and spp of the *_instanced fixtures, the aimed rays in place of the
+    random ones.  The other mixes have no fixture: tests/test_feature_mixes.py pins the oracle to the reference on each."""
+    spec = ob.load("ref_spectral")
+    lib = ob.load("ref_rgb")
+    free, everything = ("inst", "tex", "multi"), ("inst", "tex", "multi", "env", "glossy", "many")
+    for name, features, build, size in (("rgb_mix_free", free, lib, 48), ("spectral_mix_free", free, spec, 40),
+                                        ("rgb_mix_all", everything, lib, 48), ("spectral_mix_all", everything, spec, 40)):
+        if not only or name in only:
+            make(name, scenes.feature_mix(features, 1.0), build, size, size, 8, 2, rays=aimed_rays())
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "mixes":
+        main_mixes(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "round3":
         main_round3(sys.argv[2:])
         sys.exit(0)
