@@ -144,8 +144,8 @@ int slrhip_debug_host_tree(const slrhip_scene_desc* desc, uint32_t config_flags,
 int slrhip_debug_quantize_nodes(const void* nodes, uint32_t n, void* nodes_q);
 
 /* The caller's samples through the fold: host_samples is [passes][height][width][components] float32 (HOST memory), passes 1 .. 64.
- * The shard's pixels are reordered with the context's own pixel list into a result window (pass-major, as the render kernels
- * write it; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's
+ * The shard's pixels are reordered with the context's own pixel list into a result window (pixel-major, as the render kernels
+ * write it: a pixel's passes side by side; pixels outside the shard are ignored), the window is uploaded, and the fold the render would launch in the context's
  * current state — statistics on or off, clamp on or off — adds it to the sensor, the noise records and the clamp records, after
  * whatever the render has added so far.  Blocking (synchronises the device).  The render's counters and its error word are
  * untouched.  The call counts as the render having begun (slrhip_statistics_begin and slrhip_clamp_begin are refused after it),

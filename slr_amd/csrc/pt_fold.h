@@ -11,8 +11,10 @@ namespace slrhip {
 // ImageSensor::add for the passes of a finished window (Core/ImageSensor.cpp:52-62 -> SpectrumStorage::add): per pixel and bin,
 // sum += value with the compensated sum of BasicTypes/CompensatedSum.h:24-30, the entries taken in PASS ORDER — the order in which
 // one thread of the reference adds the samples of a pixel, whatever slot rendered them here.  One thread per float4 of the
-// sensor (RGB: one per pixel, the fourth component idles; spectral: four per pixel); the window is pass-major, so the threads of
-// a wave read consecutive 16-byte entries at every pass: a streaming kernel (window bytes / HBM rate).
+// sensor (RGB: one per pixel, the fourth component idles; spectral: four per pixel); the window is pixel-major (windowEntry,
+// pt_kernels.h), so a thread's entries are contiguous and the threads of a wave are a pixel's passes apart: a thread asks for a
+// whole 128-byte line of its pixel at a time (RGB: eight passes; spectral: a quad asks for four passes, 256 bytes), every line of
+// the window is fetched once: a streaming kernel (window bytes / HBM rate).
 // kStats (slrhip_statistics_begin): the same pass over the window also updates the pixel's noise record {mean, M2, n, max} of the
 // samples' luminance (pt_luminance.h) with float32 Welford steps in pass order — the entries are in registers already, the
 // extra traffic is one 16-byte record per pixel and window.  Spectral: the four planes of a pixel are four adjacent lanes (elems
@@ -115,7 +117,7 @@ struct FoldClamp<true, kSpectral> {
 // Element e of a window of `elems` elements per pass (e < elems; the caller's early exit).  kIndexed (slrhip_render_adaptive): the
 // window is over a compact pixel list, and compact pixel i adds into the sensor and the record of pixel indexMap[i] of the shard;
 // a spectral quad (four adjacent elements, e >> 2 = the compact pixel) moves as a whole, so the quad exchange of FoldStats holds.
-// The window is read at e either way.  Not indexed: the pixel is the element's own, and indexMap is not read.
+// The window is read at the compact pixel's entries either way.  Not indexed: the pixel is the element's own, and indexMap is not read.
 template <bool kClamp, bool kStats, bool kSpectral, bool kIndexed>
 __device__ __forceinline__ void foldElement(const PathBuffers& pb, uint32_t e, uint32_t elems, uint32_t passes, float4* statRecords,
                                             const uint32_t* indexMap, const FoldClampArgs<kClamp>& clampArgs) {
@@ -126,11 +128,34 @@ __device__ __forceinline__ void foldElement(const PathBuffers& pb, uint32_t e, u
     float4 s = pb.fbSum[dst], c = pb.fbComp[dst];
     FoldStats<kStats, kSpectral> st(statRecords, pixel);
     FoldClamp<kClamp, kSpectral> cl(clampArgs, pixel);
-    const float4* r = pb.results + e;
+    // the pixel's entries are contiguous (windowEntry): pass p of this lane's plane is r[p * planes]
+    constexpr uint32_t planes = kSpectral ? 4u : 1u;
+    const float4* r = pb.results + windowEntry(compact, 0u, passes) * planes + plane;
     uint32_t p = 0;
+    if constexpr (!kSpectral) {
+        // RGB: eight entries requested together — the 128 bytes of a pixel's passes p .. p + 7, so that a line is fetched once
+        // (the lanes of a wave are `passes` entries apart); added one after the other
+        for (; p + 8 <= passes; p += 8) {
+            float4 v[8];
+            float y[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = r[p + k];
+            if constexpr (kClamp) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) y[k] = cl.apply(v[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { kahanAdd(s.x, c.x, v[k].x); kahanAdd(s.y, c.y, v[k].y); kahanAdd(s.z, c.z, v[k].z); kahanAdd(s.w, c.w, v[k].w); }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if constexpr (kClamp) st.addY(y[k]);
+                else st.add(v[k]);
+            }
+        }
+    }
     for (; p + 4 <= passes; p += 4) {
-        // four entries requested together; added one after the other
-        float4 v0 = r[(size_t)p * elems], v1 = r[(size_t)(p + 1) * elems], v2 = r[(size_t)(p + 2) * elems], v3 = r[(size_t)(p + 3) * elems];
+        // four entries requested together (spectral: the 256 bytes of a quad's four passes); added one after the other
+        float4 v0 = r[(size_t)p * planes], v1 = r[(size_t)(p + 1) * planes], v2 = r[(size_t)(p + 2) * planes], v3 = r[(size_t)(p + 3) * planes];
         float y0, y1, y2, y3;
         if constexpr (kClamp) { y0 = cl.apply(v0); y1 = cl.apply(v1); y2 = cl.apply(v2); y3 = cl.apply(v3); }
         kahanAdd(s.x, c.x, v0.x); kahanAdd(s.y, c.y, v0.y); kahanAdd(s.z, c.z, v0.z); kahanAdd(s.w, c.w, v0.w);
@@ -141,7 +166,7 @@ __device__ __forceinline__ void foldElement(const PathBuffers& pb, uint32_t e, u
         else { st.add(v0); st.add(v1); st.add(v2); st.add(v3); }
     }
     for (; p < passes; ++p) {
-        float4 v = r[(size_t)p * elems];
+        float4 v = r[(size_t)p * planes];
         float y;
         if constexpr (kClamp) y = cl.apply(v);
         kahanAdd(s.x, c.x, v.x); kahanAdd(s.y, c.y, v.y); kahanAdd(s.z, c.z, v.z); kahanAdd(s.w, c.w, v.w);

@@ -113,10 +113,13 @@ struct PathBuffers {
     float4* alpha;                // path throughput (+ pdf of the sampled direction)
     float4* spR;                  // path radiance Kahan sum (sp) (+ camera weight)
     float4* spC;                  // its compensation
-    // Result window of the render call: one entry per (pass of the window, pixel of the shard), pass-major — RGB one float4,
-    // spectral four (the sixteen bins of SpectrumStorage) — written once by the slot whose path was that sample; then the
-    // sensor itself: per pixel the Kahan sum and its compensation (CompensatedSum, BasicTypes/CompensatedSum.h:24-30), kept
-    // across the render calls of one slrhip_render_begin.
+    // Result window of the render call: one entry per (pixel of the shard, pass of the window), PIXEL-major — entry
+    // windowEntry(pixel, pass, P) = pixel x P + pass with P the pass count of the window being rendered (RenderParams::sppCount,
+    // not the allocation's: the windows of a call may differ in P); RGB one float4, spectral four (the sixteen bins of
+    // SpectrumStorage) — written once by the slot whose path was that sample.  The 64 slots of a k_shade wave hold consecutive
+    // passes of one pixel (WorkItem below), so a wave's results and records are one contiguous run (1 KiB in RGB), and the passes
+    // of a pixel that k_fold adds are contiguous too.  Then the sensor itself: per pixel the Kahan sum and its compensation
+    // (CompensatedSum, BasicTypes/CompensatedSum.h:24-30), kept across the render calls of one slrhip_render_begin.
     // While a sample has not finished, its entry holds the primary pass's record of its camera ray instead ({triangle, t, b1, b2}:
     // the whole RGB entry, the first float4 of a spectral one; RenderParams::primary) and primaryInstance[entry] the instance of
     // that hit (instanced scenes only, else nullptr).
@@ -201,6 +204,12 @@ struct RenderParams {
 // (measured: with the slots of a wave spread over an 8 x 8 tile the traversal launch took 2.1 ms instead of 1.76).  Static
 // queues need no global counter: one word that every wave bumps saturates near 88 atomics per microsecond (above).
 static const uint32_t kWorkRotate = 40503u;
+// The entry of sample (pixel, pass of the window) in a result window of windowPasses passes (PathBuffers::results, in entries;
+// PathBuffers::primaryInstance, in words).  It does not depend on the pixel count: a window over a compact list
+// (slrhip_render_adaptive) is laid out the same way.
+__host__ __device__ inline size_t windowEntry(uint32_t pix, uint32_t passOfWindow, uint32_t windowPasses) {
+    return (size_t)pix * windowPasses + passOfWindow;
+}
 struct WorkItem {
     uint32_t pix, pass;           // pass relative to RenderParams::sppBegin
     bool valid;                   // false: the queue is exhausted (every later item of this queue is invalid too)

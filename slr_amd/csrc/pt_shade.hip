@@ -75,7 +75,9 @@ void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecor
         return;
     }
     const FoldClampArgs<false> off;
-    if (!statRecords) hipLaunchKernelGGL((k_fold<false, false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
+    // (the plain fold too has a spectral instantiation: where a lane's entries lie depends on the planes per pixel)
+    if (!statRecords && rp.spectral) hipLaunchKernelGGL((k_fold<false, false, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
+    else if (!statRecords) hipLaunchKernelGGL((k_fold<false, false, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
     else if (rp.spectral) hipLaunchKernelGGL((k_fold<false, true, true>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
     else hipLaunchKernelGGL((k_fold<false, true, false>), grid, block, 0, stream, pb, elems, rp.sppCount, statRecords, off);
 }

@@ -913,7 +913,7 @@ __device__ __forceinline__ void startSample(const DevScene& sc, const PathBuffer
 template <class S>
 __device__ __forceinline__ void loadPrimaryRecord(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t pix, uint32_t passOfWindow,
                                                   float4& h, int32_t& inst) {
-    const size_t entry = (size_t)passOfWindow * rp.numPixels + pix;
+    const size_t entry = windowEntry(pix, passOfWindow, rp.sppCount);
     h = pb.results[entry * (S::N == 3 ? 1u : 4u)];
     inst = sc.instances ? pb.primaryInstance[entry] : -1;
 }
@@ -938,7 +938,7 @@ __device__ __forceinline__ void writeResult(const PathBuffers& pb, const RenderP
         if (F_SPVALID(flags)) SpecIO<S>::load(pb.spR, nullptr, slot * pb.spStride, rp.numSlots * pb.spStride, C, unusedW);     // else the path gathered nothing: C = 0
     }
     const S weight = (S(1.0f) * S(1.0f)) * camW;
-    storeResult(pb.results, (size_t)hdr.w * rp.numPixels + hdr.x, storageAddend(weight * C, S::N == 3 ? 0.0f : __uint_as_float(hdr.z)));
+    storeResult(pb.results, windowEntry(hdr.x, hdr.w, rp.sppCount), storageAddend(weight * C, S::N == 3 ? 0.0f : __uint_as_float(hdr.z)));
 }
 
 // What the finishing lanes of a k_shade workgroup hand to its first lanes: the samples to start.

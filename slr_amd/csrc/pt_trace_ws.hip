@@ -855,14 +855,18 @@ void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* h
 // the host sizes the windows).  The producer wave GENERATES the camera ray of each index into the LDS ring — the path tracer's own
 // draws and camera arithmetic (pt_camera.h) — so no ray array exists in HBM; the consumer's finish writes the sample's hit record, and
 // k_feature_fold computes the surface point of each hit (pt_surface.h, as logicSlot does) and adds it to the pixel in pass order.
-SLR_DEV void featureCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
-    const uint32_t pass = index / fp.numPixels, pix = index - pass * fp.numPixels;
+SLR_DEV void cameraRayOf(const DevCamera& cam, const FeatureParams& fp, uint32_t pix, uint32_t pass, float4& o, float4& d, uint32_t& xy) {
     xy = fp.pixelXY[pix];
     Rng rng;
     const CameraDraws draws = drawCameraSample(rng, fp.rngSeed, xy & 0xFFFFu, xy >> 16, fp.passBegin + pass, fp.timeStart, fp.timeEnd);
     const CameraRay r = sampleCameraRay(cam, fp.imageWidth, fp.imageHeight, draws);
     o = make_float4(r.org.x, r.org.y, r.org.z, 0.0f);
     d = make_float4(r.dir.x, r.dir.y, r.dir.z, INFINITY);
+}
+// the feature passes' numbering: the pixel fastest (their record windows are pass-major, writer and reader alike)
+SLR_DEV void featureCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+    const uint32_t pass = index / fp.numPixels, pix = index - pass * fp.numPixels;
+    cameraRayOf(cam, fp, pix, pass, o, d, xy);
 }
 
 // The consumer's side of the feature pass: the hit record of the sample, as the query kernel writes it, plus the instance — the
@@ -976,15 +980,23 @@ void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSu
 // ---- primary pass of a render window (launchPrimary, pt_kernels.h): the feature pass's producer, the path tracer's own hit record ----
 // A camera ray is a function of (pixel, pass, seed) alone, so the first segment of every sample of a window is traced here, before
 // the window's first iteration, instead of making a round trip through the slot state (startSample -> k_trace_ws -> k_shade).  A ring
-// entry is a sample of the launch, index = pass of the launch x pixels + pixel; finish writes {triangle, t, b1, b2} — what
-// WsRenderIO writes to PathBuffers::hit — to the sample's entry of the result window, which nobody else touches until the sample
-// finishes (writeResult), and the instance to its plane.  `stride`: float4 per entry (RGB 1, spectral 4: the record is the first).
+// entry is a sample of the launch, index = pixel x passes of the launch + pass of the launch — the window's own order
+// (windowEntry, pt_kernels.h), so consecutive ring entries are consecutive passes of one pixel: all but identical camera rays in a
+// consumer wave, and consecutive record addresses.  finish writes {triangle, t, b1, b2} — what WsRenderIO writes to
+// PathBuffers::hit — to the sample's entry of the result window, which nobody else touches until the sample finishes
+// (writeResult), and the instance to its plane.  `stride`: float4 per entry (RGB 1, spectral 4: the record is the first).
 struct PrimaryParams {
-    FeatureParams fp;             // the camera arguments of the launch; records = the launch's first entry; errorWord = the render's
-    int32_t* instances;           // the launch's first entry of PathBuffers::primaryInstance, or nullptr
+    FeatureParams fp;             // the camera arguments of the launch; records = the entry of (pixel 0, the launch's first pass); errorWord = the render's
+    int32_t* instances;           // that entry of PathBuffers::primaryInstance, or nullptr
     uint64_t* totals;
     uint32_t stride;
+    uint32_t windowPasses;        // passes of the window (>= fp.numPasses, the launch's): the distance of two pixels' entries
 };
+// index of the launch -> (pixel, pass of the launch): the pass fastest
+SLR_DEV void primaryCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+    const uint32_t pix = index / fp.numPasses, pass = index - pix * fp.numPasses;
+    cameraRayOf(cam, fp, pix, pass, o, d, xy);
+}
 struct WsPrimaryIO {
     const DevScene& sc;
     const PrimaryParams& pp;
@@ -992,12 +1004,15 @@ struct WsPrimaryIO {
     __device__ WsPrimaryIO(const DevScene& s, const PrimaryParams& p) : sc(s), pp(p), errorWord(p.fp.errorWord) {}
     __device__ __forceinline__ void worldRay(uint32_t slot, float4& o, float4& d) const {
         uint32_t xy;
-        featureCameraRay(sc.camera, pp.fp, slot, o, d, xy);
+        primaryCameraRay(sc.camera, pp.fp, slot, o, d, xy);
     }
     template <bool INST>
     __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
-        ntStore4(pp.fp.records + (size_t)slot * pp.stride, make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2));
-        if (INST) __builtin_nontemporal_store(hitInst, pp.instances + slot);
+        // windowEntry(pixel, pass of the launch, windowPasses) relative to the launch's first entry; a launch of the whole window: slot itself
+        size_t entry = slot;
+        if (pp.windowPasses != pp.fp.numPasses) entry += (size_t)(slot / pp.fp.numPasses) * (pp.windowPasses - pp.fp.numPasses);
+        ntStore4(pp.fp.records + entry * pp.stride, make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2));
+        if (INST) __builtin_nontemporal_store(hitInst, pp.instances + entry);
     }
 };
 
@@ -1009,7 +1024,7 @@ __global__ __launch_bounds__(64 * (NC + 1)) __attribute__((amdgpu_waves_per_eu(8
     WsCounts cnt;
     WsDebug dbg;
     if (threadIdx.x < 64) {
-        const uint32_t rays = wsProduceIndexed(n, 0u, pp.fp.errorWord, lds, dbg, [&](uint32_t i, float4& o, float4& d) { uint32_t xy; featureCameraRay(sc.camera, pp.fp, i, o, d, xy); });
+        const uint32_t rays = wsProduceIndexed(n, 0u, pp.fp.errorWord, lds, dbg, [&](uint32_t i, float4& o, float4& d) { uint32_t xy; primaryCameraRay(sc.camera, pp.fp, i, o, d, xy); });
         // Scene::intersect of PathTracingRenderer.cpp:147, counted where it is traced: one atomic per workgroup
         if (threadIdx.x == 0 && rays) atomicAdd((unsigned long long*)&pp.totals[totalIndex(T_EXT_RAYS, blockIdx.x % kShards)], (unsigned long long)rays);
     }
@@ -1032,7 +1047,8 @@ void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams
     if (n == 0) return;
     PrimaryParams pp{};
     pp.stride = rp.spectral ? 4u : 1u;
-    const size_t first = (size_t)firstPass * rp.numPixels;
+    pp.windowPasses = rp.sppCount;
+    const size_t first = windowEntry(0u, firstPass, rp.sppCount);
     pp.fp.pixelXY = pb.pixelXY; pp.fp.records = pb.results + first * pp.stride; pp.fp.errorWord = pb.errorWord;
     pp.fp.numPixels = rp.numPixels; pp.fp.numPasses = numPasses; pp.fp.passBegin = rp.sppBegin + firstPass;
     pp.fp.rngSeed = rp.rngSeed; pp.fp.timeStart = rp.timeStart; pp.fp.timeEnd = rp.timeEnd;

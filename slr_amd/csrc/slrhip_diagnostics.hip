@@ -66,7 +66,7 @@ int slrhip_debug_fold(slrhip_ctx* ctx, const float* hostSamples, uint32_t passes
     for (uint32_t p = 0; p < passes; ++p)
         for (uint32_t i = 0; i < rp.numPixels; ++i) {
             const float* src = hostSamples + (((size_t)p * rp.imageHeight + (xy[i] >> 16)) * rp.imageWidth + (xy[i] & 0xFFFFu)) * comps;
-            float4* dst = window.data() + (size_t)p * elems + (size_t)i * planes;
+            float4* dst = window.data() + windowEntry(i, p, passes) * planes;
             if (rp.spectral) for (uint32_t q = 0; q < 4; ++q) dst[q] = make_float4(src[4 * q], src[4 * q + 1], src[4 * q + 2], src[4 * q + 3]);
             else dst[0] = make_float4(src[0], src[1], src[2], 0.0f);
         }
