@@ -24,8 +24,6 @@ struct Box {
 struct QBVH {
     std::vector<QNode> nodes;        // breadth-first; nodes[0] is the root
     std::vector<QNodeQ> quantized;   // same nodes, 8-bit child boxes (quantizeNodes); empty unless asked for
-    std::vector<QNode8> nodes8;      // the same binary tree collapsed to eight-wide quantized nodes (buildQBVH's wide8 argument); same leaf packets
-    uint32_t depth8 = 0;
     std::vector<LeafTri> leafTris;   // leaf packets, contiguous per leaf
     uint32_t depth = 0;              // levels of 4-wide nodes
     std::vector<uint32_t> levelFirst;   // first node of each level of the tree built last (breadth-first: a level is a run of nodes); instanced: the top level's
@@ -73,7 +71,7 @@ int buildGeometryDevice(const slrhip_vertex* verts, uint32_t numVerts, const slr
                         uint32_t numLights, bool wantQuantized, DeviceGeometry* out, std::string* err);
 
 // Returns 0 on success.
-int buildQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, uint32_t numTris, QBVH* out, bool spatialSplits = false, bool wide8 = false);
+int buildQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, uint32_t numTris, QBVH* out, bool spatialSplits = false);
 
 // Scenes with instanced meshes (slrhip_instance): one tree per distinct mesh in its local space and a top-level tree over the loose
 // triangles and the instances' world boxes, all in ONE node array and ONE leaf array (the top level first); an instance is a child

@@ -1,7 +1,7 @@
 // pt_albedo.hip — device code of the albedo feature buffer (slrhip_render_albedo / slrhip_resolve_albedo) and of slrhip_modulate, as
 // defined in include/slrhip.h.  gfx950, wave64.
 //
-// The traversal of an albedo pass is the feature pass's (k_features_ws, pt_trace_ws.hip: camera rays made on the spot, one hit record
+// The traversal of an albedo pass is the feature pass's (launchFeatureTrace, pt_trace_indexed.hip: camera rays made on the spot, one hit record
 // {triangle, instance, dist, b1} per sample, b2 in a plane of its own).  k_albedo_fold turns a window's records into base colours: one
 // lane owns a pixel and takes its passes in pass order — the material record of the hit triangle (MatIO), its textures at the hit's
 // texture coordinate (texturizeMat), BSDF::getBaseColor(All) of the lobe (bsdfBaseColor, pt_bsdf.h) or of the MultiBSDF

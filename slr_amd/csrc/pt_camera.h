@@ -1,9 +1,10 @@
 // pt_camera.h — the camera half of Job::kernel (Renderers/PathTracingRenderer.cpp:100-120) as device functions: the sample's
 // draws and PerspectiveCamera::sample + PerspectiveIDF::sample (Cameras/PerspectiveCamera.cpp:33-74).  One statement of the
-// reference's arithmetic, used by the path tracer's startSample (pt_shade_kernels.h), by the feature pass and by
-// slrhip_camera_rays (k_features_ws, k_camera_rays: pt_trace_ws.hip).
+// reference's arithmetic, used by the path tracer's startSample (pt_shade_kernels.h), by the producer waves of the feature trace
+// and the primary pass (pt_trace_indexed.hip) and by slrhip_camera_rays (k_camera_rays, pt_features.hip).
 #pragma once
 #include "pt_device.h"
+#include "pt_kernels.h"
 
 namespace slrhip {
 
@@ -53,6 +54,26 @@ SLR_DEV CameraRay sampleCameraRay(const DevCamera& cam, uint32_t imageWidth, uin
     r.dirLocalZ = dirLocal.z;
     r.dir = lf.fromLocal(dirLocal);
     return r;
+}
+
+// The camera ray of (pixel of the shard, pass of the launch) as a ring entry or a slrhip_ray: {org, distMin 0}, {dir, distMax inf}
+SLR_DEV void cameraRayOf(const DevCamera& cam, const FeatureParams& fp, uint32_t pix, uint32_t pass, float4& o, float4& d, uint32_t& xy) {
+    xy = fp.pixelXY[pix];
+    Rng rng;
+    const CameraDraws draws = drawCameraSample(rng, fp.rngSeed, xy & 0xFFFFu, xy >> 16, fp.passBegin + pass, fp.timeStart, fp.timeEnd);
+    const CameraRay r = sampleCameraRay(cam, fp.imageWidth, fp.imageHeight, draws);
+    o = make_float4(r.org.x, r.org.y, r.org.z, 0.0f);
+    d = make_float4(r.dir.x, r.dir.y, r.dir.z, INFINITY);
+}
+// the feature passes' numbering: the pixel fastest (their record windows are pass-major, writer and reader alike)
+SLR_DEV void featureCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+    const uint32_t pass = index / fp.numPixels, pix = index - pass * fp.numPixels;
+    cameraRayOf(cam, fp, pix, pass, o, d, xy);
+}
+// the primary pass's numbering: the pass fastest (the result window's own order, windowEntry)
+SLR_DEV void primaryCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+    const uint32_t pix = index / fp.numPasses, pass = index - pix * fp.numPasses;
+    cameraRayOf(cam, fp, pix, pass, o, d, xy);
 }
 
 } // namespace slrhip

@@ -28,7 +28,6 @@ struct DevScene {
     const float* lightCDF;        // numLights + 1 entries
     uint32_t numNodes;
     const float4* nodesQ;         // QNodeQ array (4 x float4 per node) or nullptr: large scenes traverse this one
-    const float4* nodes8;         // QNode8 array (8 x float4 per node) or nullptr: the eight-wide quantized tree (k_trace_ws only)
     uint32_t numMaterials;
     uint32_t numLights;
     uint32_t lightPow2;           // prevPowerOf2(numLights)
@@ -285,18 +284,18 @@ void launchTraceBatch(const DevScene& sc, const float4* org, const float4* dir, 
 void launchTraceWs(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, uint32_t blocks, bool count,
                    hipStream_t stream);
 int traceWsBlocksPerCU(bool quantizedTree);
-// The primary pass of a render window (pt_trace_ws.hip, k_primary_ws): the camera ray of every sample of the passes
+// The primary pass of a render window (pt_trace_indexed.hip, WsPrimaryIO): the camera ray of every sample of the passes
 // [firstPass, firstPass + numPasses) of the window (relative to rp.sppBegin) through the wave-specialised consumer, made on the spot
 // by the producer wave; the hit record goes to the sample's entry of the result window (PathBuffers::results, primaryInstance),
 // errors to the render's error word, the ray count to T_EXT_RAYS.  numPixels x numPasses < 2^31 (render_plan.h, planPrimary).
 void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
                    hipStream_t stream);
-// ray queries (slrhip_intersect_rays / slrhip_test_visibility) through the same consumer: rays = n slrhip_ray records (2 x float4);
+// ray queries (slrhip_intersect_rays / slrhip_test_visibility) through the same consumer (pt_trace_indexed.hip): rays = n slrhip_ray records (2 x float4);
 // visible == nullptr: closest hit into hits (slrhip_hit) and, if given, instances; else visibility into visible.  n < 2^31.
 void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,
                    int numCUs, hipStream_t stream);
 
-// First-hit feature pass (slrhip_render_features; pt_trace_ws.hip): the passes [passBegin, passBegin + numPasses) of every pixel of
+// First-hit feature pass (slrhip_render_features; pt_features.hip, traversal: pt_trace_indexed.hip): the passes [passBegin, passBegin + numPasses) of every pixel of
 // the shard in one launch.  records: numPixels x numPasses float4 {triangle, instance, dist, b1}, pass-major; b2: as many floats,
 // or nullptr when no vector channel is asked for (see WsFeatureIO).
 struct FeatureParams {

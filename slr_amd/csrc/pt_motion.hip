@@ -1,7 +1,7 @@
 // pt_motion.hip — device code of the motion pass (slrhip_render_motion / slrhip_resolve_motion), as defined in include/slrhip.h.
 // gfx950, wave64.
 //
-// The traversal of a motion pass is the feature pass's (k_features_ws, pt_trace_ws.hip: camera rays made on the spot, one hit record
+// The traversal of a motion pass is the feature pass's (launchFeatureTrace, pt_trace_indexed.hip: camera rays made on the spot, one hit record
 // {triangle, instance, dist, b1} per sample).  k_motion_fold turns a window's records into motion vectors: one lane owns a pixel and
 // takes its passes in pass order.  The hit point is not in the record: the fold makes the sample's camera ray again from
 // (seed, pixel, pass) with the path tracer's own draws and camera arithmetic (pt_camera.h, as featureCameraRay does) and walks `dist`

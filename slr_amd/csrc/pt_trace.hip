@@ -5,7 +5,8 @@
 // (Surface/TriangleMesh.cpp:131-178) and Scene::testVisibility (SurfaceObject.cpp:418-430).
 //
 // The stand-alone ray-query kernel behind slrhip_trace_rays (k_trace_batch); the render path traces with the wave-specialised
-// kernel of pt_trace_ws.hip and, for the last paths of a call, with the same device function inside the tail kernel.
+// kernel of pt_trace_ws.hip (consumer: pt_trace_ws.h) and, for the last paths of a call, with traverse() inside the tail kernel;
+// both are built on the slab, triangle, tie-rule and instance functions of pt_traverse.h.
 // Workgroups stage the top of the tree — the first kTopNodes breadth-first nodes — in LDS once, then stride over the rays, 64 per
 // wave at a time.  One lane = one ray; per node four child slabs are tested from six 16-byte loads
 // whose near/far selection (QBVH.h:66-71: invRayDir > 0 ? min : max) is folded into per-ray load

@@ -58,7 +58,7 @@ WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthO
 // iteration, the hit record kept in the sample's entry of the result window.  Off with SLRHIP_FLAG_NO_PRIMARY_PASS, and with
 // SLRHIP_FLAG_COUNT_TRAVERSAL: the nodes and triangles per ray are counted by the wavefront kernels, and they are properties of the
 // rays, not of the schedule.  A launch numbers its samples in 31 bits, so the window's passes go in groups of passesPerLaunch.
-const uint32_t kPrimaryMaxSamples = 0x7FFFFFFFu;        // ring indices of one launch (pt_trace_ws.hip, wsProduceIndexed)
+const uint32_t kPrimaryMaxSamples = 0x7FFFFFFFu;        // ring indices of one launch (pt_trace_ws.h, wsProduceIndexed)
 struct PrimaryPlan {
     bool on = false;
     uint32_t passesPerLaunch = 0;              // numPixels x passesPerLaunch <= kPrimaryMaxSamples

@@ -349,15 +349,13 @@ int prepareTree(const slrhip_scene_desc& d, const slrhip_config& config, const M
         return SLRHIP_OK;
     }
     else {
-        static const bool wide8 = [] { const char* e = tuningEnv("SLRHIP_WIDE8"); return e && std::string(e) == "1"; }();      // measurement: the eight-wide quantized tree
         p.build = TreeBuild::Host;
-        if (buildQBVH(d.vertices, d.triangles, d.num_triangles, &p.bvh, (config.flags & SLRHIP_FLAG_BVH_SPATIAL_SPLITS) != 0, wide8) != 0)
+        if (buildQBVH(d.vertices, d.triangles, d.num_triangles, &p.bvh, (config.flags & SLRHIP_FLAG_BVH_SPATIAL_SPLITS) != 0) != 0)
             return reject(err, SLRHIP_ERR_INVALID_ARGUMENT, "BVH build failed");
         PREP_TRY(checkTreeLimits(p.bvh.depth, p.bvh.nodes.size(), p.bvh.leafTris.size(), "tree deeper than the 64-entry traversal stack (QBVH.h:299)", err));
     }
     p.quantized = p.build == TreeBuild::Host && useQuantizedNodes(p.bvh.nodes.size());      // instanced scenes traverse float nodes
     if (p.quantized) quantizeNodes(&p.bvh);
-    p.wide8 = !p.bvh.nodes8.empty() && 7 * p.bvh.depth8 + 1 <= 64;          // up to seven pushes per level on the 64-entry stack
     return SLRHIP_OK;
 }
 

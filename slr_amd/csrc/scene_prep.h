@@ -28,7 +28,6 @@ struct PreparedScene {
     QBVH bvh;                                     // host and instanced builds: alpha records patched into the leaves
     std::vector<DevInstance> instances;
     bool quantized = false;                       // host build: upload bvh.quantized as well
-    bool wide8 = false;                           // host build: upload bvh.nodes8 as well
     bool wantQuantized = false;                   // device build: ask for the quantized records (the tree could pass 64 Ki nodes)
 
     std::vector<ShadeTri> shadeTris;              // empty for the device build (it writes these records itself)

@@ -75,7 +75,6 @@ static void bindScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepare
     DevScene sc{};
     sc.nodes = reinterpret_cast<const float4*>(ctx->nodes.ptr); sc.numNodes = numNodes;
     sc.nodesQ = quantized ? reinterpret_cast<const float4*>(ctx->nodesQ.ptr) : nullptr;
-    sc.nodes8 = p.wide8 ? reinterpret_cast<const float4*>(ctx->nodes8.ptr) : nullptr;
     sc.leafTris = reinterpret_cast<const float4*>(ctx->leafTris.ptr);
     sc.shadeTris = ctx->shadeTris.ptr;
     sc.instances = p.instances.empty() ? nullptr : reinterpret_cast<const float4*>(ctx->instances.ptr); sc.numInstances = (uint32_t)p.instances.size();
@@ -132,7 +131,6 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     else {
         HIP_TRY(ctx->nodes.upload(p.bvh.nodes));
         if (p.quantized) HIP_TRY(ctx->nodesQ.upload(p.bvh.quantized));
-        if (p.wide8) HIP_TRY(ctx->nodes8.upload(p.bvh.nodes8));
         HIP_TRY(ctx->leafTris.upload(p.bvh.leafTris));
     }
     HIP_TRY(ctx->textures.upload(p.textures));
@@ -700,7 +698,7 @@ int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples) {
 }
 
 // Ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): the render's wave-specialised traversal fed from
-// the caller's ray array (pt_trace_ws.hip, k_query_ws).  Stream-ordered; no allocation, no copy, no host synchronisation: the
+// the caller's ray array (pt_trace_indexed.hip, WsQueryIO).  Stream-ordered; no allocation, no copy, no host synchronisation: the
 // only other work is clearing the query error word on the same stream.
 static int checkQueryArgs(slrhip_ctx* ctx, const char* what, const void* rays, uint32_t n, const void* out, size_t outAlign, const void* extra) {
     const std::string w(what);

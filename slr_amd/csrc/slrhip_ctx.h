@@ -92,7 +92,6 @@ struct slrhip_ctx {
     // scene
     DevArray<slrhip::QNode> nodes;
     DevArray<slrhip::QNodeQ> nodesQ;
-    DevArray<slrhip::QNode8> nodes8;
     DevArray<slrhip::DevTexture> textures;
     DevArray<slrhip::DevMatTex> matTex;
     DevArray<float4> triUV, alphaTris;

@@ -7,7 +7,7 @@ The reference asks the tree-free question — of all triangles, which does this 
 arithmetic (helpers.brute_force_hits) on scenes whose coordinates are exact (scenes.lattice_terrain and its kin), so every ray
 has ONE right answer and no ray is exempted on the device side.  CPU: the reference against the oracle's tree and against a
 float64 evaluation, the scene generators, the families.  GPU (MI355X): slrhip_trace_rays (k_trace_batch),
-slrhip_intersect_rays and slrhip_test_visibility (k_query_ws: closest hit, any hit, the quantized and the instanced variants) on
+slrhip_intersect_rays and slrhip_test_visibility (k_ring_ws with the query client: closest hit, any hit, the quantized and the instanced variants) on
 every tree the upload builds.
 
 Measured on the CPU (8 threads): the brute force takes 0.1 s on the 139-triangle terrain (6 532 rays), 0.6 s on the 1 069-triangle
@@ -298,7 +298,7 @@ TREES = {
 @pytest.mark.gpu
 @pytest.mark.parametrize("tree", list(TREES))
 def test_every_entry_point_equals_the_brute_force(tree):
-    """k_trace_batch, k_query_ws closest-hit and any-hit (float, quantized and instanced nodes) against the brute force, ray for
+    """k_trace_batch, the query kernel's closest-hit and any-hit (float, quantized and instanced nodes) against the brute force, ray for
     ray.  The exact tie rule is asserted where it is provable: on the deck (every box is the same box, every triangle is tested:
     the last layer wins, triangle >= 8 190) and on the terrain's rays whose tie set lies in the two coincident quads (identical
     boxes, t exact for det = 16: the second quad wins).  grid_quantized: 404 rays against 320 011 triangles, 1.1 s of brute force."""

@@ -8,7 +8,7 @@ Rays: `camera` = 4 Mi rays from the camera position through a grid over the scen
 Query times are device-event times of one call (median of --reps).  slrhip_trace_rays copies through the host and synchronises:
 its wall time is printed, and its KERNEL time comes from a run of this script under
     rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/query_rate.py
-(k_trace_batch vs k_query_ws in the stats file).  One JSON line per (scene, ray set); --out appends them to a file."""
+(k_trace_batch vs k_ring_ws<..., WsQueryIO> in the stats file).  One JSON line per (scene, ray set); --out appends them to a file."""
 import argparse
 import json
 import os
