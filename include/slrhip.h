@@ -351,6 +351,9 @@ typedef struct slrhip_profile {
 } slrhip_profile;
 
 /* config.flags */
+#define SLRHIP_FLAG_DYNAMIC_GEOMETRY 512u /* keep what slrhip_set_vertices works from (see there): the scene's vertex and index arrays, one box per leaf
+                                         * record and the tree's level table stay on the device after slrhip_upload_scene.  Memory: 44 B per vertex +
+                                         * 16 B per triangle + 32 B per leaf record.  Without the flag nothing is kept and nothing else changes.      */
 #define SLRHIP_FLAG_NO_PRIMARY_PASS 256u /* turn the primary pass OFF.  By default the camera ray of every sample of a result window is traced by one
                                          * pass before the window's iterations and a slot shades its new sample's first hit in the launch that
                                          * starts it; with this flag a new sample's camera ray goes through the slot state and the traversal
@@ -1248,7 +1251,7 @@ int slrhip_env_texels_to_uvs(const float* rgb, size_t num_texels, float* uvs);
  * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, count == 0, a misaligned
  * pointer (16 bytes), a range beyond slrhip_scene_desc::num_instances.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.
  * SLRHIP_ERR_UNSUPPORTED for a scene without instances.  Not covered: adding or removing instances, instances that emit, moving
- * loose triangles, a rebuild of the top level.                                                                                     */
+ * loose triangles (flat scenes: slrhip_set_vertices), a rebuild of the top level.                                                  */
 #define SLRHIP_INSTANCE_BAD_TRANSFORM 1u   /* a record of a call had a non-finite entry or a bottom row other than 0 0 0 1; its instance did not move */
 typedef struct slrhip_instance_transform {
     float local_to_world[16];
@@ -1300,6 +1303,56 @@ int slrhip_spectrum_to_rgb(int32_t spectrum_type, const float* lambdas, float la
 int slrhip_tonemap_bgr8(const float* framebuffer, int32_t width, int32_t height, int32_t components,
                         float scale, uint8_t* dst_bgr, size_t dst_bytes);
 int slrhip_save_bmp(const char* path, const uint8_t* bgr_bottom_up, int32_t width, int32_t height);
+
+/* ---- moving vertices without a scene upload ----------------------------------------------------------------------------------------
+ * The next frame of a deforming mesh: what the reference does by building a new TriangleMesh and a new aggregate over it
+ * (Surface/TriangleMesh.cpp, Core/SurfaceObject.cpp:226-250), with no descriptor check, no host tree build and no copy of any record.
+ * Together with slrhip_set_camera, slrhip_set_instance_transforms and slrhip_set_environment it completes what a second frame of
+ * the same scene can change without slrhip_upload_scene.
+ *
+ * A context created with SLRHIP_FLAG_DYNAMIC_GEOMETRY keeps, from slrhip_upload_scene on and all on the device: the scene's vertex
+ * array (44 B per vertex), its triangle index array (16 B per triangle), a scratch of one box per LeafTri record (32 B each: one per
+ * triangle) and, on the host, the first node of every tree level.  A 10 M-triangle grid of 5 M vertices costs 220 + 160 + 320 MB.
+ *
+ * slrhip_set_vertices replaces the vertices [first_vertex, first_vertex + count) of the kept array with the records at
+ * `device_src`: DEVICE memory, 4-byte aligned, `count` whole slrhip_vertex records — position, normal, tangent and texcoord all take
+ * effect.  Then everything that depends on vertices is rebuilt in place from the kept array, on the device: the leaf triangles
+ * (v0, e1, e2), the shading records, the light records (both copies), the texture coordinates of textured scenes and of the alpha
+ * records, every child box of the tree bottom-up, and the quantized nodes where they are in use.  The arithmetic is the upload's own,
+ * operation for operation (one definition: slr_amd/csrc/pt_triangle.h), the NaN normal of a degenerate triangle included.  Indices,
+ * materials, the light list and its distribution (every light's importance is the constant 1) stay.
+ *
+ * The contract.  From the call on, the context renders, answers ray queries (slrhip_intersect_rays, slrhip_test_visibility,
+ * slrhip_trace_rays) and fills feature and albedo buffers exactly as a fresh context does that uploaded the scene with the kept
+ * vertex array as it now stands: every bit of the frame, of the hits and of the samples / extension_rays / shadow_rays counters.
+ * The tree keeps its SHAPE — child words, node order, packet order, depth; bvh_nodes, bvh_depth and build_seconds keep the upload's
+ * values — and gets EXACT boxes: a packet's box is the min / max over the vertex positions of its triangles, an inner child's the
+ * min / max union of the valid child boxes of the node it names, with no padding.  Hits do not depend on the tree's shape because
+ * the tie rule among equal distances is a rule on (instance, triangle) pairs.  Speed does depend on it: after large deformation the
+ * tree fits the scene badly and rays visit more nodes; a caller for whom that matters uploads the scene again.  Measured (DESIGN.md
+ * 7.23): every vertex of the 10 M-triangle grid displaced by up to half a cell costs 1.14 - 1.16 x the nodes per ray of the tree as
+ * uploaded, which is 0.95 - 0.97 x what a fresh build of the displaced scene costs — at that amplitude a rebuild buys nothing.
+ *
+ * A record is checked on the device: all eleven floats finite.  A record that fails leaves ITS vertex exactly as it was, the others
+ * of the call move, and SLRHIP_GEOMETRY_BAD_VERTEX is set in a status word that slrhip_geometry_status reads and clears (it waits
+ * for `stream`).
+ *
+ * Ordering, as for slrhip_set_instance_transforms.  The call allocates nothing, copies nothing from the host and does not
+ * synchronise; its launches are ordered on `stream`.  No scene array is reallocated or moved, so a captured render graph stays
+ * valid.  NOTHING accumulated is reset; starting the new frame is the caller's slrhip_render_begin.
+ *
+ * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, count == 0, a misaligned
+ * pointer (4 bytes), a range beyond slrhip_scene_desc::num_vertices.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.
+ * SLRHIP_ERR_UNSUPPORTED: a context created without SLRHIP_FLAG_DYNAMIC_GEOMETRY, a scene with instances, a tree built with spatial
+ * splits (its leaf boxes are clipped and its references duplicated).
+ * Not covered: scenes with instances (mesh-tree refits, new mesh and instance boxes: a follow-up), spatial-split trees, adding or
+ * removing vertices or triangles, changing indices or materials, a rebuild when the tree has degraded (the caller uploads again),
+ * motion vectors of moved vertices (slrhip_render_motion still takes loose triangles to stand still), the C++ host mirror and the
+ * libSLR adapter.                                                                                                                   */
+#define SLRHIP_GEOMETRY_BAD_VERTEX 1u      /* a record of a call had a non-finite float; its vertex did not move */
+int slrhip_set_vertices(slrhip_ctx* ctx, const slrhip_vertex* device_src, uint32_t first_vertex, uint32_t count, void* stream);
+/* The SLRHIP_GEOMETRY_* bits of the calls since the last read, then cleared; waits for `stream`.  0 before any scene.              */
+int slrhip_geometry_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
 
 const char* slrhip_last_error_string(void);
 int slrhip_version(void);

@@ -111,6 +111,31 @@ int slrhip_debug_instance_update_check(int32_t have_scene, uint32_t num_instance
  * little room.                                                                                                                      */
 int slrhip_debug_top_level(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
 
+/* The argument checks of slrhip_set_vertices (slr_amd/csrc/render_plan.h, geometryUpdateRefusal), evaluated on the HOST with the
+ * function the entry point calls, for a context that holds a scene (have_scene != 0) or none, created with SLRHIP_FLAG_DYNAMIC_GEOMETRY
+ * (dynamic != 0) or without, whose tree came from builder `tree_builder` (SLRHIP_TREE_*, below) and whose scene has `num_instances`
+ * instances and `num_vertices` vertices: SLRHIP_OK if the call would go ahead, else the code it returns, with the reason in
+ * slrhip_last_error_string.  The pointer is only compared, never followed.  No GPU is touched.                                      */
+int slrhip_debug_geometry_update_check(int32_t have_scene, int32_t dynamic, uint32_t tree_builder, uint32_t num_instances, uint32_t num_vertices,
+                                       const void* device_src, uint32_t first_vertex, uint32_t count);
+
+/* What slrhip_set_vertices keeps and rewrites beyond the tree (slrhip_debug_tree reads that), read back to HOST memory as 32-bit
+ * words.  what:
+ *   0  the summary, 32 words: [0] levels of the tree, [1] nodes, [2] vertices, [3] triangles, [4] lights, [5] 1 if the shade tables are
+ *      staged (the lights have a second copy there), [6] the widest level one workgroup of the refit takes (wider levels: a launch
+ *      each), [7 .. 7 + levels] the first node of each level, then [1] again; after those: the float4 count of triUV (0 for a scene
+ *      without textures), the number of alpha records, the launches of the last slrhip_set_vertices call (0: none yet)
+ *   1  the kept vertices, 11 words each (slrhip_vertex)
+ *   2  the LightTri records, 36 words each: p0[3] (floats), triangle, p1[3], material, p2[3], 1 / area, n0[3], gn.x, n1[3], gn.y,
+ *      n2[3], gn.z, t0[3], 0, t1[3], 0, t2[3], 0
+ *   3  the same records as staged in the shade tables; SLRHIP_ERR_UNSUPPORTED when the tables are not staged
+ *   4  triUV, 8 words per triangle: u0 v0 u1 v1, u2 v2 0 0 (floats)
+ *   5  the alpha records, 8 words each: u0 v0 u1 v1, u2 v2 (floats), the texture's index, 0
+ * num_words: room at host_dst, at least that many.  Synchronises.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene,
+ * SLRHIP_ERR_UNSUPPORTED for a context without SLRHIP_FLAG_DYNAMIC_GEOMETRY or a scene slrhip_set_vertices does not cover,
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room.                                          */
+int slrhip_debug_geometry(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
+
 /* The tree builders (slr_amd/csrc/bvh.cpp, sbvh.cpp, bvh_device.hip), as the summary of the two read-outs below names them. */
 #define SLRHIP_TREE_HOST_SAH 0u              /* binned SAH over object partitions, on the host                                    */
 #define SLRHIP_TREE_HOST_SPATIAL_SPLITS 1u   /* the same with spatial splits (SLRHIP_FLAG_BVH_SPATIAL_SPLITS, SLRHIP_BVH=sbvh)   */

@@ -46,6 +46,7 @@ INVALID_CHILD, LEAF_FLAG, LEAF_COUNT_SHIFT, LEAF_INDEX_MASK, MAX_LEAF_TRIS = 0xF
 TREE_HOST_SAH, TREE_HOST_SPATIAL_SPLITS, TREE_DEVICE, TREE_INSTANCED = 0, 1, 2, 3
 TREE_BUILDERS = ("host SAH", "host spatial splits", "device", "instanced")
 INSTANCE_BAD_TRANSFORM = 1     # slrhip_instances_status: a record was not finite or not affine; its instance did not move
+GEOMETRY_BAD_VERTEX = 1        # slrhip_geometry_status: a record of set_vertices had a non-finite float; its vertex did not move
 TEX_CHECKER_SPECTRUM, TEX_CHECKER_FLOAT, TEX_CHECKER_NORMAL, TEX_IMAGE_SPECTRUM = 0, 1, 2, 3
 # ray queries on device memory (slrhip_intersect_rays / slrhip_test_visibility): one [n, 8] float32 row per slrhip_ray, one [n, 4]
 # row per slrhip_hit (column 0 holds the triangle index's bits)
@@ -250,6 +251,7 @@ def noise_metric(summary, metric=NOISE_RMSE):
 
 FLAG_TIME_KERNELS, FLAG_COUNT_TRAVERSAL, FLAG_BVH_DEVICE_BUILD, FLAG_TEST_DEVICE_ERROR, FLAG_BVH_SPATIAL_SPLITS, FLAG_TAIL_KERNEL = 1, 2, 4, 16, 64, 128
 FLAG_NO_PRIMARY_PASS = 256      # the primary pass (camera rays traced before a window's iterations) is on by default; this turns it off
+FLAG_DYNAMIC_GEOMETRY = 512     # keep the vertex and index arrays on the device, so that Context.set_vertices can move vertices without an upload
 MAX_STRIPES = 64
 KERNEL_NAMES = ("trace", "shade", "tail")
 

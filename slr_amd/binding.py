@@ -26,6 +26,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_render_motion", "slrhip_resolve_motion", "slrhip_read_motion", "slrhip_motion_camera", "slrhip_motion_sample", "slrhip_reproject",
            "slrhip_debug_motion_check", "slrhip_debug_reproject_check",
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
+           "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -156,6 +157,14 @@ def load_library():
     for name, argtypes in (("slrhip_debug_tree", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
                            ("slrhip_debug_host_tree", [C.POINTER(abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
                            ("slrhip_debug_quantize_nodes", [C.c_void_p, C.c_uint32, C.c_void_p])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before vertices could move lacks these four)
+    for name, argtypes in (("slrhip_set_vertices", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_geometry_status", [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+                           ("slrhip_debug_geometry_update_check", [C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                                   C.c_uint32]),
+                           ("slrhip_debug_geometry", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
@@ -357,6 +366,63 @@ class Context:
         bits = C.c_uint32(0)
         _check(self.lib, self.lib.slrhip_instances_status(self.handle, C.byref(bits), self._stream_handle(stream)), "slrhip_instances_status")
         return bits.value
+
+    # ---- moving vertices without a scene upload (slrhip_set_vertices; contexts created with abi.FLAG_DYNAMIC_GEOMETRY) ----
+    def set_vertices_into(self, device_ptr, first, count, stream=None):
+        """slrhip_set_vertices over a DEVICE pointer (an integer address): `count` 44-byte slrhip_vertex records, 4-byte aligned, read in
+        order on `stream`; returns at once."""
+        _check(self.lib, self.lib.slrhip_set_vertices(self.handle, device_ptr, first, count, self._stream_handle(stream)), "slrhip_set_vertices")
+
+    def set_vertices(self, vertices, first=0, count=None, stream=None):
+        """New records for the vertices [first, first + n) of the uploaded flat scene (slrhip_set_vertices): position, normal, tangent
+        and texcoord all take effect, and every record and box that depends on them is rebuilt on the device; the tree keeps its shape
+        and nothing accumulated is reset.  `vertices`: a DEVICE address (an integer; `count` records), n records of abi.vertex_dtype, or a
+        contiguous [n, 11] float32 numpy array or torch CUDA tensor.  A tensor is passed without a copy and read in order on `stream`
+        (default: torch.cuda.current_stream()); a numpy array is copied to the device first, and that call synchronises.  A record with a
+        non-finite float leaves its vertex as it was: see geometry_status."""
+        if vertices is None or isinstance(vertices, int):
+            return self.set_vertices_into(vertices, first, 0 if count is None else count, stream)
+        if isinstance(vertices, np.ndarray):
+            a = np.ascontiguousarray(vertices)
+            a = a.view(np.float32) if a.dtype == abi.vertex_dtype else np.ascontiguousarray(a, np.float32)
+            a = a.reshape(-1, 11)
+            with DeviceBlocks() as dev:
+                self.set_vertices_into(dev.put(a) if len(a) else None, first, len(a), stream)
+                self.synchronize()                     # the staging block is freed on the way out
+            return
+        import torch
+        if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2
+                and vertices.shape[1] == 11 and vertices.is_contiguous()):
+            raise ValueError("vertices: a contiguous [n, 11] float32 CUDA tensor (or a numpy array, or a device address) expected")
+        if vertices.device.index != self.device:
+            raise SlrHipError("set_vertices: the tensor is on device %r, the context on device %d" % (vertices.device.index, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.set_vertices_into(vertices.data_ptr(), first, vertices.shape[0], s)
+
+    def geometry_status(self, stream=None):
+        """The abi.GEOMETRY_* bits of the set_vertices calls since the last read, then cleared (slrhip_geometry_status); waits for
+        `stream` (a torch stream, a raw handle; default: the null stream)."""
+        bits = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_geometry_status(self.handle, C.byref(bits), self._stream_handle(stream)), "slrhip_geometry_status")
+        return bits.value
+
+    def debug_geometry(self):
+        """Diagnostic (slrhip_debug_geometry): what set_vertices keeps and rewrites beyond the tree, as a dict — levels (first node of
+        each level, then the number of nodes), num_nodes, group_nodes (the widest level the refit takes in one workgroup), staged
+        (the shade tables hold a second copy of the lights), launches (of the last set_vertices call), vertices (abi.vertex_dtype),
+        light_tris [n, 36] uint32, light_tris_staged (the same, or None), tri_uv [2 t, 4] float32, alpha [2 a, 4] uint32.
+        Synchronises."""
+        def read(what, words, dtype=np.uint32):
+            out = np.zeros(words, dtype)
+            _check(self.lib, self.lib.slrhip_debug_geometry(self.handle, what, out.ctypes.data, out.nbytes // 4), "slrhip_debug_geometry")
+            return out
+        head = read(0, 32)
+        levels, nodes, nv, nt, nl, staged, group = (int(v) for v in head[:7])
+        uv4, alpha, launches = (int(v) for v in head[8 + levels:11 + levels])
+        return dict(levels=head[7:8 + levels].copy(), num_nodes=nodes, num_triangles=nt, group_nodes=group, staged=bool(staged), launches=launches,
+                    vertices=read(1, nv, abi.vertex_dtype), light_tris=read(2, nl * 36).reshape(nl, 36),
+                    light_tris_staged=read(3, nl * 36).reshape(nl, 36) if staged else None,
+                    tri_uv=read(4, uv4 * 4, np.float32).reshape(uv4, 4), alpha=read(5, alpha * 8).reshape(alpha * 2, 4))
 
     def set_camera(self, camera):
         """Replaces the camera of the uploaded scene (slrhip_set_camera; an abi.Camera): later launches see it, nothing is reset."""
@@ -1001,6 +1067,14 @@ def quantize_nodes(nodes):
     out = np.zeros(len(a), abi.qnodeq_dtype)
     _check(lib, lib.slrhip_debug_quantize_nodes(a.ctypes.data, len(a), out.ctypes.data), "slrhip_debug_quantize_nodes")
     return out
+
+
+def geometry_update_check(have_scene, dynamic, tree_builder, num_instances, num_vertices, device_src, first, count):
+    """Diagnostic (slrhip_debug_geometry_update_check): the argument checks of Context.set_vertices without a context; raises SlrHipError
+    with the code and the message the call would give.  No GPU."""
+    lib = load_library()
+    _check(lib, lib.slrhip_debug_geometry_update_check(int(have_scene), int(dynamic), tree_builder, num_instances, num_vertices, device_src, first, count),
+           "slrhip_debug_geometry_update_check")
 
 
 def instance_world_box(mesh_lo, mesh_hi, local_to_world):

@@ -9,6 +9,7 @@
 // first K nodes are the top of the tree (the part the traversal kernel stages in LDS).
 #include "bvh.h"
 #include "pt_instance.h"
+#include "pt_triangle.h"
 
 #include <sched.h>
 #include <stdio.h>
@@ -423,11 +424,7 @@ int buildQBVHPrims(const slrhip_vertex* verts, const slrhip_triangle* tris, cons
                     const float* p2 = verts[tris[t].v[2]].position;
                     LeafTri lt;
                     std::memset(&lt, 0, sizeof(lt));
-                    for (int a = 0; a < 3; ++a) {
-                        lt.v0[a] = p0[a];
-                        lt.e1[a] = p1[a] - p0[a];      // edge01, TriangleMesh.cpp:136
-                        lt.e2[a] = p2[a] - p0[a];      // edge02, TriangleMesh.cpp:137
-                    }
+                    leafTriEdges(p0, p1, p2, lt);      // pt_triangle.h
                     lt.tri = t;
                     lt.alpha = kNoAlpha;               // set by slrhip_upload_scene for triangles whose material has an alpha texture
                     out->leafTris[first + k] = lt;

@@ -65,6 +65,7 @@ struct DeviceGeometry {
     LeafTri* leafTris = nullptr;
     ShadeTri* shadeTris = nullptr;
     uint32_t numNodes = 0, numLeafTris = 0, depth = 0;
+    std::vector<uint32_t> levelFirst; // first node of each level (QBVH::levelFirst of the host build)
     double secondsUpload = 0, secondsSort = 0, secondsHierarchy = 0, secondsCollapse = 0, secondsRecords = 0;
 };
 int buildGeometryDevice(const slrhip_vertex* verts, uint32_t numVerts, const slrhip_triangle* tris, uint32_t numTris, const uint32_t* lightTris,

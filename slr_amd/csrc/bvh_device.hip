@@ -35,6 +35,8 @@
 #include <vector>
 
 #include "bvh.h"
+#include "pt_quantize.h"
+#include "pt_triangle.h"
 
 namespace slrhip {
 
@@ -228,9 +230,6 @@ __global__ void k_collapse_count(BinTree t, int n, const uint32_t* __restrict__ 
     innerCount[i] = inner;
 }
 
-// what the traversal kernel computes for a quantized plane
-__device__ __forceinline__ float dequantDev(uint32_t q, float scale, float origin) { return __builtin_fmaf((float)q, scale, origin); }
-
 // pass 2: write the level's QNode (and QNodeQ) records; inner children are numbered nextBase + scan[i] + (rank among the inner
 // children of this node), and listed in the next frontier in that order
 __global__ void k_collapse_emit(BinTree t, int n, uint32_t numFrontier, uint32_t levelBase, uint32_t nextBase, const Kids* __restrict__ kidsIn,
@@ -266,45 +265,7 @@ __global__ void k_collapse_emit(BinTree t, int n, uint32_t numFrontier, uint32_t
     }
     nodes[levelBase + i] = qn;
     if (!nodesQ) return;
-    // quantizeNodes of bvh.cpp, with the device's own fma as the check (rounded outwards: every dequantized box contains the float box)
-    QNodeQ d;
-    const float* mins[3] = {qn.minx, qn.miny, qn.minz};
-    const float* maxs[3] = {qn.maxx, qn.maxy, qn.maxz};
-    float org[3], scl[3];
-    uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-    for (int a = 0; a < 3; ++a) {
-        float bmin = INFINITY, bmax = -INFINITY;
-        for (int c = 0; c < 4; ++c)
-            if (qn.child[c] != kInvalidChild) { bmin = fminf(bmin, mins[a][c]); bmax = fmaxf(bmax, maxs[a][c]); }
-        if (!(bmin <= bmax)) { bmin = 0.0f; bmax = 0.0f; }
-        org[a] = bmin;
-        // quantScale of bvh.cpp, statement for statement: a box with bmax > bmin never gets scale 0 (a subnormal extent whose division
-        // rounds to 0 starts at the smallest subnormal), and the same bound on the loop
-        float sc = (bmax - bmin) / 255.0f;
-        if (sc == 0.0f && bmax > bmin) sc = __uint_as_float(1u);
-        for (int guard = 0; guard < 64 && sc > 0.0f && dequantDev(255, sc, bmin) < bmax; ++guard) sc = __uint_as_float(__float_as_uint(sc) + 1u);      // nextafter upwards (sc > 0)
-        scl[a] = sc;
-        for (int c = 0; c < 4; ++c) {
-            uint32_t l = 255, h = 0;                       // empty slot: inverted, never entered
-            if (qn.child[c] != kInvalidChild) {
-                if (sc > 0.0f) {
-                    l = (uint32_t)fminf(255.0f, fmaxf(0.0f, floorf((mins[a][c] - bmin) / sc)));
-                    h = (uint32_t)fminf(255.0f, fmaxf(0.0f, ceilf((maxs[a][c] - bmin) / sc)));
-                    while (l > 0 && dequantDev(l, sc, bmin) > mins[a][c]) --l;
-                    while (h < 255 && dequantDev(h, sc, bmin) < maxs[a][c]) ++h;
-                }
-                else { l = 0; h = 0; }                    // flat box on this axis: origin is the plane, exactly
-            }
-            qlo[a] |= l << (8 * c);
-            qhi[a] |= h << (8 * c);
-        }
-    }
-    d.ox = org[0]; d.oy = org[1]; d.oz = org[2];
-    d.sx = scl[0]; d.sy = scl[1]; d.sz = scl[2];
-    d.qlox = qlo[0]; d.qloy = qlo[1]; d.qloz = qlo[2];
-    d.qhix = qhi[0]; d.qhiy = qhi[1]; d.qhiz = qhi[2];
-    for (int c = 0; c < 4; ++c) d.child[c] = qn.child[c];
-    nodesQ[levelBase + i] = d;
+    nodesQ[levelBase + i] = quantizeNode(qn);      // pt_quantize.h
 }
 
 __global__ void k_leaf_tris(const slrhip_vertex* __restrict__ verts, const slrhip_triangle* __restrict__ tris, const uint32_t* __restrict__ vals, uint32_t n,
@@ -314,38 +275,21 @@ __global__ void k_leaf_tris(const slrhip_vertex* __restrict__ verts, const slrhi
     const uint32_t ti = vals[k];
     const slrhip_triangle t = tris[ti];
     LeafTri lt;
-    for (int a = 0; a < 3; ++a) {
-        const float p0 = verts[t.v[0]].position[a];
-        lt.v0[a] = p0;
-        lt.e1[a] = verts[t.v[1]].position[a] - p0;      // edge01, TriangleMesh.cpp:136
-        lt.e2[a] = verts[t.v[2]].position[a] - p0;      // edge02, TriangleMesh.cpp:137
-    }
+    leafTriEdges(verts[t.v[0]].position, verts[t.v[1]].position, verts[t.v[2]].position, lt);      // pt_triangle.h
     lt.tri = ti;
     lt.alpha = kNoAlpha;
     lt.pad1 = 0u;
     out[k] = lt;
 }
 
-// the per-triangle loop of slrhip_upload_scene, operation for operation (same float results)
+// the per-triangle loop of slrhip_upload_scene: both call pt_triangle.h's function (same float results)
 __global__ void k_shade_tris(const slrhip_vertex* __restrict__ verts, const slrhip_triangle* __restrict__ tris, uint32_t n, ShadeTri* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const slrhip_triangle t = tris[i];
     const slrhip_vertex v0 = verts[t.v[0]], v1 = verts[t.v[1]], v2 = verts[t.v[2]];
     ShadeTri s;
-    float e1[3], e2[3];
-    for (int a = 0; a < 3; ++a) {
-        s.n0[a] = v0.normal[a]; s.n1[a] = v1.normal[a]; s.n2[a] = v2.normal[a];
-        s.t0[a] = v0.tangent[a]; s.t1[a] = v1.tangent[a]; s.t2[a] = v2.tangent[a];
-        e1[a] = v1.position[a] - v0.position[a];
-        e2[a] = v2.position[a] - v0.position[a];
-    }
-    // normalize(cross(edge01, edge02)) TriangleMesh.cpp:171
-    const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-    const float len = sqrtf(cx * cx + cy * cy + cz * cz);
-    const float r = 1.0f / len;
-    s.gnx = cx * r; s.gny = cy * r; s.gnz = cz * r;
-    s.areaPDF = 1.0f / (0.5f * len);                    // 1 / Triangle::area() :217-222
+    shadeTriGeometry(v0, v1, v2, s);                    // pt_triangle.h
     s.material = t.material;
     s.light = -1;
     out[i] = s;
@@ -445,8 +389,10 @@ int buildGeometryDevice(const slrhip_vertex* hVerts, uint32_t numVerts, const sl
     uint32_t numFrontier = 1, levelBase = 0, depth = 0;
     uint32_t* cur = frontierA.p;
     uint32_t* next = frontierB.p;
+    out->levelFirst.clear();
     while (numFrontier > 0) {
         ++depth;
+        out->levelFirst.push_back(levelBase);          // breadth-first: a level is the run of nodes from its base (slrhip_set_vertices refits by level)
         if (depth > 64) return failFree("device build: tree deeper than 64 levels");
         if ((size_t)levelBase + numFrontier > maxNodes) return failFree("device build: node budget exceeded");
         const uint32_t g = (numFrontier + B - 1) / B;

@@ -1,0 +1,213 @@
+// pt_geometry.hip — device code of slrhip_set_vertices: new vertices for the uploaded flat scene, and everything that depends on
+// vertices rebuilt in place from the kept vertex array — the tree keeps its shape and gets exact boxes.  gfx950, wave64.  Launches
+// in stream order (a launch reads what earlier launches stored; nothing is handed between workgroups inside one):
+//
+//   k_vertices_store      one lane per caller's record: eleven 4-byte loads (the record is 44 bytes, 4-byte aligned), the finite check,
+//                         eleven stores into the kept array.  A record with a non-finite float leaves its vertex as it was and sets
+//                         SLRHIP_GEOMETRY_BAD_VERTEX with one atomic OR on a word of its own.
+//   k_geometry_leaves     one lane per LeafTri record: its `tri` word, the index triple, three positions; v0 / e1 / e2 (pt_triangle.h:
+//                         the upload's arithmetic) with the record's w words kept; the triangle's exact box (min / max over the
+//                         positions) into the box scratch; the texture coordinates of its alpha record where it has one.
+//   k_geometry_triangles  one lane per scene triangle: ShadeTri (`material` and `light` kept) and, with textures, triUV.
+//   k_geometry_lights     one lane per light: LightTri::tri names the triangle; both copies (lightTris and the shade tables' segment).
+//   k_geometry_refit      the child boxes of every node, bottom-up, one lane per (node, child), pt_refit.h's rule: a packet takes the
+//                         union of its triangles' scratch boxes, an inner child the union of the valid child boxes of the node it
+//                         names, an empty slot keeps its bytes.  A level wider than kRefitGroupNodes is a launch of its own; a run of
+//                         consecutive narrower levels is ONE workgroup with a barrier between levels (k_geometry_refit_levels).
+//   k_geometry_quantize   one lane per node: QNodeQ from the refitted float node (pt_quantize.h), when the quantized nodes are in use.
+//
+// No atomics but the status bit, no parent pointers, no flags between workgroups: the order comes from the launches.
+#include <hip/hip_runtime.h>
+
+#include "pt_geometry.h"
+#include "pt_quantize.h"
+#include "pt_triangle.h"
+
+namespace slrhip {
+
+namespace {
+
+const uint32_t kVertexFloats = 11;
+static_assert(sizeof(slrhip_vertex) == kVertexFloats * sizeof(float), "slrhip_vertex is eleven floats");
+
+__global__ __launch_bounds__(256) void k_vertices_store(GeometryUpdate u) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= u.count) return;                                                 // count records at src; first + count <= numVertices
+    const float* src = u.src + (size_t)t * kVertexFloats;
+    float v[kVertexFloats];
+    bool finite = true;
+#pragma unroll
+    for (uint32_t k = 0; k < kVertexFloats; ++k) {
+        v[k] = src[k];
+        finite = finite && fabsf(v[k]) <= 3.402823466e+38f;
+    }
+    if (!finite) {
+        atomicOr(u.status, (uint32_t)SLRHIP_GEOMETRY_BAD_VERTEX);
+        return;
+    }
+    float* dst = u.vertices + (size_t)(u.first + t) * kVertexFloats;
+#pragma unroll
+    for (uint32_t k = 0; k < kVertexFloats; ++k) dst[k] = v[k];
+}
+
+__device__ __forceinline__ slrhip_vertex loadVertex(const float* vertices, uint32_t i) {
+    const float* p = vertices + (size_t)i * kVertexFloats;
+    slrhip_vertex v;
+    v.position[0] = p[0]; v.position[1] = p[1]; v.position[2] = p[2];
+    v.normal[0] = p[3]; v.normal[1] = p[4]; v.normal[2] = p[5];
+    v.tangent[0] = p[6]; v.tangent[1] = p[7]; v.tangent[2] = p[8];
+    v.texcoord[0] = p[9]; v.texcoord[1] = p[10];
+    return v;
+}
+
+// the index triple of triangle `tri`, or false for an index outside the kept arrays (never: the upload checked them)
+__device__ __forceinline__ bool loadTriangle(const GeometryUpdate& u, uint32_t tri, uint32_t* v) {
+    if (tri >= u.numTriangles) return false;
+    const uint4 t = *reinterpret_cast<const uint4*>(u.triangles + tri);      // v[3], material
+    v[0] = t.x; v[1] = t.y; v[2] = t.z;
+    return t.x < u.numVertices && t.y < u.numVertices && t.z < u.numVertices;
+}
+
+__global__ __launch_bounds__(256) void k_geometry_leaves(GeometryUpdate u) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= u.numLeafTris) return;
+    float4* rec = u.leafTris + (size_t)k * 3u;
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    uint32_t vi[3];
+    if (!loadTriangle(u, __float_as_uint(r0.w), vi)) return;
+    float p[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float* q = u.vertices + (size_t)vi[j] * kVertexFloats;
+        p[j][0] = q[0]; p[j][1] = q[1]; p[j][2] = q[2];
+    }
+    LeafTri lt;
+    leafTriEdges(p[0], p[1], p[2], lt);
+    rec[0] = make_float4(lt.v0[0], lt.v0[1], lt.v0[2], r0.w);                 // tri
+    rec[1] = make_float4(lt.e1[0], lt.e1[1], lt.e1[2], r1.w);                 // alpha
+    rec[2] = make_float4(lt.e2[0], lt.e2[1], lt.e2[2], r2.w);
+    float lo[3], hi[3];
+    triangleBox(p[0], p[1], p[2], lo, hi);
+    u.leafBoxes[2u * (size_t)k] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+    u.leafBoxes[2u * (size_t)k + 1u] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    const uint32_t alpha = __float_as_uint(r1.w);
+    if (alpha == kNoAlpha || alpha >= u.numAlphaRecords) return;
+    float uv[6];
+    triangleTexcoords(loadVertex(u.vertices, vi[0]), loadVertex(u.vertices, vi[1]), loadVertex(u.vertices, vi[2]), uv);
+    float4* a = u.alphaTris + 2u * (size_t)alpha;
+    const float4 tail = a[1];                                                 // .z: the texture's index, .w: 0
+    a[0] = make_float4(uv[0], uv[1], uv[2], uv[3]);
+    a[1] = make_float4(uv[4], uv[5], tail.z, tail.w);
+}
+
+__global__ __launch_bounds__(256) void k_geometry_triangles(GeometryUpdate u) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= u.numTriangles) return;
+    uint32_t vi[3];
+    if (!loadTriangle(u, i, vi)) return;
+    const slrhip_vertex v0 = loadVertex(u.vertices, vi[0]), v1 = loadVertex(u.vertices, vi[1]), v2 = loadVertex(u.vertices, vi[2]);
+    float4* rec = u.shadeTris + (size_t)i * 6u;
+    const float material = rec[0].w, light = rec[1].w;                        // kept, as bits
+    ShadeTri s;
+    shadeTriGeometry(v0, v1, v2, s);
+    rec[0] = make_float4(s.n0[0], s.n0[1], s.n0[2], material);
+    rec[1] = make_float4(s.n1[0], s.n1[1], s.n1[2], light);
+    rec[2] = make_float4(s.n2[0], s.n2[1], s.n2[2], s.areaPDF);
+    rec[3] = make_float4(s.t0[0], s.t0[1], s.t0[2], s.gnx);
+    rec[4] = make_float4(s.t1[0], s.t1[1], s.t1[2], s.gny);
+    rec[5] = make_float4(s.t2[0], s.t2[1], s.t2[2], s.gnz);
+    if (!u.triUV) return;
+    float uv[6];
+    triangleTexcoords(v0, v1, v2, uv);
+    u.triUV[2u * (size_t)i] = make_float4(uv[0], uv[1], uv[2], uv[3]);
+    u.triUV[2u * (size_t)i + 1u] = make_float4(uv[4], uv[5], 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void k_geometry_lights(GeometryUpdate u) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= u.numLights) return;
+    float4* rec = u.lightTris + (size_t)i * 9u;
+    const float tri = rec[0].w, material = rec[1].w;                          // kept, as bits
+    uint32_t vi[3];
+    if (!loadTriangle(u, __float_as_uint(tri), vi)) return;
+    const slrhip_vertex v0 = loadVertex(u.vertices, vi[0]), v1 = loadVertex(u.vertices, vi[1]), v2 = loadVertex(u.vertices, vi[2]);
+    ShadeTri s;
+    shadeTriGeometry(v0, v1, v2, s);
+    LightTri l;
+    lightTriGeometry(v0, v1, v2, s, l);
+    float4 out[9];
+    out[0] = make_float4(l.p0[0], l.p0[1], l.p0[2], tri);
+    out[1] = make_float4(l.p1[0], l.p1[1], l.p1[2], material);
+    out[2] = make_float4(l.p2[0], l.p2[1], l.p2[2], l.areaPDF);
+    out[3] = make_float4(l.n0[0], l.n0[1], l.n0[2], l.gnx);
+    out[4] = make_float4(l.n1[0], l.n1[1], l.n1[2], l.gny);
+    out[5] = make_float4(l.n2[0], l.n2[1], l.n2[2], l.gnz);
+    out[6] = make_float4(l.t0[0], l.t0[1], l.t0[2], 0.0f);
+    out[7] = make_float4(l.t1[0], l.t1[1], l.t1[2], 0.0f);
+    out[8] = make_float4(l.t2[0], l.t2[1], l.t2[2], 0.0f);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) rec[q] = out[q];
+    if (!u.stagedLights) return;
+    float4* staged = u.stagedLights + (size_t)i * 9u;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) staged[q] = out[q];
+}
+
+// One level of more than kRefitGroupNodes nodes: nodes [first, first + count), four lanes each.
+__global__ __launch_bounds__(kRefitBlock) void k_geometry_refit(float4* nodes, const float4* leafBoxes, uint32_t first, uint32_t count, uint32_t numNodes,
+                                                                uint32_t numLeafTris) {
+    const uint32_t t = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (t >= 4u * count) return;
+    refitChild(nodes, nullptr, leafBoxes, first + (t >> 2), t & 3u, numNodes, 0u, numLeafTris);
+}
+
+// Levels levelHi, levelHi - 1, .. levelLo, each of at most kRefitGroupNodes nodes: one workgroup, a barrier between levels.
+__global__ __launch_bounds__(kRefitBlock) void k_geometry_refit_levels(GeometryUpdate u, uint32_t levelHi, uint32_t levelLo) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t level = levelHi + 1u; level-- > levelLo;) {                 // uniform over the workgroup: every lane reaches every barrier
+        const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
+        if (t < 4u * count) refitChild(u.nodes, nullptr, u.leafBoxes, first + (t >> 2), t & 3u, u.numNodes, 0u, u.numLeafTris);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_geometry_quantize(const QNode* __restrict__ nodes, QNodeQ* __restrict__ nodesQ, uint32_t numNodes) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= numNodes) return;
+    const QNode qn = nodes[i];
+    nodesQ[i] = quantizeNode(qn);
+}
+
+inline dim3 gridOf(uint32_t lanes, uint32_t block) { return dim3((lanes + block - 1u) / block); }
+
+} // namespace
+
+uint32_t launchGeometryUpdate(const GeometryUpdate& u, hipStream_t stream) {
+    uint32_t launches = 0;
+    hipLaunchKernelGGL(k_vertices_store, gridOf(u.count, 256u), dim3(256), 0, stream, u); ++launches;
+    hipLaunchKernelGGL(k_geometry_leaves, gridOf(u.numLeafTris, 256u), dim3(256), 0, stream, u); ++launches;
+    hipLaunchKernelGGL(k_geometry_triangles, gridOf(u.numTriangles, 256u), dim3(256), 0, stream, u); ++launches;
+    if (u.numLights) { hipLaunchKernelGGL(k_geometry_lights, gridOf(u.numLights, 256u), dim3(256), 0, stream, u); ++launches; }
+    // from the deepest level to the root; consecutive levels that fit one workgroup share a launch (as launchInstanceUpdate does)
+    for (uint32_t level = u.numLevels; level-- > 0u;) {
+        const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
+        ++launches;
+        if (count > kRefitGroupNodes) {
+            hipLaunchKernelGGL(k_geometry_refit, gridOf(4u * count, kRefitBlock), dim3(kRefitBlock), 0, stream, u.nodes, u.leafBoxes, first, count, u.numNodes,
+                               u.numLeafTris);
+            continue;
+        }
+        uint32_t lo = level;
+        while (lo > 0u && u.levelFirst[lo] - u.levelFirst[lo - 1u] <= kRefitGroupNodes) --lo;
+        hipLaunchKernelGGL(k_geometry_refit_levels, dim3(1), dim3(kRefitBlock), 0, stream, u, level, lo);
+        level = lo;
+    }
+    if (u.nodesQ) {
+        hipLaunchKernelGGL(k_geometry_quantize, gridOf(u.numNodes, 256u), dim3(256), 0, stream, reinterpret_cast<const QNode*>(u.nodes),
+                           reinterpret_cast<QNodeQ*>(u.nodesQ), u.numNodes);
+        ++launches;
+    }
+    return launches;
+}
+
+} // namespace slrhip

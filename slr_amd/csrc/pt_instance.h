@@ -5,6 +5,8 @@
 #pragma once
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
+
+#include "pt_refit.h"            // kRefitGroupNodes, kMaxTreeLevels: the refit's child rule, shared with slrhip_set_vertices
 #endif
 
 #include <cmath>
@@ -51,8 +53,7 @@ SLR_HOST_DEV void instanceWorldBox(const float* meshLo, const float* meshHi, con
 #ifdef __HIP__
 // slrhip_set_instance_transforms' device work (pt_instances.hip): place the records, then refit the top-level tree's child boxes
 // level by level from the deepest level to the root, all on `stream`.  The range has passed instanceUpdateRefusal (render_plan.h).
-static const uint32_t kMaxTopLevels = 21;                  // 3 x depth + 1 <= 64 (checkTreeLimits)
-static const uint32_t kRefitGroupNodes = 64;               // a level of at most this many nodes fits one workgroup of k_top_refit (4 lanes per node)
+static const uint32_t kMaxTopLevels = kMaxTreeLevels;
 struct InstanceUpdate {
     const float4* src;                                     // the caller's records, 8 x float4 each: local_to_world, world_to_local
     uint32_t first, count;                                 // instances [first, first + count)

@@ -6,7 +6,8 @@
 //                     SLRHIP_INSTANCE_BAD_TRANSFORM with one atomic OR on a word of its own.  A good record goes into DevInstance
 //                     (eight 16-byte stores; the ninth float4 — root, range, mesh — stays) and its world box (pt_instance.h,
 //                     instanceWorldBox: the host's arithmetic, same bits) into the instance boxes, two 16-byte stores.
-//   k_top_refit       the child boxes of the top-level nodes, bottom-up.  One lane per (node, child): an instance child takes its
+//   k_top_refit       the child boxes of the top-level nodes, bottom-up (the child rule is pt_refit.h's, shared with
+//                     slrhip_set_vertices).  One lane per (node, child): an instance child takes its
 //                     instance's world box, an inner child the exact min / max union of the valid child boxes of the node it names
 //                     (six 16-byte loads of that node's planes + one of its references, a horizontal min / max over the valid
 //                     children), a triangle packet and an empty slot keep their bytes.  Six 4-byte stores per lane; the four lanes
@@ -26,8 +27,6 @@
 namespace slrhip {
 
 namespace {
-
-const uint32_t kRefitBlock = 4u * kRefitGroupNodes;      // 256 lanes: four per node
 
 __global__ __launch_bounds__(256) void k_instance_place(InstanceUpdate u) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -56,59 +55,12 @@ __global__ __launch_bounds__(256) void k_instance_place(InstanceUpdate u) {
     u.instBoxes[2u * (size_t)k + 1u] = make_float4(hi[0], hi[1], hi[2], 0.0f);
 }
 
-__device__ __forceinline__ float pick(const float4& v, uint32_t c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-__device__ __forceinline__ uint32_t pick(const uint4& v, uint32_t c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
-// min / max of a plane over the children whose reference is valid; an empty slot's bytes take no part
-__device__ __forceinline__ float unionMin(const float4& v, const uint4& ref) {
-    float r = INFINITY;
-    if (ref.x != kInvalidChild) r = fminf(r, v.x);
-    if (ref.y != kInvalidChild) r = fminf(r, v.y);
-    if (ref.z != kInvalidChild) r = fminf(r, v.z);
-    if (ref.w != kInvalidChild) r = fminf(r, v.w);
-    return r;
-}
-__device__ __forceinline__ float unionMax(const float4& v, const uint4& ref) {
-    float r = -INFINITY;
-    if (ref.x != kInvalidChild) r = fmaxf(r, v.x);
-    if (ref.y != kInvalidChild) r = fmaxf(r, v.y);
-    if (ref.z != kInvalidChild) r = fmaxf(r, v.z);
-    if (ref.w != kInvalidChild) r = fmaxf(r, v.w);
-    return r;
-}
-
-// Child c of top-level node `node`.  nodes: not restrict, not const — a level reads what the level below it stored.
-__device__ __forceinline__ void refitChild(float4* nodes, const float4* instBoxes, uint32_t node, uint32_t c, uint32_t topNodes, uint32_t numInstances) {
-    float4* self = nodes + (size_t)node * 8u;
-    const uint32_t ref = pick(*reinterpret_cast<const uint4*>(self + 6), c);
-    if (ref == kInvalidChild) return;
-    float lo[3], hi[3];
-    if (ref & kLeafFlag) {
-        if (((ref >> kLeafCountShift) & 0xFu) != 0u) return;                   // a triangle packet keeps its box
-        const uint32_t k = ref & kLeafIndexMask;
-        if (k >= numInstances) return;                                        // (never: the upload wrote the reference)
-        const float4 a = instBoxes[2u * (size_t)k], b = instBoxes[2u * (size_t)k + 1u];
-        lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; hi[0] = b.x; hi[1] = b.y; hi[2] = b.z;
-    }
-    else {
-        if (ref >= topNodes) return;                                          // (never: a top-level node names top-level nodes)
-        const float4* kid = nodes + (size_t)ref * 8u;
-        const float4 p0 = kid[0], p1 = kid[1], p2 = kid[2], p3 = kid[3], p4 = kid[4], p5 = kid[5];
-        const uint4 refs = *reinterpret_cast<const uint4*>(kid + 6);
-        lo[0] = unionMin(p0, refs); lo[1] = unionMin(p1, refs); lo[2] = unionMin(p2, refs);
-        hi[0] = unionMax(p3, refs); hi[1] = unionMax(p4, refs); hi[2] = unionMax(p5, refs);
-    }
-    float* planes = reinterpret_cast<float*>(self);                            // minx[4] miny[4] minz[4] maxx[4] maxy[4] maxz[4]
-    planes[c] = lo[0]; planes[4u + c] = lo[1]; planes[8u + c] = lo[2];
-    planes[12u + c] = hi[0]; planes[16u + c] = hi[1]; planes[20u + c] = hi[2];
-}
-
 // One level of more than kRefitGroupNodes nodes: nodes [first, first + count), four lanes each.
 __global__ __launch_bounds__(kRefitBlock) void k_top_refit(float4* nodes, const float4* instBoxes, uint32_t first, uint32_t count, uint32_t topNodes,
                                                            uint32_t numInstances) {
     const uint32_t t = blockIdx.x * kRefitBlock + threadIdx.x;
     if (t >= 4u * count) return;
-    refitChild(nodes, instBoxes, first + (t >> 2), t & 3u, topNodes, numInstances);
+    refitChild(nodes, instBoxes, nullptr, first + (t >> 2), t & 3u, topNodes, numInstances, 0u);
 }
 
 // Levels levelHi, levelHi - 1, .. levelLo, each of at most kRefitGroupNodes nodes: one workgroup, a barrier between levels.
@@ -116,7 +68,7 @@ __global__ __launch_bounds__(kRefitBlock) void k_top_refit_levels(InstanceUpdate
     const uint32_t t = threadIdx.x;
     for (uint32_t level = levelHi + 1u; level-- > levelLo;) {                 // uniform over the workgroup: every lane reaches every barrier
         const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
-        if (t < 4u * count) refitChild(u.nodes, u.instBoxes, first + (t >> 2), t & 3u, u.topNodes, u.numInstances);
+        if (t < 4u * count) refitChild(u.nodes, u.instBoxes, nullptr, first + (t >> 2), t & 3u, u.topNodes, u.numInstances, 0u);
         __syncthreads();
     }
 }

@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "pt_envmap.h"
+#include "pt_triangle.h"
 
 namespace slrhip {
 namespace {
@@ -371,32 +372,15 @@ int prepareTriangles(const slrhip_scene_desc& d, const MaterialFacts& f, Prepare
         const slrhip_vertex &v0 = d.vertices[t.v[0]], &v1 = d.vertices[t.v[1]], &v2 = d.vertices[t.v[2]];
         ShadeTri s;
         std::memset(&s, 0, sizeof(s));
-        float e1[3], e2[3];
-        for (int a = 0; a < 3; ++a) {
-            s.n0[a] = v0.normal[a]; s.n1[a] = v1.normal[a]; s.n2[a] = v2.normal[a];
-            s.t0[a] = v0.tangent[a]; s.t1[a] = v1.tangent[a]; s.t2[a] = v2.tangent[a];
-            e1[a] = v1.position[a] - v0.position[a];
-            e2[a] = v2.position[a] - v0.position[a];
-        }
-        // normalize(cross(edge01, edge02)) TriangleMesh.cpp:171 — same float ops as the reference, on the host
-        float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        float len = std::sqrt(cx * cx + cy * cy + cz * cz);
-        float r = 1.0f / len;
-        s.gnx = cx * r; s.gny = cy * r; s.gnz = cz * r;
-        s.areaPDF = 1.0f / (0.5f * len);                    // 1 / Triangle::area() :217-222
+        shadeTriGeometry(v0, v1, v2, s);                    // pt_triangle.h: the arithmetic k_shade_tris and slrhip_set_vertices share
         s.material = t.material;
         s.light = -1;
         if (emitting[t.material]) {
             s.light = (int32_t)p.lightTris.size();
             LightTri l;
             std::memset(&l, 0, sizeof(l));
-            for (int a = 0; a < 3; ++a) {
-                l.p0[a] = v0.position[a]; l.p1[a] = v1.position[a]; l.p2[a] = v2.position[a];
-                l.n0[a] = v0.normal[a]; l.n1[a] = v1.normal[a]; l.n2[a] = v2.normal[a];
-                l.t0[a] = v0.tangent[a]; l.t1[a] = v1.tangent[a]; l.t2[a] = v2.tangent[a];
-            }
-            l.tri = i; l.material = t.material; l.areaPDF = s.areaPDF;
-            l.gnx = s.gnx; l.gny = s.gny; l.gnz = s.gnz;
+            lightTriGeometry(v0, v1, v2, s, l);
+            l.tri = i; l.material = t.material;
             p.lightTris.push_back(l);
             p.lightTriangles.push_back(i);
             importances.push_back(1.0f);                    // SingleSurfaceObject::importance :69-71
@@ -417,9 +401,10 @@ int prepareTriangles(const slrhip_scene_desc& d, const MaterialFacts& f, Prepare
 
 // (u0, v0, u1, v1), (u2, v2, z, 0) of one triangle: the layout of DevScene::triUV and of the alpha records.
 void gatherTexcoords(const slrhip_scene_desc& d, const slrhip_triangle& t, float z, float4* out) {
-    const float* u0 = d.vertices[t.v[0]].texcoord; const float* u1 = d.vertices[t.v[1]].texcoord; const float* u2 = d.vertices[t.v[2]].texcoord;
-    out[0] = make_float4(u0[0], u0[1], u1[0], u1[1]);
-    out[1] = make_float4(u2[0], u2[1], z, 0.0f);
+    float uv[6];
+    triangleTexcoords(d.vertices[t.v[0]], d.vertices[t.v[1]], d.vertices[t.v[2]], uv);
+    out[0] = make_float4(uv[0], uv[1], uv[2], uv[3]);
+    out[1] = make_float4(uv[4], uv[5], z, 0.0f);
 }
 
 // Alpha textures (Triangle::m_alphaTex): one record per triangle that has one, named by its leaf entries; texture coordinates of

@@ -9,6 +9,7 @@
 
 #include <chrono>
 
+#include "pt_refit.h"
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
@@ -109,9 +110,10 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     uint32_t numNodes = (uint32_t)p.bvh.nodes.size(), depth = p.bvh.depth;
     uint64_t leafRefs = p.bvh.leafTris.size();
     bool quantized = p.quantized;
+    const std::vector<uint32_t>* levelFirst = &p.bvh.levelFirst;
+    DeviceGeometry g;
     if (p.build == TreeBuild::Device) {
         // the whole geometry on the GPU: tree, quantized nodes, leaf packets, shading records (bvh_device.hip)
-        DeviceGeometry g;
         std::string err;
         if (buildGeometryDevice(d.vertices, d.num_vertices, d.triangles, d.num_triangles, p.lightTriangles.data(), (uint32_t)p.lightTriangles.size(),
                                 p.wantQuantized, &g, &err) != 0)
@@ -127,6 +129,7 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
         quantized = g.nodesQ != nullptr && useQuantizedNodes(g.numNodes);
         if (quantized) ctx->nodesQ.adopt(g.nodesQ, g.numNodes); else (void)hipFree(g.nodesQ);
         numNodes = g.numNodes; depth = g.depth; leafRefs = g.numLeafTris;
+        levelFirst = &g.levelFirst;
     }
     else {
         HIP_TRY(ctx->nodes.upload(p.bvh.nodes));
@@ -166,6 +169,26 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     HIP_TRY(ctx->envTopPDF.upload(p.envTopPDF)); HIP_TRY(ctx->envTopCDF.upload(p.envTopCDF));
     HIP_TRY(ctx->envRowPDF.upload(p.envRowPDF)); HIP_TRY(ctx->envRowCDF.upload(p.envRowCDF));
     HIP_TRY(ctx->gridCells.upload(p.gridCells)); HIP_TRY(ctx->pointUV.upload(p.pointUV)); HIP_TRY(ctx->pointSpectrum.upload(p.pointSpectrum));
+    // what slrhip_set_vertices works from (SLRHIP_FLAG_DYNAMIC_GEOMETRY; flat scenes whose leaves hold whole triangles): allocated
+    // here, so that the call allocates nothing.  Without the flag, nothing.
+    ctx->geometryKept = false;
+    if ((ctx->config.flags & SLRHIP_FLAG_DYNAMIC_GEOMETRY) && p.build != TreeBuild::Instanced && treeBuilderOf(p) != 1u) {
+        if (levelFirst->empty() || levelFirst->size() > kMaxTreeLevels || levelFirst->size() != depth)
+            return fail(SLRHIP_ERR_HIP, "slrhip_upload_scene: the tree has no level table (internal error)");
+        HIP_TRY(ctx->geoVertices.alloc(d.num_vertices));
+        HIP_TRY(hipMemcpy(ctx->geoVertices.ptr, d.vertices, (size_t)d.num_vertices * sizeof(slrhip_vertex), hipMemcpyHostToDevice));
+        HIP_TRY(ctx->geoTriangles.alloc(d.num_triangles));
+        HIP_TRY(hipMemcpy(ctx->geoTriangles.ptr, d.triangles, (size_t)d.num_triangles * sizeof(slrhip_triangle), hipMemcpyHostToDevice));
+        HIP_TRY(ctx->geoLeafBoxes.alloc(2u * (size_t)leafRefs));
+        HIP_TRY(ctx->geometryStatus.alloc(1));
+        HIP_TRY(hipMemset(ctx->geometryStatus.ptr, 0, sizeof(uint32_t)));
+        ctx->geoLevelFirst = *levelFirst;
+        ctx->geoLevelFirst.push_back(numNodes);
+        ctx->geoNumVertices = d.num_vertices; ctx->geoNumTriangles = d.num_triangles; ctx->geoNumLights = (uint32_t)p.lightTris.size();
+        ctx->geoNumAlphaRecords = (uint32_t)(p.alphaTris.size() / 2u); ctx->geoHasTriUV = !p.triUV.empty();
+        ctx->geoLastLaunches = 0;
+        ctx->geometryKept = true;
+    }
     // the ray queries' error word: allocated here, so that a query call allocates nothing (and can be captured in a graph)
     HIP_TRY(ctx->queryError.alloc(1));
     HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));

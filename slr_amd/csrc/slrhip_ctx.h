@@ -1,5 +1,5 @@
 // slrhip_ctx.h — the context behind the C ABI of include/slrhip.h and what its translation units share: slrhip_api.hip,
-// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_diagnostics.hip.  Internal: not installed.
+// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_geometry.hip, slrhip_diagnostics.hip.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,6 +105,18 @@ struct slrhip_ctx {
     DevArray<float4> meshBoxes, instBoxes;
     DevArray<uint32_t> instanceStatus;
     std::vector<uint32_t> topLevelFirst;
+    // slrhip_set_vertices (contexts created with SLRHIP_FLAG_DYNAMIC_GEOMETRY; flat scenes without spatial splits): the scene's vertex
+    // and index arrays, one box (lo, hi) per LeafTri record as scratch, its status word, and the first node of each tree level, then the
+    // number of nodes.  geometryKept: the arrays belong to the scene in place (else they are empty or an earlier scene's, and unused).
+    DevArray<slrhip_vertex> geoVertices;
+    DevArray<slrhip_triangle> geoTriangles;
+    DevArray<float4> geoLeafBoxes;
+    DevArray<uint32_t> geometryStatus;
+    std::vector<uint32_t> geoLevelFirst;
+    bool geometryKept = false;
+    uint32_t geoNumVertices = 0, geoNumTriangles = 0, geoNumLights = 0, geoNumAlphaRecords = 0;
+    bool geoHasTriUV = false;
+    uint32_t geoLastLaunches = 0;                 // launches of the last slrhip_set_vertices call (slrhip_debug_geometry's summary)
     DevArray<slrhip::DevMaterial> materials;
     DevArray<slrhip::DevMaterialS> materialsS;
     DevArray<slrhip::DevSpectrum> spectra;
