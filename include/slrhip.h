@@ -1236,7 +1236,8 @@ int slrhip_env_texels_to_uvs(const float* rgb, size_t num_texels, float* uvs);
  * that uploaded the scene with the new matrices: every bit of the frame, of the hits and of the counters.  The top-level tree keeps
  * its SHAPE and gets new child boxes (a refit on the device, bottom-up); hits do not depend on the tree's shape because the tie rule
  * among equal distances is a rule on (instance, triangle) pairs.  Speed does depend on it: after large motion the tree fits the scene
- * badly and rays visit more nodes (DESIGN.md has the measured factor); a caller for whom that matters uploads the scene again.
+ * badly and rays visit more nodes (DESIGN.md has the measured factor); a caller for whom that matters calls
+ * slrhip_rebuild_top_level (below), or uploads the scene again.
  *
  * A record is checked on the device as slrhip_upload_scene checks an instance: every entry finite, bottom rows 0 0 0 1.  A record
  * that fails leaves ITS instance exactly as it was (matrices and box), the others of the call move, and SLRHIP_INSTANCE_BAD_TRANSFORM
@@ -1251,7 +1252,7 @@ int slrhip_env_texels_to_uvs(const float* rgb, size_t num_texels, float* uvs);
  * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, count == 0, a misaligned
  * pointer (16 bytes), a range beyond slrhip_scene_desc::num_instances.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.
  * SLRHIP_ERR_UNSUPPORTED for a scene without instances.  Not covered: adding or removing instances, instances that emit, moving
- * loose triangles (flat scenes: slrhip_set_vertices), a rebuild of the top level.                                                  */
+ * loose triangles (flat scenes: slrhip_set_vertices).  Repairing the top level after large motion: slrhip_rebuild_top_level.      */
 #define SLRHIP_INSTANCE_BAD_TRANSFORM 1u   /* a record of a call had a non-finite entry or a bottom row other than 0 0 0 1; its instance did not move */
 typedef struct slrhip_instance_transform {
     float local_to_world[16];
@@ -1274,6 +1275,71 @@ int slrhip_instance_world_box(const float mesh_lo[3], const float mesh_hi[3], co
  * slrhip_render_begin.  The image size is slrhip_render_begin's, so `aspect` should agree with it as it does at upload.
  * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.                                  */
 int slrhip_set_camera(slrhip_ctx* ctx, const slrhip_camera* camera);
+
+/* ---- repairing the top-level tree after instances have moved ---------------------------------------------------------------------------
+ * slrhip_set_instance_transforms keeps the top-level tree's shape; after large motion the shape no longer fits the scene.
+ * slrhip_rebuild_top_level keeps the shape too, and moves the LEAVES: the top level's primitives are sorted by the Morton code of
+ * their box centres and seated in that order into the leaf slots of the tree as it stands, taken depth-first; then the refit of
+ * slrhip_set_instance_transforms runs.  It is the CALLER'S decision: on a tree that has lost its fit the call repairs most of the
+ * damage, on a tree that still fits it makes the tree somewhat WORSE than the upload's (INTEGRATION.md has the figures), and on a
+ * tiny top level that mixes large packets of loose triangles with small instances it does not help.  slrhip_top_level_cost is the
+ * read-out to decide with.
+ *
+ * Primitives.  A top-level primitive is a leaf child of the top-level tree: an instance leaf (count 0, index = the instance) or a
+ * packet of loose triangles (count >= 1).  Their canonical order is ascending child word: the instances first, by index.  An
+ * instance's box is its current world box (what slrhip_set_instance_transforms maintains); a packet's box is the box the upload
+ * gave its slot (loose triangles of an instanced scene never move).
+ *
+ * Scene box.  Per axis the minimum of the primitives' lo and the maximum of their hi — equal to the union of the root's valid child
+ * boxes, because uploads and refits keep unions exact.
+ *
+ * Key (slrhip_top_level_key; one definition for host and device, slr_amd/csrc/pt_toplevel.h).  float32 throughout, every operation
+ * rounded on its own, IEEE division.  Per axis a:  c = (lo[a] + hi[a]) * 0.5f;  e = scene_hi[a] - scene_lo[a];
+ * x = e > 0 ? (c - scene_lo[a]) / e : 0;  q = x >= 0 ? (uint32_t)fminf(floorf(x * 2097152.0f), 2097151.0f) : 0 (a NaN gives 0).
+ * The key is the 63-bit interleave of the three axes: bit 3 i + 2 is bit i of q.x, bit 3 i + 1 bit i of q.y, bit 3 i bit i of q.z.
+ *
+ * Order.  The primitives are sorted stably by ascending key: equal keys (coincident placements) keep the canonical order.
+ *
+ * Slots.  The leaf slots of the top-level tree depth-first from node 0: child slots 0 .. 3 in order, an inner child's whole subtree
+ * before the next slot.  Inner child words never change, so the slot table is fixed per upload.
+ *
+ * Seating.  Slot i receives primitive order[i]: its child word and its six planes.  Then every inner child box of the top level is
+ * refitted bottom-up, by the rule and the launches of slrhip_set_instance_transforms.
+ *
+ * What stays: the number of top-level nodes, the level table, slrhip_counters::bvh_nodes and bvh_depth, every inner child word and
+ * pad word, every node of the mesh trees, the instance records, the instance and mesh boxes, the triangle records and every
+ * pointer the kernels hold.  Only leaf child words and child planes of the top-level nodes are written.  The result is a pure
+ * function of the primitives' boxes: a second call with nothing moved in between changes no bit.  slrhip_set_instance_transforms
+ * keeps working after the call, and its refit then runs over the new arrangement.
+ *
+ * Behaviour.  Hits do not depend on the tree's shape.  From the call on the context renders, answers slrhip_intersect_rays /
+ * slrhip_test_visibility and fills feature buffers exactly as before the call, and as a fresh context does that uploaded the
+ * current placements: every bit of the frame, of the hits and of the counters.  Only speed changes.  Nothing accumulated is reset.
+ *
+ * Ordering.  The FIRST call after a slrhip_upload_scene reads the top level back once, builds the slot table, the canonical
+ * references and the packets' boxes on the host and allocates what the calls need (those tables, keys, order, the sort's
+ * temporary storage): it synchronises and cannot be captured.  Every LATER call allocates nothing, copies nothing from the host
+ * and does not synchronise; its launches are ordered on `stream` (two to a handful: at most SLRHIP_TOP_SEAT_GROUP primitives are
+ * sorted and seated by one launch of one workgroup, more by a key launch, a device radix sort and a seat launch; the refit's
+ * launches follow).  slrhip_upload_scene drops the state.
+ *
+ * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context.  SLRHIP_ERR_NO_SCENE before
+ * slrhip_upload_scene.  SLRHIP_ERR_UNSUPPORTED ("the scene has no instances") for a flat scene.  Not covered: another node count
+ * (a rebuild of the SHAPE), adding or removing instances, the mesh trees.                                                        */
+#define SLRHIP_TOP_SEAT_GROUP 4096u
+int slrhip_rebuild_top_level(slrhip_ctx* ctx, void* stream);
+
+/* The expected number of top-level nodes a random line through the root box visits, the surface-area measure of how well the top
+ * level fits: 1 + (sum of the surface areas of all inner-child boxes) / (area of the root box).  Computed in double on the HOST
+ * from a read-back of the top-level nodes: the sum runs in node order, then child order; a box's area is 2 (dx dy + dy dz + dz dx)
+ * of max(hi - lo, 0) taken in double; the root box is the union of the root's valid children, and a root of zero area gives 1.
+ * Waits for `stream`; allocates nothing on the device.  A caller compares the value before and after a move or a rebuild, or
+ * against the upload's.  The refusals of slrhip_rebuild_top_level, and SLRHIP_ERR_INVALID_ARGUMENT for a null pointer.          */
+int slrhip_top_level_cost(slrhip_ctx* ctx, double* host_cost, void* stream);
+
+/* The key of the box [lo, hi] in the scene box [scene_lo, scene_hi], on the HOST (pure), with the function the kernels call.
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null pointer.                                                                                */
+int slrhip_top_level_key(const float lo[3], const float hi[3], const float scene_lo[3], const float scene_hi[3], uint64_t* key);
 
 /* ---- host-side construction of spectral-mode spectra ------------------------------------------------------------------ */
 /* SpectrumType / ColorSpace of the reference (BasicTypes/Spectrum.h:17-35), as the scene language's Spectrum(...) passes them. */

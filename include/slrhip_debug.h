@@ -111,6 +111,43 @@ int slrhip_debug_instance_update_check(int32_t have_scene, uint32_t num_instance
  * little room.                                                                                                                      */
 int slrhip_debug_top_level(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
 
+/* The checks of slrhip_rebuild_top_level (slr_amd/csrc/render_plan.h, topLevelRebuildRefusal), evaluated on the HOST with the function
+ * the entry point calls, for a context that holds a scene (have_scene != 0) of `num_instances` instances or none: SLRHIP_OK if the call
+ * would go ahead, else the code it returns, with the reason in slrhip_last_error_string.  No GPU is touched.                        */
+int slrhip_debug_top_level_rebuild_check(int32_t have_scene, uint32_t num_instances);
+
+/* The plan slrhip_rebuild_top_level's first call builds (slr_amd/csrc/top_level.cpp — the function it calls), on the HOST, from QNode
+ * records (slrhip_debug_top_level's what 0 layout) whose first `top_nodes` are a top level: slots[i] = node * 4 + child of the leaf
+ * slots depth-first from node 0 (child slots 0 .. 3 in order, an inner child's whole subtree before the next slot), refs[i] = the
+ * child words of those slots ASCENDING (the canonical order of the primitives: instances 0 .. n - 1, then the packets), *count their
+ * number.  capacity: room at slots and at refs (4 x top_nodes always suffice).  No GPU is touched.  SLRHIP_ERR_INVALID_ARGUMENT, with
+ * *count = 0, for a null pointer, too little room, or nodes that are no top level (an inner child outside (its node, top_nodes), no
+ * leaf, instance leaves that are not 0 .. n - 1 once each).                                                                         */
+int slrhip_debug_top_level_plan(const void* nodes, uint32_t top_nodes, uint32_t* slots, uint32_t* refs, uint32_t capacity, uint32_t* count);
+
+/* The WHOLE operation of slrhip_rebuild_top_level on a host copy of QNode records, in place, through the same header as the kernels
+ * (slr_amd/csrc/pt_toplevel.h): plan, boxes (instance_boxes: slrhip_debug_top_level's what 3 layout, `num_instances` of them; a packet's
+ * box is its slot's), scene box, keys, stable order, seat, refit.  keys_out[p] = the key of primitive p, order_out[i] = the primitive
+ * slot i received; room for every primitive each, or NULL.  Works on slrhip_debug_host_tree's nodes and on a slrhip_debug_top_level
+ * read-out; nodes at or behind top_nodes are not touched.  No GPU is touched.  SLRHIP_ERR_INVALID_ARGUMENT, with nothing changed, as
+ * slrhip_debug_top_level_plan, and when the plan's instances are not `num_instances`.                                               */
+int slrhip_debug_top_level_reseat(void* nodes, uint32_t top_nodes, const float* instance_boxes, uint32_t num_instances, uint64_t* keys_out,
+                                  uint32_t* order_out);
+
+/* slrhip_top_level_cost's value of QNode records on the HOST, with the function it calls.  No GPU is touched.                      */
+int slrhip_debug_top_level_cost(const void* nodes, uint32_t top_nodes, double* cost);
+
+/* The tables and the last call of slrhip_rebuild_top_level, read back to HOST memory as 32-bit words.  what:
+ *   0  8 words: [0] primitives (0 before the first call after an upload: the tables are built by it), [1] SLRHIP_TOP_SEAT_GROUP,
+ *      [2] the path of the last call (0 none yet, 1 one launch of one workgroup, 2 keys + device radix sort + seat), [3] its launches,
+ *      the refit's included and the radix sort counted as one, [4] instances, [5] 1 if the tables are built, the rest 0
+ *   1  the slot table, one word a primitive (node * 4 + child)         2  the canonical references, one word a primitive
+ *   3  the keys of the last call by primitive, two words each (low, high)
+ *   4  the order of the last call: word i = the primitive slot i received
+ * num_words: room at host_dst, at least that many.  Synchronises; changes nothing.  The refusals of slrhip_rebuild_top_level;
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room.                                             */
+int slrhip_debug_top_level_rebuild(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
+
 /* The argument checks of slrhip_set_vertices (slr_amd/csrc/render_plan.h, geometryUpdateRefusal), evaluated on the HOST with the
  * function the entry point calls, for a context that holds a scene (have_scene != 0) or none, created with SLRHIP_FLAG_DYNAMIC_GEOMETRY
  * (dynamic != 0) or without, whose tree came from builder `tree_builder` (SLRHIP_TREE_*, below) and whose scene has `num_instances`

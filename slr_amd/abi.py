@@ -44,6 +44,7 @@ devinstance_dtype = np.dtype([("local_to_world", "<f4", 16), ("world_to_local", 
                               ("num_triangles", "<u4"), ("mesh", "<u4")])
 INVALID_CHILD, LEAF_FLAG, LEAF_COUNT_SHIFT, LEAF_INDEX_MASK, MAX_LEAF_TRIS = 0xFFFFFFFF, 0x80000000, 27, (1 << 27) - 1, 4
 TREE_HOST_SAH, TREE_HOST_SPATIAL_SPLITS, TREE_DEVICE, TREE_INSTANCED = 0, 1, 2, 3
+TOP_SEAT_GROUP = 4096          # SLRHIP_TOP_SEAT_GROUP: the most top-level primitives slrhip_rebuild_top_level sorts in one workgroup
 TREE_BUILDERS = ("host SAH", "host spatial splits", "device", "instanced")
 INSTANCE_BAD_TRANSFORM = 1     # slrhip_instances_status: a record was not finite or not affine; its instance did not move
 GEOMETRY_BAD_VERTEX = 1        # slrhip_geometry_status: a record of set_vertices had a non-finite float; its vertex did not move

@@ -23,6 +23,8 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_environment", "slrhip_env_importance", "slrhip_env_texels_to_uvs", "slrhip_debug_environment_check", "slrhip_debug_environment",
            "slrhip_set_instance_transforms", "slrhip_instances_status", "slrhip_instance_world_box", "slrhip_set_camera",
            "slrhip_debug_instance_update_check", "slrhip_debug_top_level",
+           "slrhip_rebuild_top_level", "slrhip_top_level_cost", "slrhip_top_level_key", "slrhip_debug_top_level_rebuild_check",
+           "slrhip_debug_top_level_plan", "slrhip_debug_top_level_reseat", "slrhip_debug_top_level_cost", "slrhip_debug_top_level_rebuild",
            "slrhip_render_motion", "slrhip_resolve_motion", "slrhip_read_motion", "slrhip_motion_camera", "slrhip_motion_sample", "slrhip_reproject",
            "slrhip_debug_motion_check", "slrhip_debug_reproject_check",
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
@@ -139,6 +141,17 @@ def load_library():
                            ("slrhip_set_camera", [C.c_void_p, C.POINTER(abi.Camera)]),
                            ("slrhip_debug_instance_update_check", [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
                            ("slrhip_debug_top_level", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before the top level could be re-seated lacks these eight)
+    for name, argtypes in (("slrhip_rebuild_top_level", [C.c_void_p, C.c_void_p]),
+                           ("slrhip_top_level_cost", [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+                           ("slrhip_top_level_key", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+                           ("slrhip_debug_top_level_rebuild_check", [C.c_int32, C.c_uint32]),
+                           ("slrhip_debug_top_level_plan", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+                           ("slrhip_debug_top_level_reseat", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+                           ("slrhip_debug_top_level_cost", [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
+                           ("slrhip_debug_top_level_rebuild", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     # (and one from before motion vectors and temporal reprojection lacks these eight)
@@ -442,6 +455,34 @@ class Context:
         return dict(levels=head[8:8 + levels + 1].copy(), top_nodes=top, group_nodes=int(head[5]), nodes=read(4, total * 32).reshape(total, 32),
                     instances=read(2, n * 36).reshape(n, 36), boxes=read(3, n * 8, np.float32).reshape(n, 2, 4),
                     mesh_boxes=read(5, meshes * 8, np.float32).reshape(meshes, 2, 4))
+
+    # ---- repairing the top level after instances have moved (slrhip_rebuild_top_level) ----
+    def rebuild_top_level(self, stream=None):
+        """Re-seats the leaves of the top-level tree in Morton order and refits it (slrhip_rebuild_top_level), ordered on `stream` (a
+        torch stream, a raw handle, None = the null stream).  The first call after an upload builds its tables and synchronises; later
+        calls return at once.  Hits, frames and counters do not change; speed does, in either direction: see top_level_cost()."""
+        _check(self.lib, self.lib.slrhip_rebuild_top_level(self.handle, self._stream_handle(stream)), "slrhip_rebuild_top_level")
+
+    def top_level_cost(self, stream=None):
+        """The surface-area cost of the top level as it stands (slrhip_top_level_cost): the expected number of top-level nodes a
+        random line through the root box visits.  Waits for `stream`."""
+        cost = C.c_double(0.0)
+        _check(self.lib, self.lib.slrhip_top_level_cost(self.handle, C.byref(cost), self._stream_handle(stream)), "slrhip_top_level_cost")
+        return cost.value
+
+    def debug_top_level_rebuild(self):
+        """Diagnostic (slrhip_debug_top_level_rebuild): primitives (0 before the first rebuild after an upload), seat_group (the most
+        primitives the one-workgroup path takes), path ("none", "group" or "radix": the last call's), launches (the last call's, the
+        refit's included, the radix sort counted as one), num_instances, slots and refs [primitives] uint32, keys [primitives] uint64
+        and order [primitives] uint32 of the last call.  Synchronises."""
+        def read(what, count, dtype=np.uint32):
+            out = np.zeros(count, dtype)
+            _check(self.lib, self.lib.slrhip_debug_top_level_rebuild(self.handle, what, out.ctypes.data, out.nbytes // 4), "slrhip_debug_top_level_rebuild")
+            return out
+        head = read(0, 8)
+        n = int(head[0])
+        return dict(primitives=n, seat_group=int(head[1]), path=("none", "group", "radix")[int(head[2])], launches=int(head[3]),
+                    num_instances=int(head[4]), slots=read(1, n), refs=read(2, n), keys=read(3, n, np.uint64), order=read(4, n))
 
     def debug_tree(self, summary_only=False):
         """Diagnostic (slrhip_debug_tree): the tree of the uploaded scene, whichever builder made it, as the dict _read_tree describes
@@ -1088,6 +1129,78 @@ def instance_world_box(mesh_lo, mesh_hi, local_to_world):
     if lib.slrhip_instance_world_box(lo.ctypes.data, hi.ctypes.data, m.ctypes.data, out_lo.ctypes.data, out_hi.ctypes.data) != 0:
         raise ValueError("instance_world_box: refused")
     return out_lo, out_hi
+
+
+def top_level_key(lo, hi, scene_lo, scene_hi):
+    """The sort key of a top-level primitive's box [lo, hi] in the scene box (slrhip_top_level_key: the function the kernels of
+    rebuild_top_level call), as a Python int (63 bits)."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, np.float32).reshape(-1) for v in (lo, hi, scene_lo, scene_hi)]
+    if any(len(v) != 3 for v in a):
+        raise ValueError("top_level_key: four [3] arrays expected")
+    key = C.c_uint64(0)
+    if lib.slrhip_top_level_key(*(v.ctypes.data for v in a), C.byref(key)) != 0:
+        raise ValueError("top_level_key: refused")
+    return key.value
+
+
+def _qnode_words(nodes):
+    """QNode records (abi.qnode_dtype, or [n, 32] uint32 words) as a fresh contiguous [n, 32] uint32 array."""
+    a = np.array(nodes, copy=True, order="C")
+    if a.dtype == abi.qnode_dtype:
+        a = a.view(np.uint32).reshape(len(a), 32)
+    if a.dtype != np.uint32 or a.ndim != 2 or a.shape[1] != 32:
+        raise ValueError("nodes: abi.qnode_dtype records or [n, 32] uint32 words expected")
+    return a
+
+
+def top_level_plan(nodes, top_nodes):
+    """Diagnostic (slrhip_debug_top_level_plan): (slots, refs) of the first `top_nodes` QNode records — the leaf slots depth-first
+    (node * 4 + child) and the primitives' child words ascending, uint32 each.  No GPU; raises SlrHipError for nodes that are no top
+    level."""
+    lib = load_library()
+    a = _qnode_words(nodes)
+    slots, refs, count = np.zeros(4 * top_nodes, np.uint32), np.zeros(4 * top_nodes, np.uint32), C.c_uint32(0)
+    if top_nodes > len(a):
+        raise ValueError("top_level_plan: top_nodes beyond the nodes given")
+    _check(lib, lib.slrhip_debug_top_level_plan(a.ctypes.data, top_nodes, slots.ctypes.data, refs.ctypes.data, len(slots), C.byref(count)),
+           "slrhip_debug_top_level_plan")
+    return slots[:count.value].copy(), refs[:count.value].copy()
+
+
+def top_level_reseat(nodes, top_nodes, instance_boxes):
+    """Diagnostic (slrhip_debug_top_level_reseat): the whole of rebuild_top_level on a host copy of QNode records — (nodes after,
+    in the form given; keys [primitives] uint64 by primitive; order [primitives] uint32 by slot).  instance_boxes: [n, 2, 4] float32
+    (lo, hi) as debug_top_level()["boxes"] and a tree read-out's "instance_boxes" hold them.  No GPU."""
+    lib = load_library()
+    a = _qnode_words(nodes)
+    boxes = np.ascontiguousarray(instance_boxes, np.float32)
+    if boxes.ndim != 3 or boxes.shape[1:] != (2, 4) or top_nodes > len(a):
+        raise ValueError("top_level_reseat: instance_boxes [n, 2, 4] and top_nodes <= len(nodes) expected")
+    keys, order = np.zeros(4 * top_nodes, np.uint64), np.zeros(4 * top_nodes, np.uint32)
+    _check(lib, lib.slrhip_debug_top_level_reseat(a.ctypes.data, top_nodes, boxes.ctypes.data, len(boxes), keys.ctypes.data, order.ctypes.data),
+           "slrhip_debug_top_level_reseat")
+    n = len(top_level_plan(a, top_nodes)[0])
+    out = a.reshape(-1).view(abi.qnode_dtype) if np.asarray(nodes).dtype == abi.qnode_dtype else a
+    return out, keys[:n].copy(), order[:n].copy()
+
+
+def top_level_cost_of(nodes, top_nodes):
+    """Diagnostic (slrhip_debug_top_level_cost): Context.top_level_cost()'s value of QNode records on the host.  No GPU."""
+    lib = load_library()
+    a = _qnode_words(nodes)
+    cost = C.c_double(0.0)
+    if top_nodes > len(a):
+        raise ValueError("top_level_cost_of: top_nodes beyond the nodes given")
+    _check(lib, lib.slrhip_debug_top_level_cost(a.ctypes.data, top_nodes, C.byref(cost)), "slrhip_debug_top_level_cost")
+    return cost.value
+
+
+def top_level_rebuild_check(have_scene, num_instances):
+    """Diagnostic (slrhip_debug_top_level_rebuild_check): the checks of Context.rebuild_top_level without a context; raises SlrHipError
+    with the code and the message the call would give.  No GPU."""
+    lib = load_library()
+    _check(lib, lib.slrhip_debug_top_level_rebuild_check(int(have_scene), num_instances), "slrhip_debug_top_level_rebuild_check")
 
 
 def motion_camera(camera):

@@ -66,6 +66,9 @@ struct InstanceUpdate {
     uint32_t levelFirst[kMaxTopLevels + 1];                // first node of each top-level level; [numLevels] = topNodes
 };
 void launchInstanceUpdate(const InstanceUpdate& u, hipStream_t stream);
+// The refit alone (src, first, count, instances, meshBoxes and status are not read): what slrhip_rebuild_top_level runs after it has
+// seated the leaves (pt_toplevel.hip).  Returns the number of launches.
+uint32_t launchTopRefit(const InstanceUpdate& u, hipStream_t stream);
 #endif
 
 } // namespace slrhip

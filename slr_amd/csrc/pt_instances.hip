@@ -18,6 +18,8 @@
 //
 // No atomics but the status bit, no parent pointers, no flags between workgroups: the order comes from the launches.  Only the
 // first topNodes nodes are written; a mesh's tree lives in its local space and does not change when a placement moves.
+// The refit's launches are a function of their own (launchTopRefit): slrhip_rebuild_top_level runs them after it has seated the
+// leaves (pt_toplevel.hip).
 #include <hip/hip_runtime.h>
 
 #include "../../include/slrhip.h"
@@ -77,8 +79,14 @@ __global__ __launch_bounds__(kRefitBlock) void k_top_refit_levels(InstanceUpdate
 
 void launchInstanceUpdate(const InstanceUpdate& u, hipStream_t stream) {
     hipLaunchKernelGGL(k_instance_place, dim3((u.count + 255u) / 256u), dim3(256), 0, stream, u);
+    launchTopRefit(u, stream);
+}
+
+uint32_t launchTopRefit(const InstanceUpdate& u, hipStream_t stream) {
+    uint32_t launches = 0;
     // from the deepest level to the root; consecutive levels that fit one workgroup share a launch
     for (uint32_t level = u.numLevels; level-- > 0u;) {
+        ++launches;
         const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
         if (count > kRefitGroupNodes) {
             hipLaunchKernelGGL(k_top_refit, dim3((4u * count + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, stream, u.nodes, u.instBoxes, first, count,
@@ -90,6 +98,7 @@ void launchInstanceUpdate(const InstanceUpdate& u, hipStream_t stream) {
         hipLaunchKernelGGL(k_top_refit_levels, dim3(1), dim3(kRefitBlock), 0, stream, u, level, lo);
         level = lo;
     }
+    return launches;
 }
 
 } // namespace slrhip

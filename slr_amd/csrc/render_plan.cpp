@@ -325,6 +325,13 @@ int instanceUpdateRefusal(bool haveScene, uint32_t numInstances, const void* dev
     return SLRHIP_OK;
 }
 
+int topLevelRebuildRefusal(bool haveScene, uint32_t numInstances, const char** what) {
+    if (!haveScene) { *what = "no scene uploaded"; return SLRHIP_ERR_NO_SCENE; }
+    if (numInstances == 0) { *what = "the scene has no instances"; return SLRHIP_ERR_UNSUPPORTED; }
+    *what = nullptr;
+    return SLRHIP_OK;
+}
+
 int geometryUpdateRefusal(bool haveScene, bool dynamic, uint32_t treeBuilder, uint32_t numInstances, uint32_t numVertices, const void* deviceSrc,
                           uint32_t first, uint32_t count, const char** what) {
     if (!deviceSrc) { *what = "null device_src"; return SLRHIP_ERR_INVALID_ARGUMENT; }

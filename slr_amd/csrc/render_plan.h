@@ -118,6 +118,9 @@ const char* environmentRefusal(const slrhip_environment_desc& d);
 // The argument checks of slrhip_set_instance_transforms against what the context holds (a scene or none, its number of instances; the
 // pointer is only compared, never followed): SLRHIP_OK if the call goes ahead, else the code it returns with *what = what is wrong.
 int instanceUpdateRefusal(bool haveScene, uint32_t numInstances, const void* deviceSrc, uint32_t first, uint32_t count, const char** what);
+// The checks of slrhip_rebuild_top_level and slrhip_top_level_cost against what the context holds (a scene or none, its number of
+// instances): SLRHIP_OK if the call goes ahead, else the code it returns with *what = what is wrong.
+int topLevelRebuildRefusal(bool haveScene, uint32_t numInstances, const char** what);
 // The argument checks of slrhip_set_vertices against what the context holds (a scene or none, created with SLRHIP_FLAG_DYNAMIC_GEOMETRY
 // or not, the builder behind the scene's tree as include/slrhip_debug.h numbers them, its numbers of instances and vertices; the pointer
 // is only compared, never followed): SLRHIP_OK if the call goes ahead, else the code it returns with *what = what is wrong.

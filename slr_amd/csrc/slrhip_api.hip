@@ -106,6 +106,8 @@ static void bindScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepare
 // last step has succeeded: a failure here leaves it without one (SLRHIP_ERR_NO_SCENE), never naming freed or mismatched arrays.
 static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const PreparedScene& p) {
     ctx->haveScene = ctx->haveRender = false;
+    ctx->topSeatReady = false;                    // slrhip_rebuild_top_level's tables are the previous scene's: its next call builds them again
+    ctx->topPrimitives = ctx->topLastPath = ctx->topLastLaunches = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     uint32_t numNodes = (uint32_t)p.bvh.nodes.size(), depth = p.bvh.depth;
     uint64_t leafRefs = p.bvh.leafTris.size();

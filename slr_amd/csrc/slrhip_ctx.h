@@ -1,5 +1,5 @@
 // slrhip_ctx.h — the context behind the C ABI of include/slrhip.h and what its translation units share: slrhip_api.hip,
-// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_geometry.hip, slrhip_diagnostics.hip.  Internal: not installed.
+// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_toplevel.hip, slrhip_geometry.hip, slrhip_diagnostics.hip.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,6 +105,18 @@ struct slrhip_ctx {
     DevArray<float4> meshBoxes, instBoxes;
     DevArray<uint32_t> instanceStatus;
     std::vector<uint32_t> topLevelFirst;
+    // slrhip_rebuild_top_level (slrhip_toplevel.hip): what its first call after an upload builds and allocates — the leaf slots of
+    // the top level depth-first, the primitives' child words in canonical order, the packets' boxes, the identity the radix sort
+    // permutes — and what every call writes: keys by primitive, the order (slot i receives primitive topOrder[i]).  topSeatReady:
+    // they belong to the scene in place (slrhip_upload_scene drops them).
+    DevArray<uint32_t> topSlots, topRefs, topIdentity, topOrder;
+    DevArray<float4> topPacketBoxes;
+    DevArray<uint64_t> topKeys, topSortedKeys;
+    DevArray<uint8_t> topSortTemp;
+    std::vector<uint32_t> topSlotsHost, topRefsHost;
+    bool topSeatReady = false;
+    uint32_t topPrimitives = 0;
+    uint32_t topLastPath = 0, topLastLaunches = 0;       // the last call: 1 one workgroup, 2 keys + radix sort + seat; its launches (0: none yet)
     // slrhip_set_vertices (contexts created with SLRHIP_FLAG_DYNAMIC_GEOMETRY; flat scenes without spatial splits): the scene's vertex
     // and index arrays, one box (lo, hi) per LeafTri record as scratch, its status word, and the first node of each tree level, then the
     // number of nodes.  geometryKept: the arrays belong to the scene in place (else they are empty or an earlier scene's, and unused).
