@@ -351,6 +351,10 @@ typedef struct slrhip_profile {
 } slrhip_profile;
 
 /* config.flags */
+#define SLRHIP_FLAG_DYNAMIC_INSTANCED 1024u /* together with SLRHIP_FLAG_DYNAMIC_GEOMETRY (alone it means nothing): also keep what slrhip_set_vertices
+                                         * works from for a scene WITH instances, and accept the call on it.  Memory: as below (a leaf record is
+                                         * the top level's or a mesh's) + 4 B per mesh node + 4 B per mesh.  With 512 alone a scene with
+                                         * instances is refused as before; a flat scene behaves the same with or without this flag.                  */
 #define SLRHIP_FLAG_DYNAMIC_GEOMETRY 512u /* keep what slrhip_set_vertices works from (see there): the scene's vertex and index arrays, one box per leaf
                                          * record and the tree's level table stay on the device after slrhip_upload_scene.  Memory: 44 B per vertex +
                                          * 16 B per triangle + 32 B per leaf record.  Without the flag nothing is kept and nothing else changes.      */
@@ -1409,12 +1413,28 @@ int slrhip_save_bmp(const char* path, const uint8_t* bgr_bottom_up, int32_t widt
  *
  * Errors, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, count == 0, a misaligned
  * pointer (4 bytes), a range beyond slrhip_scene_desc::num_vertices.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.
- * SLRHIP_ERR_UNSUPPORTED: a context created without SLRHIP_FLAG_DYNAMIC_GEOMETRY, a scene with instances, a tree built with spatial
- * splits (its leaf boxes are clipped and its references duplicated).
- * Not covered: scenes with instances (mesh-tree refits, new mesh and instance boxes: a follow-up), spatial-split trees, adding or
- * removing vertices or triangles, changing indices or materials, a rebuild when the tree has degraded (the caller uploads again),
- * motion vectors of moved vertices (slrhip_render_motion still takes loose triangles to stand still), the C++ host mirror and the
- * libSLR adapter.                                                                                                                   */
+ * SLRHIP_ERR_UNSUPPORTED: a context created without SLRHIP_FLAG_DYNAMIC_GEOMETRY, a scene with instances in a context created
+ * without SLRHIP_FLAG_DYNAMIC_INSTANCED, a tree built with spatial splits (its leaf boxes are clipped and its references duplicated).
+ *
+ * Scenes with instances.  A context created with SLRHIP_FLAG_DYNAMIC_GEOMETRY | SLRHIP_FLAG_DYNAMIC_INSTANCED keeps the same arrays
+ * for a scene with instances (the leaf records of the top level's loose packets and of every mesh share one array), and on top of
+ * them the mesh trees' merged level list (4 B per mesh node: level d of EVERY mesh tree is one run, so the refit's launches are
+ * bounded by the deepest mesh, not by meshes x depth) and each mesh's root.  The call then runs, in order on `stream`: the vertex
+ * store and the record kernels as for a flat scene (a mesh's triangles stay in its local space, exactly as the upload stores them);
+ * the refit of ALL mesh trees, deepest merged level first; one launch that gives every mesh its box (the exact union of the valid
+ * child boxes of its root) and every instance its world box (the upload's bounds() arithmetic on that box and the instance's CURRENT
+ * local_to_world, with that function's own pad and no other); the top-level refit, where an instance child takes its world box and a
+ * loose packet the union of its triangles' boxes; and, where slrhip_rebuild_top_level has built its tables, a refresh of the
+ * packet boxes it seats with.  The contract is the one above, read as: a fresh context that uploaded the scene with the kept
+ * vertex array AND the current placements — frames, slrhip_intersect_rays with instance ids, slrhip_test_visibility, feature,
+ * albedo and motion buffers, and the three counters, bit for bit.  Both tree levels keep their shape.  All meshes are refitted on
+ * every call, whatever the range.  slrhip_set_instance_transforms afterwards places against the new mesh boxes, and
+ * slrhip_rebuild_top_level afterwards seats with the new packet boxes.
+ *
+ * Not covered: spatial-split trees; adding or removing vertices, triangles or instances; changing indices or materials; a change
+ * of SHAPE of either tree level (slrhip_rebuild_top_level re-seats the top level's leaves, nothing rebuilds a mesh tree: the caller
+ * uploads again when a tree has degraded); instances that emit; motion vectors of moved vertices (slrhip_render_motion still takes
+ * vertices to stand still); the C++ host mirror and the libSLR adapter.                                                             */
 #define SLRHIP_GEOMETRY_BAD_VERTEX 1u      /* a record of a call had a non-finite float; its vertex did not move */
 int slrhip_set_vertices(slrhip_ctx* ctx, const slrhip_vertex* device_src, uint32_t first_vertex, uint32_t count, void* stream);
 /* The SLRHIP_GEOMETRY_* bits of the calls since the last read, then cleared; waits for `stream`.  0 before any scene.              */

@@ -156,6 +156,13 @@ int slrhip_debug_top_level_rebuild(slrhip_ctx* ctx, uint32_t what, void* host_ds
 int slrhip_debug_geometry_update_check(int32_t have_scene, int32_t dynamic, uint32_t tree_builder, uint32_t num_instances, uint32_t num_vertices,
                                        const void* device_src, uint32_t first_vertex, uint32_t count);
 
+/* The same checks with one more input (geometryUpdateRefusal2, the function slrhip_set_vertices itself calls): instanced_kept != 0 for a
+ * context created with SLRHIP_FLAG_DYNAMIC_INSTANCED as well, which keeps what the call needs of a scene with instances.  Then
+ * `num_instances` != 0 and SLRHIP_TREE_INSTANCED are no refusal; every other answer, code and message is the check's above, and with
+ * instanced_kept == 0 so are all of them.  No GPU is touched.                                                                         */
+int slrhip_debug_geometry_update_check2(int32_t have_scene, int32_t dynamic, int32_t instanced_kept, uint32_t tree_builder, uint32_t num_instances,
+                                        uint32_t num_vertices, const void* device_src, uint32_t first_vertex, uint32_t count);
+
 /* What slrhip_set_vertices keeps and rewrites beyond the tree (slrhip_debug_tree reads that), read back to HOST memory as 32-bit
  * words.  what:
  *   0  the summary, 32 words: [0] levels of the tree, [1] nodes, [2] vertices, [3] triangles, [4] lights, [5] 1 if the shade tables are
@@ -168,8 +175,22 @@ int slrhip_debug_geometry_update_check(int32_t have_scene, int32_t dynamic, uint
  *   3  the same records as staged in the shade tables; SLRHIP_ERR_UNSUPPORTED when the tables are not staged
  *   4  triUV, 8 words per triangle: u0 v0 u1 v1, u2 v2 0 0 (floats)
  *   5  the alpha records, 8 words each: u0 v0 u1 v1, u2 v2 (floats), the texture's index, 0
+ *   6  the summary of a scene with instances, 48 words: [0] 1 if the scene has instances and is kept (else the words [1 .. 6], [9] and
+ *      [16 ..] are 0), [1] levels of the top level, [2] merged levels of the mesh trees (the depth of the deepest mesh), [3] meshes,
+ *      [4] instances, [5] nodes of the top level, [6] mesh nodes (the entries of the merged list), [7] LeafTri records (the boxes of
+ *      what 8), [8] the launches of the last slrhip_set_vertices call, [9] the loose packets whose boxes the call refreshes for
+ *      slrhip_rebuild_top_level (0 before that call has built its tables), [16 .. 16 + [2]] the first entry of each merged level,
+ *      then [6] again
+ *   7  the merged mesh-level list, one word per mesh node: the node indices of level 0 (the roots) of every mesh, then level 1, ..
+ *   8  the leaf-box scratch as the last call left it, 8 words (floats) per LeafTri record: lo[3], 0, hi[3], 0 (before any call: not
+ *      initialised)
+ *   9  the root node of each mesh, one word each       10  slrhip_rebuild_top_level's packet boxes, 8 words (floats) per loose packet
+ *      in its canonical order: lo[3], 0, hi[3], 0
+ * For a scene with instances, what 0 describes the TOP level: [0] its levels, [7 .. 7 + levels] the first node of each, then the
+ * number of top-level nodes ([1] stays the number of all nodes).
  * num_words: room at host_dst, at least that many.  Synchronises.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene,
- * SLRHIP_ERR_UNSUPPORTED for a context without SLRHIP_FLAG_DYNAMIC_GEOMETRY or a scene slrhip_set_vertices does not cover,
+ * SLRHIP_ERR_UNSUPPORTED for a context without SLRHIP_FLAG_DYNAMIC_GEOMETRY or a scene slrhip_set_vertices does not cover (spatial
+ * splits; instances in a context without SLRHIP_FLAG_DYNAMIC_INSTANCED),
  * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room.                                          */
 int slrhip_debug_geometry(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
 

@@ -29,6 +29,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_debug_motion_check", "slrhip_debug_reproject_check",
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
+           "slrhip_debug_geometry_update_check2",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -180,6 +181,9 @@ def load_library():
                            ("slrhip_debug_geometry", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
+    # (and one from before the vertices of instanced scenes could move lacks this one)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_geometry_update_check2"):
+        lib.slrhip_debug_geometry_update_check2.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     # (and one from before the primary pass lacks these two)
@@ -389,7 +393,8 @@ class Context:
     def set_vertices(self, vertices, first=0, count=None, stream=None):
         """New records for the vertices [first, first + n) of the uploaded flat scene (slrhip_set_vertices): position, normal, tangent
         and texcoord all take effect, and every record and box that depends on them is rebuilt on the device; the tree keeps its shape
-        and nothing accumulated is reset.  `vertices`: a DEVICE address (an integer; `count` records), n records of abi.vertex_dtype, or a
+        and nothing accumulated is reset.  A scene with instances is covered in a context created with abi.FLAG_DYNAMIC_INSTANCED as
+        well: the mesh trees, the meshes' and instances' boxes and the top level are refitted too.  `vertices`: a DEVICE address (an integer; `count` records), n records of abi.vertex_dtype, or a
         contiguous [n, 11] float32 numpy array or torch CUDA tensor.  A tensor is passed without a copy and read in order on `stream`
         (default: torch.cuda.current_stream()); a numpy array is copied to the device first, and that call synchronises.  A record with a
         non-finite float leaves its vertex as it was: see geometry_status."""
@@ -423,8 +428,12 @@ class Context:
         """Diagnostic (slrhip_debug_geometry): what set_vertices keeps and rewrites beyond the tree, as a dict — levels (first node of
         each level, then the number of nodes), num_nodes, group_nodes (the widest level the refit takes in one workgroup), staged
         (the shade tables hold a second copy of the lights), launches (of the last set_vertices call), vertices (abi.vertex_dtype),
-        light_tris [n, 36] uint32, light_tris_staged (the same, or None), tri_uv [2 t, 4] float32, alpha [2 a, 4] uint32.
-        Synchronises."""
+        light_tris [n, 36] uint32, light_tris_staged (the same, or None), tri_uv [2 t, 4] float32, alpha [2 a, 4] uint32,
+        leaf_boxes [leaf records, 2, 4] float32 (the scratch as the last call left it).  For a scene with instances (instanced: True)
+        `levels` is the top level's table, and there are also: top_levels, mesh_depth (merged levels of the mesh trees), num_meshes,
+        num_instances, top_nodes, mesh_levels (first entry of each merged level, then the number of mesh nodes), mesh_level_nodes (the
+        merged list: one node index per mesh node), mesh_roots, packet_boxes [p, 2, 4] float32 (slrhip_rebuild_top_level's, once its
+        tables exist).  Synchronises."""
         def read(what, words, dtype=np.uint32):
             out = np.zeros(words, dtype)
             _check(self.lib, self.lib.slrhip_debug_geometry(self.handle, what, out.ctypes.data, out.nbytes // 4), "slrhip_debug_geometry")
@@ -432,10 +441,18 @@ class Context:
         head = read(0, 32)
         levels, nodes, nv, nt, nl, staged, group = (int(v) for v in head[:7])
         uv4, alpha, launches = (int(v) for v in head[8 + levels:11 + levels])
-        return dict(levels=head[7:8 + levels].copy(), num_nodes=nodes, num_triangles=nt, group_nodes=group, staged=bool(staged), launches=launches,
-                    vertices=read(1, nv, abi.vertex_dtype), light_tris=read(2, nl * 36).reshape(nl, 36),
-                    light_tris_staged=read(3, nl * 36).reshape(nl, 36) if staged else None,
-                    tri_uv=read(4, uv4 * 4, np.float32).reshape(uv4, 4), alpha=read(5, alpha * 8).reshape(alpha * 2, 4))
+        out = dict(levels=head[7:8 + levels].copy(), num_nodes=nodes, num_triangles=nt, group_nodes=group, staged=bool(staged), launches=launches,
+                   vertices=read(1, nv, abi.vertex_dtype), light_tris=read(2, nl * 36).reshape(nl, 36),
+                   light_tris_staged=read(3, nl * 36).reshape(nl, 36) if staged else None,
+                   tri_uv=read(4, uv4 * 4, np.float32).reshape(uv4, 4), alpha=read(5, alpha * 8).reshape(alpha * 2, 4))
+        more = read(6, 48)
+        instanced, top_levels, depth, meshes, instances, top_nodes, mesh_nodes, leaves, _, packets = (int(v) for v in more[:10])
+        out.update(instanced=bool(instanced), leaf_boxes=read(8, leaves * 8, np.float32).reshape(leaves, 2, 4))
+        if instanced:
+            out.update(top_levels=top_levels, mesh_depth=depth, num_meshes=meshes, num_instances=instances, top_nodes=top_nodes,
+                       mesh_levels=more[16:17 + depth].copy(), mesh_level_nodes=read(7, mesh_nodes), mesh_roots=read(9, meshes),
+                       packet_boxes=read(10, packets * 8, np.float32).reshape(packets, 2, 4))
+        return out
 
     def set_camera(self, camera):
         """Replaces the camera of the uploaded scene (slrhip_set_camera; an abi.Camera): later launches see it, nothing is reset."""
@@ -1116,6 +1133,15 @@ def geometry_update_check(have_scene, dynamic, tree_builder, num_instances, num_
     lib = load_library()
     _check(lib, lib.slrhip_debug_geometry_update_check(int(have_scene), int(dynamic), tree_builder, num_instances, num_vertices, device_src, first, count),
            "slrhip_debug_geometry_update_check")
+
+
+def geometry_update_check2(have_scene, dynamic, instanced_kept, tree_builder, num_instances, num_vertices, device_src, first, count):
+    """Diagnostic (slrhip_debug_geometry_update_check2): the same checks for a context that may have been created with
+    abi.FLAG_DYNAMIC_INSTANCED as well (instanced_kept) — the ones Context.set_vertices makes; raises SlrHipError with the call's own
+    message.  No GPU is touched."""
+    lib = load_library()
+    _check(lib, lib.slrhip_debug_geometry_update_check2(int(have_scene), int(dynamic), int(instanced_kept), tree_builder, num_instances, num_vertices,
+                                                        device_src, first, count), "slrhip_debug_geometry_update_check2")
 
 
 def instance_world_box(mesh_lo, mesh_hi, local_to_world):

@@ -501,10 +501,17 @@ int buildInstancedQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, 
     for (const Mesh& mesh : meshes) out->meshBoxes.push_back(mesh.box);
     // the mesh trees go behind the top-level tree in the same arrays; their inner child indices and leaf packets are rebased
     uint32_t maxMeshDepth = 0;
+    std::vector<std::vector<uint32_t>> meshLevels;      // [d]: the rebased nodes of every mesh's level d (a mesh's levels are runs: breadth-first)
     for (size_t m = 0; m < meshes.size(); ++m) {
         const uint32_t nodeBase = (uint32_t)out->nodes.size(), leafBase = (uint32_t)out->leafTris.size();
         if ((uint64_t)leafBase + trees[m].leafTris.size() > kLeafIndexMask) { *err = "too many leaf entries"; return 1; }
         meshes[m].root = nodeBase;
+        const std::vector<uint32_t>& lf = trees[m].levelFirst;
+        if (meshLevels.size() < lf.size()) meshLevels.resize(lf.size());
+        for (size_t d = 0; d < lf.size(); ++d) {
+            const uint32_t end = d + 1 < lf.size() ? lf[d + 1] : (uint32_t)trees[m].nodes.size();
+            for (uint32_t i = lf[d]; i < end; ++i) meshLevels[d].push_back(nodeBase + i);
+        }
         for (QNode qn : trees[m].nodes) {
             for (int c = 0; c < 4; ++c) {
                 if (qn.child[c] == kInvalidChild) continue;
@@ -516,6 +523,13 @@ int buildInstancedQBVH(const slrhip_vertex* verts, const slrhip_triangle* tris, 
         out->leafTris.insert(out->leafTris.end(), trees[m].leafTris.begin(), trees[m].leafTris.end());
         maxMeshDepth = std::max(maxMeshDepth, meshes[m].depth);
     }
+    out->meshLevelNodes.clear(); out->meshLevelFirst.clear(); out->meshRoots.clear();
+    for (const std::vector<uint32_t>& level : meshLevels) {
+        out->meshLevelFirst.push_back((uint32_t)out->meshLevelNodes.size());
+        out->meshLevelNodes.insert(out->meshLevelNodes.end(), level.begin(), level.end());
+    }
+    out->meshLevelFirst.push_back((uint32_t)out->meshLevelNodes.size());
+    for (const Mesh& mesh : meshes) out->meshRoots.push_back(mesh.root);
     out->depth += maxMeshDepth + 1;        // stack entries: the top level's, kPopInstance, the mesh's (slrhip_upload_scene checks 3 x depth + 1 <= 64)
     devInstances->resize(numInstances);
     for (uint32_t k = 0; k < numInstances; ++k) {

@@ -31,6 +31,10 @@ struct QBVH {
     uint32_t topNodes = 0;           // nodes of the top-level tree, which come first in `nodes`
     std::vector<Box> meshBoxes;      // local-space box of each distinct mesh, indexed by DevInstance::mesh
     std::vector<Box> instBoxes;      // world box of each instance (pt_instance.h, instanceWorldBox)
+    // ... and what slrhip_set_vertices refits the mesh trees from: level d of EVERY mesh tree as one run of (rebased) node indices,
+    // meshLevelNodes[meshLevelFirst[d] .. meshLevelFirst[d + 1]); meshLevelFirst has one entry per depth of the deepest mesh, then the
+    // number of mesh nodes.  meshRoots: the root node of each mesh, indexed by DevInstance::mesh.
+    std::vector<uint32_t> meshLevelNodes, meshLevelFirst, meshRoots;
     uint64_t spatialSplits = 0;      // spatial-split build only: splits in space, and leaf references (>= triangles: duplicates)
     uint64_t references = 0;
 };

@@ -1,6 +1,6 @@
 // pt_geometry.h — what slrhip_set_vertices hands its device code (pt_geometry.hip): the kept vertex and index arrays of a context
 // created with SLRHIP_FLAG_DYNAMIC_GEOMETRY and every scene array that depends on vertices, all updated in place.  The range has passed
-// geometryUpdateRefusal (render_plan.h).
+// geometryUpdateRefusal2 (render_plan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,7 +27,18 @@ struct GeometryUpdate {
     float4* nodes;                                         // QNode as 8 x float4
     float4* nodesQ;                                        // QNodeQ as 4 x float4, nullptr unless the quantized nodes are in use
     uint32_t* status;                                      // SLRHIP_GEOMETRY_* bits
-    uint32_t levelFirst[kMaxTreeLevels + 1];               // first node of each level; [numLevels] = numNodes
+    uint32_t levelFirst[kMaxTreeLevels + 1];               // first node of each level; [numLevels] = numNodes (instanced: the TOP level's; = topNodes)
+    // a scene with instances (numInstances != 0): the mesh trees behind the top level, and what slrhip_set_instance_transforms and
+    // slrhip_rebuild_top_level work from
+    uint32_t numInstances, numMeshes, numMeshLevels, numTopPackets;
+    const uint32_t* meshLevelNodes;                        // level d of every mesh tree: entries [meshLevelFirst[d], meshLevelFirst[d + 1])
+    const uint32_t* meshRoots;                             // the root node of each mesh
+    const float4* instances;                               // DevInstance as 9 x float4 (read only: localToWorld, rootNode, mesh)
+    float4* meshBoxes;                                     // 2 x float4 per mesh: lo, hi
+    float4* instBoxes;                                     // 2 x float4 per instance: lo, hi
+    const uint32_t* topPacketRefs;                         // slrhip_rebuild_top_level's canonical child words of the loose packets, or nullptr: no tables yet
+    float4* topPacketBoxes;                                // ... and their boxes, 2 x float4 per packet
+    uint32_t meshLevelFirst[kMaxTreeLevels + 1];           // [numMeshLevels] = the number of mesh nodes
 };
 
 // The launches of one call, in order on `stream`; returns how many there were.

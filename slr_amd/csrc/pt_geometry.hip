@@ -1,4 +1,4 @@
-// pt_geometry.hip — device code of slrhip_set_vertices: new vertices for the uploaded flat scene, and everything that depends on
+// pt_geometry.hip — device code of slrhip_set_vertices: new vertices for the uploaded scene (flat, or with instances), and everything that depends on
 // vertices rebuilt in place from the kept vertex array — the tree keeps its shape and gets exact boxes.  gfx950, wave64.  Launches
 // in stream order (a launch reads what earlier launches stored; nothing is handed between workgroups inside one):
 //
@@ -16,10 +16,23 @@
 //                         consecutive narrower levels is ONE workgroup with a barrier between levels (k_geometry_refit_levels).
 //   k_geometry_quantize   one lane per node: QNodeQ from the refitted float node (pt_quantize.h), when the quantized nodes are in use.
 //
+//
+// A scene with instances (SLRHIP_FLAG_DYNAMIC_INSTANCED as well) runs the same four record kernels — LeafTri records of the top
+// level's loose packets and of every mesh share one array, and a mesh's triangles stay in its local space — and then, instead of
+// k_geometry_refit over one tree:
+//   k_geometry_mesh_refit    ALL mesh trees at once, by the merged level list (level d of every mesh is one run of node indices): the
+//                            same child rule and the same grouping by width, so the launches are bounded by the deepest mesh.
+//   k_geometry_instance_boxes  one lane per instance: its mesh's box = the union of the valid child boxes of the mesh's root, its
+//                            world box = instanceWorldBox of that (pt_instance.h); lanes below the number of meshes store the mesh boxes.
+//   the top-level refit      pt_instances.hip's launchTopRefit, here with the leaf boxes: instance children take the new world boxes,
+//                            loose packets the union of their triangles' boxes.
+//   k_geometry_packet_boxes  where slrhip_rebuild_top_level has built its tables: the loose packets' boxes in its canonical order.
+//
 // No atomics but the status bit, no parent pointers, no flags between workgroups: the order comes from the launches.
 #include <hip/hip_runtime.h>
 
 #include "pt_geometry.h"
+#include "pt_instance.h"
 #include "pt_quantize.h"
 #include "pt_triangle.h"
 
@@ -171,6 +184,88 @@ __global__ __launch_bounds__(kRefitBlock) void k_geometry_refit_levels(GeometryU
     }
 }
 
+// ---- a scene with instances: the mesh trees lie behind the top level, and their levels are the merged list's ----
+
+// One merged level of more than kRefitGroupNodes entries: entries [first, first + count) of the list, four lanes each.
+__global__ __launch_bounds__(kRefitBlock) void k_geometry_mesh_refit(float4* nodes, const float4* leafBoxes, const uint32_t* __restrict__ list, uint32_t first,
+                                                                     uint32_t count, uint32_t numNodes, uint32_t numLeafTris) {
+    const uint32_t t = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (t >= 4u * count) return;
+    const uint32_t node = list[first + (t >> 2)];
+    if (node < numNodes) refitChild(nodes, nullptr, leafBoxes, node, t & 3u, numNodes, 0u, numLeafTris);      // (always: the upload wrote the list)
+}
+
+// Merged levels levelHi, levelHi - 1, .. levelLo, each of at most kRefitGroupNodes entries: one workgroup, a barrier between levels.
+__global__ __launch_bounds__(kRefitBlock) void k_geometry_mesh_refit_levels(GeometryUpdate u, uint32_t levelHi, uint32_t levelLo) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t level = levelHi + 1u; level-- > levelLo;) {                 // uniform over the workgroup: every lane reaches every barrier
+        const uint32_t first = u.meshLevelFirst[level], count = u.meshLevelFirst[level + 1u] - first;
+        if (t < 4u * count) {
+            const uint32_t node = u.meshLevelNodes[first + (t >> 2)];
+            if (node < u.numNodes) refitChild(u.nodes, nullptr, u.leafBoxes, node, t & 3u, u.numNodes, 0u, u.numLeafTris);
+        }
+        __syncthreads();
+    }
+}
+
+// the exact union of the valid child boxes of node `root`: a mesh's local box
+__device__ __forceinline__ void rootBox(const float4* nodes, uint32_t root, float* lo, float* hi) {
+    const float4* n = nodes + (size_t)root * 8u;
+    const float4 p0 = n[0], p1 = n[1], p2 = n[2], p3 = n[3], p4 = n[4], p5 = n[5];
+    const uint4 refs = *reinterpret_cast<const uint4*>(n + 6);
+    lo[0] = unionMin(p0, refs); lo[1] = unionMin(p1, refs); lo[2] = unionMin(p2, refs);
+    hi[0] = unionMax(p3, refs); hi[1] = unionMax(p4, refs); hi[2] = unionMax(p5, refs);
+}
+
+// One lane per instance: its mesh's box from the mesh's refitted root, its world box (pt_instance.h: the upload's arithmetic) from
+// that and its localToWorld.  Lanes k < numMeshes also store mesh k's box (numMeshes <= numInstances: every mesh is placed).  Every
+// lane takes the union it needs itself; no lane reads what another lane of this launch stores.
+__global__ __launch_bounds__(256) void k_geometry_instance_boxes(GeometryUpdate u) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= u.numInstances) return;
+    float lo[3], hi[3];
+    if (k < u.numMeshes) {
+        const uint32_t root = u.meshRoots[k];
+        if (root < u.numNodes) {
+            rootBox(u.nodes, root, lo, hi);
+            u.meshBoxes[2u * (size_t)k] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+            u.meshBoxes[2u * (size_t)k + 1u] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+        }
+    }
+    const float4* rec = u.instances + (size_t)k * 9u;
+    const uint4 tail = *reinterpret_cast<const uint4*>(rec + 8);              // rootNode, firstTriangle, numTriangles, mesh
+    if (tail.x >= u.numNodes) return;                                         // (never: written by the upload)
+    rootBox(u.nodes, tail.x, lo, hi);
+    float m[16];                                                              // localToWorld
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 v = rec[q];
+        m[4 * q] = v.x; m[4 * q + 1] = v.y; m[4 * q + 2] = v.z; m[4 * q + 3] = v.w;
+    }
+    float wlo[3], whi[3];
+    instanceWorldBox(lo, hi, m, wlo, whi);
+    u.instBoxes[2u * (size_t)k] = make_float4(wlo[0], wlo[1], wlo[2], 0.0f);
+    u.instBoxes[2u * (size_t)k + 1u] = make_float4(whi[0], whi[1], whi[2], 0.0f);
+}
+
+// One lane per loose-triangle packet of slrhip_rebuild_top_level's canonical order: the union of its triangles' boxes into the table
+// a later rebuild seats the packet with.
+__global__ __launch_bounds__(256) void k_geometry_packet_boxes(GeometryUpdate u) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= u.numTopPackets) return;
+    const uint32_t ref = u.topPacketRefs[p];
+    const uint32_t count = (ref >> kLeafCountShift) & 0xFu, k = ref & kLeafIndexMask;
+    if (!(ref & kLeafFlag) || ref == kInvalidChild || count == 0u || count > kMaxLeafTris || (uint64_t)k + count > u.numLeafTris) return;      // (never)
+    float4 a = u.leafBoxes[2u * (size_t)k], b = u.leafBoxes[2u * (size_t)k + 1u];
+    for (uint32_t j = 1; j < count; ++j) {
+        const float4 a2 = u.leafBoxes[2u * (size_t)(k + j)], b2 = u.leafBoxes[2u * (size_t)(k + j) + 1u];
+        a.x = fminf(a.x, a2.x); a.y = fminf(a.y, a2.y); a.z = fminf(a.z, a2.z);
+        b.x = fmaxf(b.x, b2.x); b.y = fmaxf(b.y, b2.y); b.z = fmaxf(b.z, b2.z);
+    }
+    u.topPacketBoxes[2u * (size_t)p] = make_float4(a.x, a.y, a.z, 0.0f);
+    u.topPacketBoxes[2u * (size_t)p + 1u] = make_float4(b.x, b.y, b.z, 0.0f);
+}
+
 __global__ __launch_bounds__(256) void k_geometry_quantize(const QNode* __restrict__ nodes, QNodeQ* __restrict__ nodesQ, uint32_t numNodes) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= numNodes) return;
@@ -180,6 +275,34 @@ __global__ __launch_bounds__(256) void k_geometry_quantize(const QNode* __restri
 
 inline dim3 gridOf(uint32_t lanes, uint32_t block) { return dim3((lanes + block - 1u) / block); }
 
+// The refits of a scene with instances, after the records: every mesh tree by merged levels from the deepest to the roots, the meshes'
+// and the instances' boxes, the top level (pt_instances.hip, with the leaf boxes: its loose packets moved too), and the packet boxes of
+// slrhip_rebuild_top_level where its tables exist.  Returns the launches.
+uint32_t launchInstancedRefit(const GeometryUpdate& u, hipStream_t stream) {
+    uint32_t launches = 0;
+    for (uint32_t level = u.numMeshLevels; level-- > 0u;) {
+        const uint32_t first = u.meshLevelFirst[level], count = u.meshLevelFirst[level + 1u] - first;
+        ++launches;
+        if (count > kRefitGroupNodes) {
+            hipLaunchKernelGGL(k_geometry_mesh_refit, gridOf(4u * count, kRefitBlock), dim3(kRefitBlock), 0, stream, u.nodes, u.leafBoxes, u.meshLevelNodes, first,
+                               count, u.numNodes, u.numLeafTris);
+            continue;
+        }
+        uint32_t lo = level;
+        while (lo > 0u && u.meshLevelFirst[lo] - u.meshLevelFirst[lo - 1u] <= kRefitGroupNodes) --lo;
+        hipLaunchKernelGGL(k_geometry_mesh_refit_levels, dim3(1), dim3(kRefitBlock), 0, stream, u, level, lo);
+        level = lo;
+    }
+    hipLaunchKernelGGL(k_geometry_instance_boxes, gridOf(u.numInstances, 256u), dim3(256), 0, stream, u); ++launches;
+    InstanceUpdate top{};                                                     // the refit's part of it
+    top.numInstances = u.numInstances; top.topNodes = u.levelFirst[u.numLevels]; top.numLevels = u.numLevels;
+    top.instBoxes = u.instBoxes; top.leafBoxes = u.leafBoxes; top.numLeafBoxes = u.numLeafTris; top.nodes = u.nodes;
+    for (uint32_t l = 0; l <= u.numLevels; ++l) top.levelFirst[l] = u.levelFirst[l];
+    launches += launchTopRefit(top, stream);
+    if (u.topPacketRefs && u.numTopPackets) { hipLaunchKernelGGL(k_geometry_packet_boxes, gridOf(u.numTopPackets, 256u), dim3(256), 0, stream, u); ++launches; }
+    return launches;
+}
+
 } // namespace
 
 uint32_t launchGeometryUpdate(const GeometryUpdate& u, hipStream_t stream) {
@@ -188,6 +311,7 @@ uint32_t launchGeometryUpdate(const GeometryUpdate& u, hipStream_t stream) {
     hipLaunchKernelGGL(k_geometry_leaves, gridOf(u.numLeafTris, 256u), dim3(256), 0, stream, u); ++launches;
     hipLaunchKernelGGL(k_geometry_triangles, gridOf(u.numTriangles, 256u), dim3(256), 0, stream, u); ++launches;
     if (u.numLights) { hipLaunchKernelGGL(k_geometry_lights, gridOf(u.numLights, 256u), dim3(256), 0, stream, u); ++launches; }
+    if (u.numInstances) return launches + launchInstancedRefit(u, stream);
     // from the deepest level to the root; consecutive levels that fit one workgroup share a launch (as launchInstanceUpdate does)
     for (uint32_t level = u.numLevels; level-- > 0u;) {
         const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;

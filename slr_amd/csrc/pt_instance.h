@@ -61,13 +61,16 @@ struct InstanceUpdate {
     float4* instances;                                     // DevInstance as 9 x float4
     const float4* meshBoxes;                               // 2 x float4 per mesh: lo, hi
     float4* instBoxes;                                     // 2 x float4 per instance: lo, hi
+    const float4* leafBoxes;                               // 2 x float4 per LeafTri record, or nullptr: the loose-triangle packets keep their boxes
+    uint32_t numLeafBoxes;                                 //   (slrhip_set_vertices on a scene with instances gives them: the packets' triangles moved)
     float4* nodes;                                         // the scene's QNodes as 8 x float4; the first topNodes are the top level
     uint32_t* status;                                      // SLRHIP_INSTANCE_* bits
     uint32_t levelFirst[kMaxTopLevels + 1];                // first node of each top-level level; [numLevels] = topNodes
 };
 void launchInstanceUpdate(const InstanceUpdate& u, hipStream_t stream);
 // The refit alone (src, first, count, instances, meshBoxes and status are not read): what slrhip_rebuild_top_level runs after it has
-// seated the leaves (pt_toplevel.hip).  Returns the number of launches.
+// seated the leaves (pt_toplevel.hip), and slrhip_set_vertices after it has refitted the meshes (pt_geometry.hip; with leafBoxes).
+// Returns the number of launches.
 uint32_t launchTopRefit(const InstanceUpdate& u, hipStream_t stream);
 #endif
 

@@ -10,7 +10,8 @@
 //                     slrhip_set_vertices).  One lane per (node, child): an instance child takes its
 //                     instance's world box, an inner child the exact min / max union of the valid child boxes of the node it names
 //                     (six 16-byte loads of that node's planes + one of its references, a horizontal min / max over the valid
-//                     children), a triangle packet and an empty slot keep their bytes.  Six 4-byte stores per lane; the four lanes
+//                     children), a triangle packet keeps its bytes (or, for slrhip_set_vertices, takes the union of its triangles' boxes:
+//                     InstanceUpdate::leafBoxes) and an empty slot keeps its bytes.  Six 4-byte stores per lane; the four lanes
 //                     of a node fill one 16-byte group of each plane.  The named node is on the NEXT level, so a level needs the
 //                     levels below it complete: a level wider than kRefitGroupNodes is a launch of its own, and a run of
 //                     consecutive levels that each fit one workgroup is ONE launch of one workgroup with a barrier between levels
@@ -58,11 +59,11 @@ __global__ __launch_bounds__(256) void k_instance_place(InstanceUpdate u) {
 }
 
 // One level of more than kRefitGroupNodes nodes: nodes [first, first + count), four lanes each.
-__global__ __launch_bounds__(kRefitBlock) void k_top_refit(float4* nodes, const float4* instBoxes, uint32_t first, uint32_t count, uint32_t topNodes,
-                                                           uint32_t numInstances) {
+__global__ __launch_bounds__(kRefitBlock) void k_top_refit(float4* nodes, const float4* instBoxes, const float4* leafBoxes, uint32_t first, uint32_t count,
+                                                           uint32_t topNodes, uint32_t numInstances, uint32_t numLeafBoxes) {
     const uint32_t t = blockIdx.x * kRefitBlock + threadIdx.x;
     if (t >= 4u * count) return;
-    refitChild(nodes, instBoxes, nullptr, first + (t >> 2), t & 3u, topNodes, numInstances, 0u);
+    refitChild(nodes, instBoxes, leafBoxes, first + (t >> 2), t & 3u, topNodes, numInstances, numLeafBoxes);
 }
 
 // Levels levelHi, levelHi - 1, .. levelLo, each of at most kRefitGroupNodes nodes: one workgroup, a barrier between levels.
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(kRefitBlock) void k_top_refit_levels(InstanceUpdate
     const uint32_t t = threadIdx.x;
     for (uint32_t level = levelHi + 1u; level-- > levelLo;) {                 // uniform over the workgroup: every lane reaches every barrier
         const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
-        if (t < 4u * count) refitChild(u.nodes, u.instBoxes, nullptr, first + (t >> 2), t & 3u, u.topNodes, u.numInstances, 0u);
+        if (t < 4u * count) refitChild(u.nodes, u.instBoxes, u.leafBoxes, first + (t >> 2), t & 3u, u.topNodes, u.numInstances, u.numLeafBoxes);
         __syncthreads();
     }
 }
@@ -89,8 +90,8 @@ uint32_t launchTopRefit(const InstanceUpdate& u, hipStream_t stream) {
         ++launches;
         const uint32_t first = u.levelFirst[level], count = u.levelFirst[level + 1u] - first;
         if (count > kRefitGroupNodes) {
-            hipLaunchKernelGGL(k_top_refit, dim3((4u * count + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, stream, u.nodes, u.instBoxes, first, count,
-                               u.topNodes, u.numInstances);
+            hipLaunchKernelGGL(k_top_refit, dim3((4u * count + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, stream, u.nodes, u.instBoxes, u.leafBoxes,
+                               first, count, u.topNodes, u.numInstances, u.numLeafBoxes);
             continue;
         }
         uint32_t lo = level;

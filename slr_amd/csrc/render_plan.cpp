@@ -334,12 +334,17 @@ int topLevelRebuildRefusal(bool haveScene, uint32_t numInstances, const char** w
 
 int geometryUpdateRefusal(bool haveScene, bool dynamic, uint32_t treeBuilder, uint32_t numInstances, uint32_t numVertices, const void* deviceSrc,
                           uint32_t first, uint32_t count, const char** what) {
+    return geometryUpdateRefusal2(haveScene, dynamic, false, treeBuilder, numInstances, numVertices, deviceSrc, first, count, what);
+}
+
+int geometryUpdateRefusal2(bool haveScene, bool dynamic, bool instancedKept, uint32_t treeBuilder, uint32_t numInstances, uint32_t numVertices,
+                           const void* deviceSrc, uint32_t first, uint32_t count, const char** what) {
     if (!deviceSrc) { *what = "null device_src"; return SLRHIP_ERR_INVALID_ARGUMENT; }
     if ((uintptr_t)deviceSrc & 3u) { *what = "misaligned device_src (4 bytes)"; return SLRHIP_ERR_INVALID_ARGUMENT; }
     if (count == 0) { *what = "count must be >= 1"; return SLRHIP_ERR_INVALID_ARGUMENT; }
     if (!haveScene) { *what = "no scene uploaded"; return SLRHIP_ERR_NO_SCENE; }
     if (!dynamic) { *what = "the context was created without SLRHIP_FLAG_DYNAMIC_GEOMETRY"; return SLRHIP_ERR_UNSUPPORTED; }
-    if (numInstances != 0 || treeBuilder == 3u) { *what = "the scene has instances"; return SLRHIP_ERR_UNSUPPORTED; }
+    if ((numInstances != 0 || treeBuilder == 3u) && !instancedKept) { *what = "the scene has instances"; return SLRHIP_ERR_UNSUPPORTED; }
     if (treeBuilder == 1u) { *what = "the tree was built with spatial splits"; return SLRHIP_ERR_UNSUPPORTED; }
     if (first >= numVertices || count > numVertices - first) { *what = "first_vertex + count is beyond the scene's vertices"; return SLRHIP_ERR_INVALID_ARGUMENT; }
     *what = nullptr;

@@ -126,5 +126,10 @@ int topLevelRebuildRefusal(bool haveScene, uint32_t numInstances, const char** w
 // is only compared, never followed): SLRHIP_OK if the call goes ahead, else the code it returns with *what = what is wrong.
 int geometryUpdateRefusal(bool haveScene, bool dynamic, uint32_t treeBuilder, uint32_t numInstances, uint32_t numVertices, const void* deviceSrc,
                           uint32_t first, uint32_t count, const char** what);
+// The same checks for a context that may keep what the call needs of a scene WITH instances (instancedKept: created with
+// SLRHIP_FLAG_DYNAMIC_INSTANCED as well): then instances are no refusal; everything else, and every message, is as above.  This is the
+// one slrhip_set_vertices calls; geometryUpdateRefusal is it with instancedKept = false.
+int geometryUpdateRefusal2(bool haveScene, bool dynamic, bool instancedKept, uint32_t treeBuilder, uint32_t numInstances, uint32_t numVertices,
+                           const void* deviceSrc, uint32_t first, uint32_t count, const char** what);
 
 } // namespace slrhip

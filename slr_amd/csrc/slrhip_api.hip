@@ -173,9 +173,23 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     HIP_TRY(ctx->gridCells.upload(p.gridCells)); HIP_TRY(ctx->pointUV.upload(p.pointUV)); HIP_TRY(ctx->pointSpectrum.upload(p.pointSpectrum));
     // what slrhip_set_vertices works from (SLRHIP_FLAG_DYNAMIC_GEOMETRY; flat scenes whose leaves hold whole triangles): allocated
     // here, so that the call allocates nothing.  Without the flag, nothing.
-    ctx->geometryKept = false;
-    if ((ctx->config.flags & SLRHIP_FLAG_DYNAMIC_GEOMETRY) && p.build != TreeBuild::Instanced && treeBuilderOf(p) != 1u) {
-        if (levelFirst->empty() || levelFirst->size() > kMaxTreeLevels || levelFirst->size() != depth)
+    // A scene with instances is kept only with SLRHIP_FLAG_DYNAMIC_INSTANCED as well: then also the mesh trees' merged level list
+    // and the meshes' roots, and the level table is the top level's.
+    ctx->geometryKept = ctx->geoInstanced = false;
+    const bool dynamic = (ctx->config.flags & SLRHIP_FLAG_DYNAMIC_GEOMETRY) != 0;
+    const bool keepInstanced = dynamic && (ctx->config.flags & SLRHIP_FLAG_DYNAMIC_INSTANCED) && p.build == TreeBuild::Instanced;
+    if (keepInstanced) {
+        const QBVH& t = p.bvh;
+        if (t.meshLevelFirst.size() < 2 || t.meshLevelFirst.size() - 1u > kMaxTreeLevels || t.meshLevelFirst.back() != t.meshLevelNodes.size() ||
+            (size_t)t.topNodes + t.meshLevelNodes.size() != numNodes || t.meshRoots.size() != t.meshBoxes.size() || levelFirst->empty() ||
+            levelFirst->size() > kMaxTreeLevels)
+            return fail(SLRHIP_ERR_HIP, "slrhip_upload_scene: the mesh trees have no level list (internal error)");
+        HIP_TRY(ctx->geoMeshLevelNodes.upload(t.meshLevelNodes));
+        HIP_TRY(ctx->geoMeshRoots.upload(t.meshRoots));
+        ctx->geoMeshLevelFirst = t.meshLevelFirst;
+    }
+    if (keepInstanced || (dynamic && p.build != TreeBuild::Instanced && treeBuilderOf(p) != 1u)) {
+        if (!keepInstanced && (levelFirst->empty() || levelFirst->size() > kMaxTreeLevels || levelFirst->size() != depth))
             return fail(SLRHIP_ERR_HIP, "slrhip_upload_scene: the tree has no level table (internal error)");
         HIP_TRY(ctx->geoVertices.alloc(d.num_vertices));
         HIP_TRY(hipMemcpy(ctx->geoVertices.ptr, d.vertices, (size_t)d.num_vertices * sizeof(slrhip_vertex), hipMemcpyHostToDevice));
@@ -185,7 +199,8 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
         HIP_TRY(ctx->geometryStatus.alloc(1));
         HIP_TRY(hipMemset(ctx->geometryStatus.ptr, 0, sizeof(uint32_t)));
         ctx->geoLevelFirst = *levelFirst;
-        ctx->geoLevelFirst.push_back(numNodes);
+        ctx->geoLevelFirst.push_back(keepInstanced ? p.bvh.topNodes : numNodes);
+        ctx->geoInstanced = keepInstanced;
         ctx->geoNumVertices = d.num_vertices; ctx->geoNumTriangles = d.num_triangles; ctx->geoNumLights = (uint32_t)p.lightTris.size();
         ctx->geoNumAlphaRecords = (uint32_t)(p.alphaTris.size() / 2u); ctx->geoHasTriUV = !p.triUV.empty();
         ctx->geoLastLaunches = 0;

@@ -129,6 +129,12 @@ struct slrhip_ctx {
     uint32_t geoNumVertices = 0, geoNumTriangles = 0, geoNumLights = 0, geoNumAlphaRecords = 0;
     bool geoHasTriUV = false;
     uint32_t geoLastLaunches = 0;                 // launches of the last slrhip_set_vertices call (slrhip_debug_geometry's summary)
+    // ... and of a scene WITH instances (contexts created with SLRHIP_FLAG_DYNAMIC_INSTANCED as well): geoInstanced, geoLevelFirst is
+    // the top level's table (topLevelFirst), and the mesh trees' merged level list (bvh.h: QBVH::meshLevelNodes / meshLevelFirst) and
+    // each mesh's root node are kept on the device.  The boxes the call rewrites are meshBoxes and instBoxes above.
+    bool geoInstanced = false;
+    DevArray<uint32_t> geoMeshLevelNodes, geoMeshRoots;
+    std::vector<uint32_t> geoMeshLevelFirst;
     DevArray<slrhip::DevMaterial> materials;
     DevArray<slrhip::DevMaterialS> materialsS;
     DevArray<slrhip::DevSpectrum> spectra;

@@ -2,8 +2,10 @@
 the tree refitted there) next to the only route there was before it, a full slrhip_upload_scene; and what the refitted tree costs the
 rays.
 
-One scene per run (--scene grid: scenes.displaced_grid, 10 M triangles; --scene cornell: the bench scene) with one tree builder
-(--tree device | host; SLRHIP_BVH is set before the library loads, so a run measures one builder).
+One scene per run (--scene grid: scenes.displaced_grid, 10 M triangles; --scene cornell: the bench scene; --scene instanced:
+scenes.instanced_grid, --tiles-x x --tiles-z placements of one patch of 2 x --cells^2 triangles, in a context created with
+FLAG_DYNAMIC_INSTANCED as well — the two-level host build, whatever --tree says) with one tree builder (--tree device | host; SLRHIP_BVH is
+set before the library loads, so a run measures one builder).
   (a) milliseconds per call on the whole vertex array: --batch calls back to back on one stream between two HIP events
       (torch.cuda.Event) and a stream synchronise, divided by the batch; one warm-up batch, the median, fastest and slowest of --reps
       batches; the launches per call.  Beside it, same box and same run: slrhip_counters::build_seconds of an upload of the same
@@ -11,7 +13,8 @@ One scene per run (--scene grid: scenes.displaced_grid, 10 M triangles; --scene 
   (b) traversal nodes per ray (a context with SLRHIP_FLAG_COUNT_TRAVERSAL) as uploaded, after an identity update (the tree is the
       same: the counts must be equal), after `perturb` (every vertex displaced by up to half a cell, seeded) refitted, and after a
       fresh upload of the perturbed scene, which is the remedy.  Frames of the refitted and the freshly uploaded context are compared
-      bit for bit.
+      bit for bit.  render_ms is the host clock around that render in the COUNTING context (slower than a plain one; comparable among
+      the states of one run only).
 Appends one JSON line to <out-dir>/vertex_update_rate.txt (a) and one to <out-dir>/vertex_update_tree_quality.txt (b)."""
 import argparse
 import json
@@ -31,9 +34,12 @@ def spread(values):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="grid", choices=["grid", "cornell"])
+    ap.add_argument("--scene", default="grid", choices=["grid", "cornell", "instanced"])
     ap.add_argument("--tree", default="device", choices=["device", "host"])
     ap.add_argument("--grid-n", type=int, default=2236)
+    ap.add_argument("--tiles-x", type=int, default=25)
+    ap.add_argument("--tiles-z", type=int, default=50)
+    ap.add_argument("--cells", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--uploads", type=int, default=2)
@@ -52,16 +58,23 @@ def main():
     if args.scene == "grid":
         sc = scenes.displaced_grid(args.grid_n, aspect)
         reach = 0.5 * 8.0 / args.grid_n           # half a cell of the grid (extent 4)
+    elif args.scene == "instanced":
+        sc = scenes.instanced_grid(args.tiles_x, args.tiles_z, args.cells, aspect)
+        reach = 0.5 * 2.0 / args.cells            # half a cell of the patch (local extent 2)
     else:
         sc = scenes.cornell_box_spheres(aspect, 48, 24, "matte")
         reach = 0.01
     st = ob.settings(args.width, args.height, seed=11)
     flags = abi.FLAG_DYNAMIC_GEOMETRY | (abi.FLAG_BVH_DEVICE_BUILD if args.tree == "device" else 0)
+    if args.scene == "instanced":
+        flags = abi.FLAG_DYNAMIC_GEOMETRY | abi.FLAG_DYNAMIC_INSTANCED
     n = len(sc.vertices)
     moved = sc.vertices.copy()
     moved["position"] = (moved["position"].astype(np.float64) + np.random.default_rng(5).uniform(-reach, reach, (n, 3))).astype(np.float32)
-    sc_moved = abi.Scene(moved, sc.triangles, sc.materials, sc.spectra, sc.spectrum_data, sc.camera, None, sc.name + "_perturbed")
-    head = dict(scene=sc.name, tree=args.tree, vertices=n, triangles=len(sc.triangles), reps=args.reps, warmup=1, batch=args.batch)
+    sc_moved = abi.Scene(moved, sc.triangles, sc.materials, sc.spectra, sc.spectrum_data, sc.camera, None, sc.name + "_perturbed",
+                         instances=sc.instances if len(sc.instances) else None)
+    head = dict(scene=sc.name, tree=args.tree, vertices=n, triangles=len(sc.triangles), instances=len(sc.instances), reps=args.reps, warmup=1,
+                batch=args.batch)
 
     # (a) the call, next to the upload
     ctx = Context(flags=flags)
@@ -94,6 +107,9 @@ def main():
     geo_levels = ctx.debug_geometry()
     rate["launches_per_call"] = geo_levels["launches"]
     rate["level_widths"] = np.diff(geo_levels["levels"]).tolist()
+    if geo_levels["instanced"]:
+        rate["mesh_level_widths"] = np.diff(geo_levels["mesh_levels"]).tolist()
+        rate["meshes"] = geo_levels["num_meshes"]
     # the bytes one call must move: the caller's records in and the kept ones out, the indices, and every rewritten record in and out
     nt, nn = len(sc.triangles), tree["num_nodes"]
     rate["bytes_per_call"] = int(n * 88 + nt * (16 * 2 + 48 * 2 + 32 * 2 + 96 * 2 + 3 * 44 * 2) + nn * (128 * 2 + (64 if tree["quantized"] else 0)))
@@ -108,9 +124,12 @@ def main():
     # (b) what the refitted tree costs the rays
     def nodes_per_ray(c):
         c.render_begin(st)
+        t0 = time.perf_counter()
         c.render(0, args.spp)
+        c.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
         p = c.profile()
-        return dict(closest=p.nodes[0] / max(1, p.rays[0]), shadow=p.nodes[1] / max(1, p.rays[1]), nodes=[int(p.nodes[0]), int(p.nodes[1])],
+        return dict(render_ms=ms, closest=p.nodes[0] / max(1, p.rays[0]), shadow=p.nodes[1] / max(1, p.rays[1]), nodes=[int(p.nodes[0]), int(p.nodes[1])],
                     rays=[int(p.rays[0]), int(p.rays[1])]), c.read_framebuffer()
 
     count = Context(flags=flags | abi.FLAG_COUNT_TRAVERSAL)
