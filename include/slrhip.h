@@ -665,7 +665,8 @@ int slrhip_read_albedo(slrhip_ctx* ctx, float* host_dst, size_t num_floats, uint
  * previous_transforms, previous_transforms on a scene without instances, a pass range beyond 2^32, a null or misaligned (4 bytes)
  * destination or too little room; SLRHIP_ERR_NO_SCENE before slrhip_render_begin; spp_count == 0 does nothing.
  * Not covered: the environment under camera rotation (a miss has no vector); motion of loose triangles (they are taken to stand
- * still; only instances and the camera move); depth of field (the projection goes through the lens centre).                          */
+ * still; only instances and the camera move — vertices moved by slrhip_set_vertices, of loose triangles and of meshes alike, are
+ * covered by slrhip_render_motion_vertices below); depth of field (the projection goes through the lens centre).                    */
 struct slrhip_instance_transform;                                    /* defined below, with slrhip_set_instance_transforms */
 typedef struct slrhip_motion_desc {
     const slrhip_camera* previous_camera;                           /* HOST; NULL = the camera did not move */
@@ -691,6 +692,58 @@ int slrhip_motion_camera(const slrhip_camera* camera, float out[24]);
  * sample, {0, 0, 0, 0} for one that is not.  SLRHIP_ERR_INVALID_ARGUMENT for a null camera, P or out.                                */
 int slrhip_motion_sample(const slrhip_camera* now_camera, const slrhip_camera* prev_camera, const float* now_record, const float* prev_record,
                          uint32_t width, uint32_t height, const float P[3], float out[4]);
+
+/* ---- motion vectors of moved vertices: the caller also names the previous frame's vertices ----------------------------------------
+ * slrhip_render_motion takes vertices to stand still.  A caller who deforms a mesh with slrhip_set_vertices (below) names the vertices
+ * of the previous frame here, beside the previous camera and placements of `frame`.  The call adds into the SAME per-pixel sums as
+ * slrhip_render_motion (read by slrhip_resolve_motion / slrhip_read_motion) and keeps that call's contract in full: stateless;
+ * stream-ordered and non-blocking; the first motion call after a slrhip_render_begin allocates and may MOVE the shared record window
+ * (this call's window also keeps the second barycentric: 20 B per (pixel, pass), at most 64 passes; the first call of EACH of the two
+ * kinds may move it), later calls allocate nothing and may be captured; the same independence of shards, cuts, colour mode and
+ * interleaved calls; ALL motion calls of one render, of either kind, name ONE previous frame.  `previous_vertices` is read in order
+ * on `stream` and is free once the stream has passed the call.
+ *
+ * With previous_vertices == NULL the call IS slrhip_render_motion(ctx, &desc->frame, ...): the same path, the same kernel, bit for bit,
+ * in any context.
+ *
+ * The definition of a sample when previous_vertices is given (float32, every operation IEEE-rounded on its own, no fused multiply-add;
+ * stated once for host and device in slr_amd/csrc/pt_motion.h, motionSampleVertices):
+ *   Hit:        the feature pass's hit record of that (pixel, pass): triangle t, instance, and Moller-Trumbore's barycentrics b1 (on
+ *               the triangle's second vertex) and b2 (on its third).  A miss adds nothing.
+ *   b0:         b0 = (1.0f - b1) - b2.
+ *   Vertices:   (i0, i1, i2) = the context's kept index array at t; p_k = the position of vertex i_k in the kept vertex array AS IT NOW
+ *               STANDS (after every slrhip_set_vertices ordered before the call); q_k = the position of vertex i_k in previous_vertices.
+ *   Local:      per component l_now = (b0 * p0 + b1 * p1) + b2 * p2 and l_prev = (b0 * q0 + b1 * q1) + b2 * q2: one expression on two
+ *               sets of operands, so where the two arrays are bit-equal the two points are, and with equal matrices and cameras the
+ *               motion is exactly 0.0f, with no special case.  The camera ray is not rebuilt: org + dist * dir is not used here.
+ *   Placements: an instanced hit: P_now = mulPoint(local_to_world_now, l_now), P_prev = mulPoint(local_to_world_prev, l_prev), the
+ *               previous record being the current one when frame.previous_transforms is NULL; a loose triangle: P_now = l_now,
+ *               P_prev = l_prev.  (A mesh's vertices are in its local space, as the upload stores them.)
+ *   Result:     proj, validity, m, z' and the sums exactly as above.  A previous position that is not finite makes the sample INVALID:
+ *               it adds nothing, and the sums stay finite.
+ *
+ * Errors, synchronous, with nothing changed: everything slrhip_render_motion refuses for `frame`; SLRHIP_ERR_INVALID_ARGUMENT for a
+ * null descriptor, a nonzero outer `reserved` or a previous_vertices misaligned to 4 bytes; SLRHIP_ERR_UNSUPPORTED for
+ * previous_vertices in a context that does not keep the vertex and index arrays — one created without SLRHIP_FLAG_DYNAMIC_GEOMETRY, a
+ * scene with instances in one created without SLRHIP_FLAG_DYNAMIC_INSTANCED (the message names the missing flag), a tree built with
+ * spatial splits.  The library CANNOT check how long the caller's array is: it must hold all slrhip_scene_desc::num_vertices records.
+ * Not covered: vertex normals and shading of the previous frame, motion of the environment, depth of field, the C++ host mirror, the
+ * libSLR adapter and bench.py.                                                                                                       */
+typedef struct slrhip_motion_vertices_desc {
+    slrhip_motion_desc frame;                  /* exactly as for slrhip_render_motion (reserved 0)                       */
+    const slrhip_vertex* previous_vertices;    /* DEVICE, 4-byte aligned, ALL num_vertices records of the scene in order,
+                                                  as the previous frame had them; only `position` is read.
+                                                  NULL = no vertex moved                                                    */
+    uint64_t reserved;                         /* 0 */
+} slrhip_motion_vertices_desc;
+int slrhip_render_motion_vertices(slrhip_ctx* ctx, const slrhip_motion_vertices_desc* desc, uint32_t spp_begin, uint32_t spp_count, void* stream);
+/* One sample of that definition through the function the kernel calls (pt_motion.h), on the HOST (pure).  Cameras, records, width,
+ * height and out as for slrhip_motion_sample (only local_to_world is read of a record).  now_positions / prev_positions: x, y, z of the
+ * hit triangle's first, second and third vertex, now and in the previous frame; b1, b2: the hit's barycentrics.
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null camera, position array or out.                                                              */
+int slrhip_motion_sample_vertices(const slrhip_camera* now_camera, const slrhip_camera* prev_camera, const float* now_record, const float* prev_record,
+                                  uint32_t width, uint32_t height, const float now_positions[9], const float prev_positions[9], float b1, float b2,
+                                  float out[4]);
 
 /* The per-(pixel, sample) seeding contract (pure function, also used by the oracle).      */
 int32_t slrhip_sample_seed(int32_t rng_seed, uint32_t pixel_x, uint32_t pixel_y, uint32_t pass);
@@ -1433,8 +1486,8 @@ int slrhip_save_bmp(const char* path, const uint8_t* bgr_bottom_up, int32_t widt
  *
  * Not covered: spatial-split trees; adding or removing vertices, triangles or instances; changing indices or materials; a change
  * of SHAPE of either tree level (slrhip_rebuild_top_level re-seats the top level's leaves, nothing rebuilds a mesh tree: the caller
- * uploads again when a tree has degraded); instances that emit; motion vectors of moved vertices (slrhip_render_motion still takes
- * vertices to stand still); the C++ host mirror and the libSLR adapter.                                                             */
+ * uploads again when a tree has degraded); instances that emit; the C++ host mirror and the libSLR adapter.  Motion vectors of moved vertices: slrhip_render_motion
+ * takes vertices to stand still; slrhip_render_motion_vertices takes the previous frame's vertex array and covers them.            */
 #define SLRHIP_GEOMETRY_BAD_VERTEX 1u      /* a record of a call had a non-finite float; its vertex did not move */
 int slrhip_set_vertices(slrhip_ctx* ctx, const slrhip_vertex* device_src, uint32_t first_vertex, uint32_t count, void* stream);
 /* The SLRHIP_GEOMETRY_* bits of the calls since the last read, then cleared; waits for `stream`.  0 before any scene.              */

@@ -76,6 +76,12 @@ int slrhip_debug_reproject_check(const slrhip_reproject_desc* desc);
  * pointers are only compared, never followed.  No GPU is touched.                                                                   */
 int slrhip_debug_motion_check(int32_t have_render, uint32_t num_instances, const slrhip_motion_desc* desc, uint32_t spp_begin, uint32_t spp_count);
 
+/* The same for slrhip_render_motion_vertices (motionVerticesRefusal), for a context created with slrhip_config::flags `config_flags`
+ * whose tree came from builder `tree_builder` (SLRHIP_TREE_*, below): the outer descriptor's checks, those of its `frame`, and — where
+ * previous_vertices is given — whether such a context keeps the vertex and index arrays.  No GPU is touched.                        */
+int slrhip_debug_motion_vertices_check(int32_t have_render, uint32_t num_instances, uint32_t config_flags, uint32_t tree_builder,
+                                       const slrhip_motion_vertices_desc* desc, uint32_t spp_begin, uint32_t spp_count);
+
 /* The argument checks of slrhip_set_environment on a descriptor (slr_amd/csrc/render_plan.h, environmentRefusal), evaluated on the HOST
  * with the function the entry point calls: SLRHIP_OK if the descriptor would pass, else SLRHIP_ERR_INVALID_ARGUMENT with the reason in
  * slrhip_last_error_string.  The pointer is only compared, never followed.  No GPU is touched.                                      */

@@ -205,6 +205,12 @@ class MotionDesc(C.Structure):
     _fields_ = [("previous_camera", C.POINTER(Camera)), ("previous_transforms", C.c_void_p), ("reserved", C.c_uint32 * 2)]
 
 
+class MotionVerticesDesc(C.Structure):
+    """slrhip_motion_vertices_desc: `frame` as for slrhip_render_motion; previous_vertices a DEVICE pointer (an integer address; None: no
+    vertex moved) to ALL slrhip_vertex records of the scene as the previous frame had them."""
+    _fields_ = [("frame", MotionDesc), ("previous_vertices", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 # Context.reproject's defaults: the history is capped at 32 frames; a tap is taken if its distance is within 10 % of the expected one
 # and its normal within about 25 degrees of the pixel's
 REPROJECT_MAX_HISTORY, REPROJECT_SIGMA_DISTANCE, REPROJECT_MIN_NORMAL_DOT = 32.0, 0.1, 0.9

@@ -27,6 +27,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_debug_top_level_plan", "slrhip_debug_top_level_reseat", "slrhip_debug_top_level_cost", "slrhip_debug_top_level_rebuild",
            "slrhip_render_motion", "slrhip_resolve_motion", "slrhip_read_motion", "slrhip_motion_camera", "slrhip_motion_sample", "slrhip_reproject",
            "slrhip_debug_motion_check", "slrhip_debug_reproject_check",
+           "slrhip_render_motion_vertices", "slrhip_motion_sample_vertices", "slrhip_debug_motion_vertices_check",
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
@@ -165,6 +166,14 @@ def load_library():
                            ("slrhip_reproject", [C.c_void_p, C.POINTER(abi.ReprojectDesc), C.c_void_p]),
                            ("slrhip_debug_motion_check", [C.c_int32, C.c_uint32, C.POINTER(abi.MotionDesc), C.c_uint32, C.c_uint32]),
                            ("slrhip_debug_reproject_check", [C.POINTER(abi.ReprojectDesc)])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
+    # (and one from before motion vectors of moved vertices lacks these three)
+    for name, argtypes in (("slrhip_render_motion_vertices", [C.c_void_p, C.POINTER(abi.MotionVerticesDesc), C.c_uint32, C.c_uint32, C.c_void_p]),
+                           ("slrhip_motion_sample_vertices", [C.POINTER(abi.Camera), C.POINTER(abi.Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                              C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+                           ("slrhip_debug_motion_vertices_check", [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(abi.MotionVerticesDesc),
+                                                                   C.c_uint32, C.c_uint32])):
         if path == LIB_PATH or hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     # (and one from before the tree read-outs lacks these three)
@@ -691,37 +700,56 @@ class Context:
         return self._read_frame("slrhip_read_albedo", C.byref(passes)), passes.value
 
     # ---- motion vectors (slrhip_render_motion / slrhip_resolve_motion / slrhip_read_motion) ----
-    def render_motion(self, spp, previous_camera=None, previous_transforms=None, spp_begin=0, stream=None):
+    def render_motion(self, spp, previous_camera=None, previous_transforms=None, spp_begin=0, stream=None, previous_vertices=None):
         """Motion passes [spp_begin, spp_begin + spp) of every pixel of the shard (slrhip_render_motion): where on the PREVIOUS frame's
         image was the point each sample's camera ray hits now?  previous_camera: the abi.Camera of the previous frame (None: the
         camera did not move; taken by value).  previous_transforms: the matrices ALL instances had in the previous frame (None: no
         instance moved) — a numpy [n, 32] float32 array (or abi.instance_transform_dtype / abi.instance_dtype records), copied to
         the device first (that call synchronises); or a contiguous [n, 32] float32 torch CUDA tensor or a device address (int), read
-        in order on `stream` without a copy.  Every call between two render_begin calls must name the same previous frame."""
+        in order on `stream` without a copy.  previous_vertices: ALL vertices of the scene as the previous frame had them (None: no
+        vertex moved); given, the call goes to slrhip_render_motion_vertices (contexts that keep the vertex array: set_vertices) —
+        numpy records of abi.vertex_dtype or an [n, 11] float32 array, staged like previous_transforms; or a contiguous [n, 11] float32
+        torch CUDA tensor or a device address (int).  Every call between two render_begin calls must name the same previous frame."""
         cam = C.pointer(previous_camera) if previous_camera is not None else None
+        handle = self._stream_handle(stream)
 
-        def call(ptr):
-            d = abi.MotionDesc(cam, ptr, (C.c_uint32 * 2)(0, 0))
-            _check(self.lib, self.lib.slrhip_render_motion(self.handle, C.byref(d), spp_begin, spp, self._stream_handle(stream)), "slrhip_render_motion")
-        if isinstance(previous_transforms, np.ndarray):
-            a = previous_transforms
-            if a.dtype == abi.instance_dtype:
-                a = np.concatenate([a["local_to_world"], a["world_to_local"]], axis=1)
-            elif a.dtype == abi.instance_transform_dtype:
-                a = np.ascontiguousarray(a).view(np.float32)
-            a = np.ascontiguousarray(a, np.float32).reshape(-1, 32)
-            with DeviceBlocks() as dev:
-                call(dev.put(a))
-                self.synchronize()                     # the staging block is freed on the way out
-            return
-        if previous_transforms is not None and not isinstance(previous_transforms, int):
-            t = previous_transforms
-            if not (t.is_cuda and t.dim() == 2 and t.shape[1] == 32 and t.is_contiguous() and t.element_size() == 4 and t.is_floating_point()):
-                raise ValueError("previous_transforms: a contiguous [n, 32] float32 CUDA tensor, a numpy array or a device address expected")
+        def device_address(t, columns, what):
+            if t is None or isinstance(t, int):
+                return t
+            if not (t.is_cuda and t.dim() == 2 and t.shape[1] == columns and t.is_contiguous() and t.element_size() == 4 and t.is_floating_point()):
+                raise ValueError("%s: a contiguous [n, %d] float32 CUDA tensor, a numpy array or a device address expected" % (what, columns))
             if t.device.index != self.device:
                 raise SlrHipError("render_motion: the tensor is on device %r, the context on device %d" % (t.device.index, self.device))
-            previous_transforms = t.data_ptr()
-        call(previous_transforms)
+            return t.data_ptr()
+
+        host = [a for a in (previous_transforms, previous_vertices) if isinstance(a, np.ndarray)]
+        if not host:
+            return self._render_motion(cam, device_address(previous_transforms, 32, "previous_transforms"),
+                                       device_address(previous_vertices, 11, "previous_vertices"), spp_begin, spp, handle)
+        with DeviceBlocks() as dev:
+            if isinstance(previous_transforms, np.ndarray):
+                a = previous_transforms
+                if a.dtype == abi.instance_dtype:
+                    a = np.concatenate([a["local_to_world"], a["world_to_local"]], axis=1)
+                elif a.dtype == abi.instance_transform_dtype:
+                    a = np.ascontiguousarray(a).view(np.float32)
+                previous_transforms = dev.put(np.ascontiguousarray(a, np.float32).reshape(-1, 32))
+            if isinstance(previous_vertices, np.ndarray):
+                a = np.ascontiguousarray(previous_vertices)
+                a = a.view(np.float32) if a.dtype == abi.vertex_dtype else np.ascontiguousarray(a, np.float32)
+                previous_vertices = dev.put(a.reshape(-1, 11))
+            self._render_motion(cam, device_address(previous_transforms, 32, "previous_transforms"),
+                                device_address(previous_vertices, 11, "previous_vertices"), spp_begin, spp, handle)
+            self.synchronize()                         # the staging blocks are freed on the way out
+
+    def _render_motion(self, cam, transforms, vertices, spp_begin, spp, handle):
+        """The call on device addresses: slrhip_render_motion, or slrhip_render_motion_vertices where `vertices` is given."""
+        frame = abi.MotionDesc(cam, transforms, (C.c_uint32 * 2)(0, 0))
+        if vertices is None:
+            _check(self.lib, self.lib.slrhip_render_motion(self.handle, C.byref(frame), spp_begin, spp, handle), "slrhip_render_motion")
+        else:
+            d = abi.MotionVerticesDesc(frame, vertices, 0)
+            _check(self.lib, self.lib.slrhip_render_motion_vertices(self.handle, C.byref(d), spp_begin, spp, handle), "slrhip_render_motion_vertices")
 
     def motion_into(self, device_ptr, num_floats, stream=None):
         """The motion SUMS into device memory at `device_ptr` ([height, width, 4] float32; slrhip_resolve_motion), ordered on `stream`."""
@@ -1249,6 +1277,20 @@ def motion_sample(now_camera, prev_camera, now_record, prev_record, width, heigh
     if lib.slrhip_motion_sample(C.byref(now_camera), C.byref(prev_camera), *(None if r is None else r.ctypes.data for r in recs), width, height,
                                 p.ctypes.data, out.ctypes.data) != 0:
         raise ValueError("motion_sample: refused")
+    return out
+
+
+def motion_sample_vertices(now_camera, prev_camera, now_record, prev_record, width, height, now_positions, prev_positions, b1, b2):
+    """One sample's motion vector where the vertices moved as well, on the host, with the function the kernel calls
+    (slrhip_motion_sample_vertices): the records as for motion_sample; now_positions / prev_positions [3, 3] the positions of the hit
+    triangle's vertices now and in the previous frame; b1, b2 the hit's barycentrics; float32 [4] as motion_sample's."""
+    lib = load_library()
+    recs = [None if r is None else np.ascontiguousarray(r, np.float32).reshape(32) for r in (now_record, prev_record)]
+    pn, pp = (np.ascontiguousarray(p, np.float32).reshape(9) for p in (now_positions, prev_positions))
+    out = np.zeros(4, np.float32)
+    if lib.slrhip_motion_sample_vertices(C.byref(now_camera), C.byref(prev_camera), *(None if r is None else r.ctypes.data for r in recs), width, height,
+                                         pn.ctypes.data, pp.ctypes.data, float(b1), float(b2), out.ctypes.data) != 0:
+        raise ValueError("motion_sample_vertices: refused")
     return out
 
 

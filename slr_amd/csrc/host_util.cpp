@@ -339,6 +339,17 @@ int slrhip_motion_sample(const slrhip_camera* nowCamera, const slrhip_camera* pr
     return SLRHIP_OK;
 }
 
+// The same where the vertices moved as well (slrhip_render_motion_vertices; pt_motion.h: the function k_motion_fold<true> calls).
+int slrhip_motion_sample_vertices(const slrhip_camera* nowCamera, const slrhip_camera* prevCamera, const float* nowRecord, const float* prevRecord,
+                                  uint32_t width, uint32_t height, const float* nowPositions, const float* prevPositions, float b1, float b2, float* out) {
+    if (!nowCamera || !prevCamera || !nowPositions || !prevPositions || !out) return SLRHIP_ERR_INVALID_ARGUMENT;
+    slrhip::MotionCamera now, prev;
+    if (slrhip_motion_camera(nowCamera, reinterpret_cast<float*>(&now)) || slrhip_motion_camera(prevCamera, reinterpret_cast<float*>(&prev)))
+        return SLRHIP_ERR_INVALID_ARGUMENT;
+    slrhip::motionSampleVertices(now, prev, nowRecord, prevRecord, width, height, nowPositions, prevPositions, b1, b2, out);
+    return SLRHIP_OK;
+}
+
 // (r, g, b) -> (u, v, s) per texel, as halves (pt_envmap.h: the function k_env_store calls).  In place is fine: a texel is read whole first.
 int slrhip_env_texels_to_uvs(const float* rgb, size_t numTexels, float* uvs) {
     if (!rgb || !uvs) return SLRHIP_ERR_INVALID_ARGUMENT;

@@ -303,6 +303,31 @@ int motionRefusal(bool haveRender, uint32_t numInstances, const slrhip_motion_de
     return SLRHIP_OK;
 }
 
+static_assert(sizeof(slrhip_motion_vertices_desc) == 40 && offsetof(slrhip_motion_vertices_desc, frame) == 0 &&
+              offsetof(slrhip_motion_vertices_desc, previous_vertices) == 24 && offsetof(slrhip_motion_vertices_desc, reserved) == 32,
+              "slrhip_motion_vertices_desc's layout");
+
+int motionVerticesRefusal(bool haveRender, uint32_t numInstances, uint32_t flags, uint32_t treeBuilder, const slrhip_motion_vertices_desc* d,
+                          uint32_t sppBegin, uint32_t sppCount, const char** what) {
+    *what = nullptr;
+    if (!d) { *what = "null descriptor"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (d->reserved != 0) { *what = "reserved must be 0"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if ((uintptr_t)d->previous_vertices & 3u) { *what = "misaligned previous_vertices (4 bytes)"; return SLRHIP_ERR_INVALID_ARGUMENT; }
+    if (const int rc = motionRefusal(haveRender, numInstances, &d->frame, sppBegin, sppCount, what)) return rc;
+    if (!d->previous_vertices) return SLRHIP_OK;
+    // the context keeps the vertex and index arrays exactly where slrhip_set_vertices works (geometryUpdateRefusal2)
+    if (!(flags & SLRHIP_FLAG_DYNAMIC_GEOMETRY)) {
+        *what = "previous_vertices given, but the context was created without SLRHIP_FLAG_DYNAMIC_GEOMETRY";
+        return SLRHIP_ERR_UNSUPPORTED;
+    }
+    if ((numInstances != 0 || treeBuilder == 3u) && !(flags & SLRHIP_FLAG_DYNAMIC_INSTANCED)) {
+        *what = "previous_vertices given, but the scene has instances and the context was created without SLRHIP_FLAG_DYNAMIC_INSTANCED";
+        return SLRHIP_ERR_UNSUPPORTED;
+    }
+    if (treeBuilder == 1u) { *what = "previous_vertices given, but the tree was built with spatial splits"; return SLRHIP_ERR_UNSUPPORTED; }
+    return SLRHIP_OK;
+}
+
 const char* environmentRefusal(const slrhip_environment_desc& d) {
     if (d.reserved[0] != 0 || d.reserved[1] != 0) return "reserved must be 0";
     if (d.flags & ~(SLRHIP_ENV_TEXELS_RGB | SLRHIP_ENV_STORE_HALF)) return "unknown flag bits";

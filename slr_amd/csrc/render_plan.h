@@ -112,6 +112,11 @@ const char* reprojectRefusal(const slrhip_reproject_desc& d);
 // the pointers are only compared, never followed, `d` may be null): SLRHIP_OK if the call goes ahead, else the code it returns with
 // *what = what is wrong.
 int motionRefusal(bool haveRender, uint32_t numInstances, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, const char** what);
+// The argument checks of slrhip_render_motion_vertices: the outer descriptor's own, then motionRefusal on its `frame`, then — only where
+// previous_vertices is given — whether the context keeps the vertex and index arrays (flags: its slrhip_config::flags; treeBuilder: the
+// builder behind the scene's tree as include/slrhip_debug.h numbers them).  Codes and *what as above.
+int motionVerticesRefusal(bool haveRender, uint32_t numInstances, uint32_t flags, uint32_t treeBuilder, const slrhip_motion_vertices_desc* d,
+                          uint32_t sppBegin, uint32_t sppCount, const char** what);
 // The argument checks of slrhip_set_environment on the descriptor (the pointer is only compared, never followed): nullptr if the
 // call goes ahead, else what is wrong with it.  What depends on the context (no scene, no upsampling tables) is the entry point's.
 const char* environmentRefusal(const slrhip_environment_desc& d);

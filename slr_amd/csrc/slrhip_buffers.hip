@@ -286,32 +286,38 @@ int slrhip_read_albedo(slrhip_ctx* ctx, float* hostDst, size_t numFloats, uint32
     return readThroughScratch(ctx, hostDst, need, need, true, "slrhip_read_albedo", [&](float* scratch) { return slrhip_resolve_albedo(ctx, scratch, need, passes, nullptr); });
 }
 
-// ---- the motion buffer (slrhip_render_motion / slrhip_resolve_motion / slrhip_read_motion) -------------------------------------------
+// ---- the motion buffer (slrhip_render_motion / slrhip_render_motion_vertices / slrhip_resolve_motion / slrhip_read_motion) -----------
 // The traversal and the record window are the feature pass's; the fold and the sums are pt_motion.hip's; the sample is pt_motion.h's.
-int slrhip_render_motion(slrhip_ctx* ctx, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
-    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_motion: null context");
-    const char* what = nullptr;
-    if (const int rc = motionRefusal(ctx->haveRender, ctx->haveScene ? ctx->scene.numInstances : 0u, d, sppBegin, sppCount, &what))
-        return fail(rc, std::string("slrhip_render_motion: ") + what);
+// What the two entry points share, after their argument checks.  prevVertices == nullptr: slrhip_render_motion's pass (16 B records,
+// k_motion_fold<false>); else slrhip_render_motion_vertices' (the window also keeps b2; k_motion_fold<true> on the kept arrays).
+static int renderMotion(slrhip_ctx* ctx, const slrhip_motion_desc* d, const slrhip_vertex* prevVertices, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
     if (sppCount == 0) return SLRHIP_OK;
     const RenderParams& rp = ctx->params;
     if (rp.numPixels == 0) return SLRHIP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const hipStream_t s = (hipStream_t)streamPtr;
+    const size_t pixels = rp.numPixels;
     if (!ctx->motionReady) {
-        // the first motion call since render_begin: the sums (cleared in stream order) and room in the record window, sized by the
-        // shard alone, so that no later call allocates whatever its pass count.  The window's arrays only ever grow.
-        const size_t pixels = rp.numPixels;
-        ctx->motionWindow = featureWindow(rp.numPixels, false);
+        // the first motion call since render_begin: the sums, cleared in stream order
         HIP_TRY(ctx->motionSums.alloc(pixels));
-        if (const int rc = sizeFeatureRecords(ctx, std::max(ctx->featRecords.capacity, pixels * ctx->motionWindow), 0)) return rc;
         HIP_TRY(hipMemsetAsync(ctx->motionSums.ptr, 0, pixels * sizeof(float4), s));
         if (const int rc = clearFeatureError(ctx, s)) return rc;
+        ctx->motionWindow = ctx->motionVerticesWindow = 0;
         ctx->motionReady = true;
+    }
+    // ... and the first of its kind: room in the record window, sized by the shard alone (with b2: 20 B per record), so that no later
+    // call allocates whatever its pass count.  The window's arrays only ever grow: what the feature, albedo or other motion calls
+    // sized them for stays.
+    const bool verts = prevVertices != nullptr;
+    uint32_t& window = verts ? ctx->motionVerticesWindow : ctx->motionWindow;
+    if (window == 0) {
+        const uint32_t w = featureWindow(rp.numPixels, verts);
+        if (const int rc = sizeFeatureRecords(ctx, std::max(ctx->featRecords.capacity, pixels * w), verts ? std::max(ctx->featB2.capacity, pixels * w) : 0)) return rc;
+        window = w;
     }
     // both cameras by value, from the host arithmetic of the upload's camera constants; no previous camera: the current one
     const DevCamera& cam = ctx->scene.camera;
-    MotionParams mp;
+    MotionParams mp{};
     mp.now = makeMotionCamera(cam.mat, cam.matInv, cam.opWidth, cam.opHeight, cam.objPlaneDistance);
     mp.prev = mp.now;
     if (d->previous_camera) {
@@ -321,15 +327,41 @@ int slrhip_render_motion(slrhip_ctx* ctx, const slrhip_motion_desc* d, uint32_t 
     mp.instances = ctx->scene.instances;
     mp.prevTransforms = reinterpret_cast<const float4*>(d->previous_transforms);
     mp.sums = ctx->motionSums.ptr;
-    for (uint32_t done = 0; done < sppCount; done += ctx->motionWindow) {
-        const uint32_t n = std::min(ctx->motionWindow, sppCount - done);
+    if (verts) {
+        mp.vertices = reinterpret_cast<const float*>(ctx->geoVertices.ptr);
+        mp.triangles = reinterpret_cast<const uint4*>(ctx->geoTriangles.ptr);
+        mp.prevVertices = reinterpret_cast<const float*>(prevVertices);
+        mp.numVertices = ctx->geoNumVertices; mp.numTriangles = ctx->geoNumTriangles;
+    }
+    for (uint32_t done = 0; done < sppCount; done += window) {
+        const uint32_t n = std::min(window, sppCount - done);
         FeatureParams fp = featureParams(ctx, 0, sppBegin + done, n);
-        fp.b2 = nullptr;
+        fp.b2 = verts ? ctx->featB2.ptr : nullptr;
         launchFeatureTrace(ctx->scene, fp, ctx->numCUs, s);
         launchMotionFold(cam, fp, mp, s);
     }
     HIP_TRY(hipGetLastError());
     return SLRHIP_OK;
+}
+
+int slrhip_render_motion(slrhip_ctx* ctx, const slrhip_motion_desc* d, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_motion: null context");
+    const char* what = nullptr;
+    if (const int rc = motionRefusal(ctx->haveRender, ctx->haveScene ? ctx->scene.numInstances : 0u, d, sppBegin, sppCount, &what))
+        return fail(rc, std::string("slrhip_render_motion: ") + what);
+    return renderMotion(ctx, d, nullptr, sppBegin, sppCount, streamPtr);
+}
+
+int slrhip_render_motion_vertices(slrhip_ctx* ctx, const slrhip_motion_vertices_desc* d, uint32_t sppBegin, uint32_t sppCount, void* streamPtr) {
+    if (!ctx) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_render_motion_vertices: null context");
+    const char* what = nullptr;
+    const bool have = ctx->haveScene;
+    if (const int rc = motionVerticesRefusal(ctx->haveRender, have ? ctx->scene.numInstances : 0u, ctx->config.flags, have ? ctx->treeBuilder : 0u, d, sppBegin,
+                                             sppCount, &what))
+        return fail(rc, std::string("slrhip_render_motion_vertices: ") + what);
+    if (d->previous_vertices && (!ctx->geometryKept || !ctx->geoVertices.ptr || !ctx->geoTriangles.ptr))
+        return fail(SLRHIP_ERR_HIP, "slrhip_render_motion_vertices: the vertex and index arrays are not kept (internal error)");
+    return renderMotion(ctx, &d->frame, d->previous_vertices, sppBegin, sppCount, streamPtr);
 }
 
 int slrhip_resolve_motion(slrhip_ctx* ctx, float* deviceDst, size_t numFloats, void* streamPtr) {

@@ -187,7 +187,8 @@ struct slrhip_ctx {
     // the motion buffer (slrhip_render_motion): the sums are allocated by the first motion call after render_begin; the record window is the feature pass's
     DevArray<float4> motionSums;                  // {sum m.x, sum m.y, sum z', valid samples} per pixel of the shard
     bool motionReady = false;                     // sums allocated and cleared since render_begin
-    uint32_t motionWindow = 0;                    // passes per launch
+    uint32_t motionWindow = 0;                    // passes per launch of slrhip_render_motion (0: none since the sums were cleared)
+    uint32_t motionVerticesWindow = 0;            // ... and of slrhip_render_motion_vertices, whose window also keeps b2
     // per-pixel noise statistics: records {mean, M2, n, max}; the sample clamp: records {clamped, dropped (uint32 bits), removed, largest}
     slrhip::PixelRecords<slrhip::StatsTotals> stats;
     slrhip::PixelRecords<slrhip::ClampTotals> clamp;

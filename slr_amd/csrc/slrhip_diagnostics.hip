@@ -102,6 +102,15 @@ int slrhip_debug_motion_check(int32_t haveRender, uint32_t numInstances, const s
     return SLRHIP_OK;
 }
 
+// Diagnostic (include/slrhip_debug.h): the argument checks of slrhip_render_motion_vertices alone, for a context described by four numbers.
+int slrhip_debug_motion_vertices_check(int32_t haveRender, uint32_t numInstances, uint32_t configFlags, uint32_t treeBuilder,
+                                       const slrhip_motion_vertices_desc* d, uint32_t sppBegin, uint32_t sppCount) {
+    const char* what = nullptr;
+    if (const int rc = motionVerticesRefusal(haveRender != 0, numInstances, configFlags, treeBuilder, d, sppBegin, sppCount, &what))
+        return fail(rc, std::string("slrhip_render_motion_vertices: ") + what);
+    return SLRHIP_OK;
+}
+
 // Diagnostic (include/slrhip_debug.h): the block lengths of a slrhip_render_adaptive call.
 int slrhip_debug_adaptive_blocks(uint32_t sppMin, uint32_t sppStep, uint32_t sppMax, uint32_t* blocks, uint32_t maxBlocks, uint32_t* numBlocks) {
     if (!numBlocks || (maxBlocks && !blocks)) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_adaptive_blocks: null argument");
