@@ -54,6 +54,29 @@ int slrhip_debug_primary_plan(uint32_t num_pixels, uint32_t num_passes, uint32_t
  * for a working one.  Synchronises.                                                                                                 */
 int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples);
 
+/* Where a launch of the primary pass puts its samples (slr_amd/csrc/pt_kernels.h, primaryLaunchEntry), evaluated on the HOST with the very
+ * function its kernel calls: the launch takes the passes [first_pass, first_pass + num_passes) of a window of `window_passes` passes over
+ * `num_pixels` pixels and numbers its samples with the pass fastest; entries[i] = the entry of sample i in the result window and in the
+ * planes beside it (num_pixels x num_passes of them; expected: pixel x window_passes + first_pass + pass).  No GPU is touched.
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null pointer, no pass, passes outside the window, or 2^31 samples and more.                       */
+int slrhip_debug_primary_entries(uint32_t num_pixels, uint32_t first_pass, uint32_t num_passes, uint32_t window_passes, uint64_t* entries);
+
+/* The plan of that plane (slr_amd/csrc/render_plan.h, planPrimary), evaluated on the HOST with the function the render calls: the
+ * arguments of slrhip_debug_primary_plan, with bit 3 of `scene_class` for a scene whose tree is the quantized one (65 536 nodes and more).
+ * *entries = num_pixels x num_passes where the pass runs AND keeps the plane (scenes without instances on a tree that is not quantized),
+ * else 0.  No GPU is touched.                                                                                                         */
+int slrhip_debug_primary_stream_plan(uint32_t num_pixels, uint32_t num_passes, uint32_t config_flags, int32_t scene_class, uint64_t* entries);
+
+/* The entries of the plane that carries every sample's stream from the primary pass to the launch that starts the sample, as the last
+ * window of the context bound it: pixels x passes of that window when it ran the pass, 0 when it did not (no plane is bound then).    */
+int slrhip_debug_primary_stream_entries(slrhip_ctx* ctx, uint64_t* entries);
+
+/* The camera draws of `n` samples on device `device`, forward and recovered (slr_amd/csrc/pt_camera.h): tuples[4 i ..] = seed, pixel x,
+ * pixel y, pass; out[16 i ..] = the draws drawCameraSample makes (p.x, p.y, wavelength offset, wavelength selection, two lens draws; float
+ * bits), the four words of the stream it leaves, and the same six draws as recoverCameraDraws rebuilds them from that stream and the
+ * pixel.  Host arrays; synchronises.                                                                                                */
+int slrhip_debug_camera_draws(int32_t device, uint32_t n, const uint32_t* tuples, uint32_t* out);
+
 /* The blocks of a slrhip_render_adaptive call(slr_amd/csrc/render_plan.h, planAdaptiveBlocks), evaluated on the HOST with the
  * function the call asks for its next block: blocks[k] = passes of block k for the first `max_blocks` blocks, *num_blocks = their number (0 for a
  * triple the entry point refuses).  No GPU is touched.                                                                          */

@@ -31,7 +31,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
-           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -199,6 +199,12 @@ def load_library():
     if path == LIB_PATH or hasattr(lib, "slrhip_debug_primary_plan"):
         lib.slrhip_debug_primary_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p]
         lib.slrhip_debug_primary_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    # (and one from before the pass handed its streams to the fused start lacks these four)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_camera_draws"):
+        lib.slrhip_debug_primary_entries.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.slrhip_debug_primary_stream_entries.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.slrhip_debug_primary_stream_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]
+        lib.slrhip_debug_camera_draws.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -560,6 +566,12 @@ class Context:
         """Diagnostic (slrhip_debug_primary_samples): samples since render_begin whose first hit came from the primary pass's record."""
         n = C.c_uint64()
         _check(self.lib, self.lib.slrhip_debug_primary_samples(self.handle, C.byref(n)), "slrhip_debug_primary_samples")
+        return n.value
+
+    def primary_stream_entries(self):
+        """Diagnostic (slrhip_debug_primary_stream_entries): entries of the stream plane the last window bound; 0 = it ran no primary pass."""
+        n = C.c_uint64()
+        _check(self.lib, self.lib.slrhip_debug_primary_stream_entries(self.handle, C.byref(n)), "slrhip_debug_primary_stream_entries")
         return n.value
 
     def profile(self):

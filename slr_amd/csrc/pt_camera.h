@@ -30,6 +30,27 @@ SLR_DEV CameraDraws drawCameraSample(Rng& rng, int32_t rngSeed, uint32_t px, uin
     return d;
 }
 
+// The same draws from the stream drawCameraSample leaves behind.  xorshift128's state IS its last four outputs, so the state
+// after the seven draws is (o4, o5, o6, o7): the raw words of wlOffset, uLambda, lu0 and lu1.  The two draws before them run the
+// recurrence backwards: o_n = A(o_{n-1}) ^ B(o_{n-4}) with A(x) = x ^ (x >> 19) and B(x) = t ^ (t >> 8), t = x ^ (x << 11), so
+// B(o3) = o7 ^ A(o6) and B(o2) = o6 ^ A(o5), and both halves of B are xorshifts with closed inverses.  The time draw (o1) is not
+// used by the camera.  Integer operations and nextFloat's own conversion: the draws are the forward ones bit for bit.
+SLR_DEV uint32_t xorshiftStepBack(uint32_t newer, uint32_t older) {
+    const uint32_t y = newer ^ (older ^ (older >> 19));         // B(x)
+    const uint32_t t = y ^ (y >> 8) ^ (y >> 16) ^ (y >> 24);    // x ^ (x << 11)
+    return t ^ (t << 11) ^ (t << 22);                           // x
+}
+SLR_DEV CameraDraws recoverCameraDraws(const Rng& after, uint32_t px, uint32_t py) {
+    CameraDraws d;
+    d.px = px + Rng::toFloat(xorshiftStepBack(after.s2, after.s1));
+    d.py = py + Rng::toFloat(xorshiftStepBack(after.s3, after.s2));
+    d.wlOffset = Rng::toFloat(after.s0);
+    d.uLambda = Rng::toFloat(after.s1);
+    d.lu0 = Rng::toFloat(after.s2);
+    d.lu1 = Rng::toFloat(after.s3);
+    return d;
+}
+
 struct CameraRay {
     V3 org, dir;                // world space; the ray is Ray(org, dir, time) with distMin 0 and distMax INFINITY
     V3 lensN;                   // the lens surface's normal in world space
@@ -57,9 +78,9 @@ SLR_DEV CameraRay sampleCameraRay(const DevCamera& cam, uint32_t imageWidth, uin
 }
 
 // The camera ray of (pixel of the shard, pass of the launch) as a ring entry or a slrhip_ray: {org, distMin 0}, {dir, distMax inf}
-SLR_DEV void cameraRayOf(const DevCamera& cam, const FeatureParams& fp, uint32_t pix, uint32_t pass, float4& o, float4& d, uint32_t& xy) {
+// `rng`: the stream as the draws leave it, where the path's first bounce goes on
+SLR_DEV void cameraRayOf(const DevCamera& cam, const FeatureParams& fp, uint32_t pix, uint32_t pass, float4& o, float4& d, uint32_t& xy, Rng& rng) {
     xy = fp.pixelXY[pix];
-    Rng rng;
     const CameraDraws draws = drawCameraSample(rng, fp.rngSeed, xy & 0xFFFFu, xy >> 16, fp.passBegin + pass, fp.timeStart, fp.timeEnd);
     const CameraRay r = sampleCameraRay(cam, fp.imageWidth, fp.imageHeight, draws);
     o = make_float4(r.org.x, r.org.y, r.org.z, 0.0f);
@@ -68,12 +89,13 @@ SLR_DEV void cameraRayOf(const DevCamera& cam, const FeatureParams& fp, uint32_t
 // the feature passes' numbering: the pixel fastest (their record windows are pass-major, writer and reader alike)
 SLR_DEV void featureCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
     const uint32_t pass = index / fp.numPixels, pix = index - pass * fp.numPixels;
-    cameraRayOf(cam, fp, pix, pass, o, d, xy);
+    Rng rng;
+    cameraRayOf(cam, fp, pix, pass, o, d, xy, rng);
 }
 // the primary pass's numbering: the pass fastest (the result window's own order, windowEntry)
-SLR_DEV void primaryCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy) {
+SLR_DEV void primaryCameraRay(const DevCamera& cam, const FeatureParams& fp, uint32_t index, float4& o, float4& d, uint32_t& xy, Rng& rng) {
     const uint32_t pix = index / fp.numPasses, pass = index - pix * fp.numPasses;
-    cameraRayOf(cam, fp, pix, pass, o, d, xy);
+    cameraRayOf(cam, fp, pix, pass, o, d, xy, rng);
 }
 
 } // namespace slrhip

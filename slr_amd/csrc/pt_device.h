@@ -195,7 +195,8 @@ struct Rng {
         s0 = s1; s1 = s2; s2 = s3;
         return s3 = (s3 ^ (s3 >> 19)) ^ (t ^ (t >> 8));
     }
-    SLR_DEV float nextFloat() { return __uint_as_float((next() >> 9) | 0x3f800000u) - 1.0f; }
+    static SLR_DEV float toFloat(uint32_t bits) { return __uint_as_float((bits >> 9) | 0x3f800000u) - 1.0f; }
+    SLR_DEV float nextFloat() { return toFloat(next()); }
     SLR_DEV void seed(int32_t seed) {
         // `seed` is signed in the reference: arithmetic shift, unsigned multiply
         uint32_t v;

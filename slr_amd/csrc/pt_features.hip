@@ -79,6 +79,26 @@ void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays,
     hipLaunchKernelGGL(k_camera_rays, dim3((fp.numPixels + 255u) / 256u), dim3(256), 0, stream, sc.camera, fp, rays, pixelXY);
 }
 
+// slrhip_debug_camera_draws: drawCameraSample forward and recoverCameraDraws from the stream it leaves, one lane per tuple
+// (seed, x, y, pass); out: 16 words a tuple — the six forward draws, the stream, the six recovered draws
+__global__ __launch_bounds__(256) void k_camera_draws(uint32_t n, const uint4* tuples, uint32_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 t = tuples[i];
+    Rng rng;
+    const CameraDraws f = drawCameraSample(rng, (int32_t)t.x, t.y, t.z, t.w, 0.0f, 0.0f);
+    const CameraDraws r = recoverCameraDraws(rng, t.y, t.z);
+    const uint32_t words[16] = {__float_as_uint(f.px), __float_as_uint(f.py), __float_as_uint(f.wlOffset), __float_as_uint(f.uLambda),
+                                __float_as_uint(f.lu0), __float_as_uint(f.lu1), rng.s0, rng.s1, rng.s2, rng.s3,
+                                __float_as_uint(r.px), __float_as_uint(r.py), __float_as_uint(r.wlOffset), __float_as_uint(r.uLambda),
+                                __float_as_uint(r.lu0), __float_as_uint(r.lu1)};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[(size_t)i * 16 + k] = words[k];
+}
+void launchCameraDraws(uint32_t n, const uint4* tuples, uint32_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_camera_draws, dim3((n + 255u) / 256u), dim3(256), 0, stream, n, tuples, out);
+}
+
 // slrhip_resolve_features: one channel scattered into a [height][width][k] image the caller has filled with the value of
 // "outside the shard"; channel = one SLRHIP_FEATURE_* bit
 __global__ __launch_bounds__(256) void k_feature_resolve(FeatureParams fp, FeatureSums sums, uint32_t channel, uint32_t* dst) {

@@ -169,6 +169,10 @@ struct PathBuffers {
     // spC = spR + 1, element index = slot x stride): a kernel that visits a fraction of the slots then moves one sector per
     // visited slot and pair instead of most sectors of two arrays.  1 = separate arrays.
     uint32_t rayStride, spStride, hdrStride;      // hdrStride 2: rng = hdr + 1 (sample header + RNG state of a slot in one sector)
+    // primaryRng[entry], indexed like results: the sample's xorshift128 state after the camera draws, left by the primary pass's producer
+    // for the fused start of k_shade (windows with a primary pass only, else nullptr).  The last member: every other one keeps the
+    // offset it had in the kernels' argument block, so the kernels that do not read it are compiled as they were.
+    uint4* primaryRng;
 };
 
 struct RenderParams {
@@ -208,6 +212,14 @@ static const uint32_t kWorkRotate = 40503u;
 // (slrhip_render_adaptive) is laid out the same way.
 __host__ __device__ inline size_t windowEntry(uint32_t pix, uint32_t passOfWindow, uint32_t windowPasses) {
     return (size_t)pix * windowPasses + passOfWindow;
+}
+// The entry of sample i of a primary-pass launch (launchPrimary below) relative to the launch's first entry, windowEntry(0, its first
+// pass): the launch numbers the samples of its numPasses passes with the pass fastest, i = pixel x numPasses + pass of the launch,
+// and the window keeps windowPasses (>= numPasses) entries a pixel.  A launch of the whole window: i itself.
+__host__ __device__ inline size_t primaryLaunchEntry(uint32_t i, uint32_t numPasses, uint32_t windowPasses) {
+    size_t entry = i;
+    if (windowPasses != numPasses) entry += (size_t)(i / numPasses) * (windowPasses - numPasses);
+    return entry;
 }
 struct WorkItem {
     uint32_t pix, pass;           // pass relative to RenderParams::sppBegin
@@ -318,6 +330,8 @@ struct FeatureSums {
 };
 void launchFeatures(const DevScene& sc, const FeatureParams& fp, const FeatureSums& sums, uint32_t idsPass, int numCUs, hipStream_t stream);
 void launchCameraRays(const DevScene& sc, const FeatureParams& fp, float4* rays, uint32_t* pixelXY, hipStream_t stream);
+// slrhip_debug_camera_draws (pt_features.hip): n tuples (seed, x, y, pass) in, 16 words each out (DEVICE memory)
+void launchCameraDraws(uint32_t n, const uint4* tuples, uint32_t* out, hipStream_t stream);
 void launchFeatureResolve(const FeatureParams& fp, const FeatureSums& sums, uint32_t channel, void* dst, hipStream_t stream);
 // the traversal half of launchFeatures alone: the window's records, and b2 when fp.b2 is given
 void launchFeatureTrace(const DevScene& sc, const FeatureParams& fp, int numCUs, hipStream_t stream);

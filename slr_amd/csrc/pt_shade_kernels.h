@@ -875,13 +875,9 @@ struct SampleStart {
     float wlOffset, camWeight;
     V3 org, dir;
 };
+// ... from the draws on: st.rng holds the stream after them
 template <class S>
-__device__ __forceinline__ SampleStart beginSample(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t pix, uint32_t passOfWindow) {
-    // Job::kernel PathTracingRenderer.cpp:100-120, draws in source (left-to-right) order
-    const uint32_t xy = pb.pixelXY[pix];
-    const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
-    SampleStart st;
-    const CameraDraws draws = drawCameraSample(st.rng, rp.rngSeed, px, py, rp.sppBegin + passOfWindow, rp.timeStart, rp.timeEnd);
+__device__ __forceinline__ void sampleFromDraws(const DevScene& sc, const RenderParams& rp, const CameraDraws& draws, SampleStart& st) {
     // createWithEqualOffsets: RGBTypes.h:37-45 (offset unused, PDF 1) / SpectrumTypes.h:54-64 (PDF N / 470)
     st.wlOffset = draws.wlOffset;
     st.wl = min((uint32_t)(uint16_t)(S::N * draws.uLambda), (uint32_t)(S::N - 1));
@@ -894,6 +890,24 @@ __device__ __forceinline__ SampleStart beginSample(const DevScene& sc, const Pat
                    ((cam.dirLocalZ * cam.dirLocalZ * cam.dirLocalZ) * sc.camera.imgPlaneArea);
     // weight :126
     st.camWeight = absDot(st.dir, lensN) / (sc.camera.areaPDF * dirPDF * selectWLPDF);
+}
+template <class S>
+__device__ __forceinline__ SampleStart beginSample(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t pix, uint32_t passOfWindow) {
+    // Job::kernel PathTracingRenderer.cpp:100-120, draws in source (left-to-right) order
+    const uint32_t xy = pb.pixelXY[pix];
+    const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
+    SampleStart st;
+    const CameraDraws draws = drawCameraSample(st.rng, rp.rngSeed, px, py, rp.sppBegin + passOfWindow, rp.timeStart, rp.timeEnd);
+    sampleFromDraws<S>(sc, rp, draws, st);
+    return st;
+}
+// The fused start (k_shade with a primary pass): the stream after the camera draws comes from the primary pass, which drew them for
+// the same sample (PathBuffers::primaryRng), and the draws from the stream (recoverCameraDraws, pt_camera.h).
+template <class S>
+__device__ __forceinline__ SampleStart resumeSample(const DevScene& sc, const RenderParams& rp, uint32_t xy, const uint4& stream) {
+    SampleStart st;
+    st.rng.s0 = stream.x; st.rng.s1 = stream.y; st.rng.s2 = stream.z; st.rng.s3 = stream.w;
+    sampleFromDraws<S>(sc, rp, recoverCameraDraws(st.rng, xy & 0xFFFFu, xy >> 16), st);
     return st;
 }
 template <class S>
@@ -958,7 +972,9 @@ struct StartLds {
 // for both took k_shade<RGB, glossy> from 163 to 181 VGPRs and the spectral kernels to 190 - 220 B more scratch, and renders WITHOUT
 // the pass (spectral, environment light: render_plan.h) ran 13 - 14 % slower than before.  Without PRIMARY the
 // kernel is what it was.  Built for the RGB kernels only: the plan keeps the pass off in spectral contexts.
-template <class S, bool LDS_TABLES, bool MF, bool MULTI = false, bool TEX = false, bool PRIMARY = false>
+// RESUME (with PRIMARY): the fused start goes on from the stream the primary pass left (PathBuffers::primaryRng; windows whose plan keeps
+// that plane, render_plan.h) instead of seeding its own.  A template argument for the reason PRIMARY is one.
+template <class S, bool LDS_TABLES, bool MF, bool MULTI = false, bool TEX = false, bool PRIMARY = false, bool RESUME = false>
 __global__ __launch_bounds__(kShadeBlock)
 __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_SPECTRAL_GLOSSY : SLR_WAVES_SPECTRAL)))) void k_shade(DevScene sc, PathBuffers pb, RenderParams rp, uint32_t parity) {
     __shared__ ShadeLds<S::N != 3> lds;
@@ -1078,9 +1094,13 @@ __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_S
         if (curActive) {
             curSlot = blockIdx.x * kShadeBlock + start.lane[threadIdx.x];
             const uint32_t pix = start.pix[threadIdx.x], pass = start.pass[threadIdx.x];
-            // the record first: its round trip is hidden behind the seeding of the stream
+            // RESUME: one round trip for everything the new sample needs — the record, the stream the primary pass left behind the camera
+            // draws (it drew them for the same sample: no seeding here) and the pixel's coordinates; else the record first: its round
+            // trip is hidden behind the seeding of the stream
             loadPrimaryRecord<S>(sc, pb, rp, pix, pass, in.h, in.hitInstance);
-            const SampleStart st = beginSample<S>(sc, pb, rp, pix, pass);
+            SampleStart st;
+            if constexpr (RESUME) st = resumeSample<S>(sc, rp, pb.pixelXY[pix], pb.primaryRng[windowEntry(pix, pass, rp.sppCount)]);
+            else st = beginSample<S>(sc, pb, rp, pix, pass);
             curHdr = make_uint4(pix, __float_as_uint(st.camWeight), __float_as_uint(st.wlOffset), pass);
             pb.hdr[(size_t)curSlot * pb.hdrStride] = curHdr;
             // the rest of what startSample writes stays in registers: the visit below stores the state of the first bounce

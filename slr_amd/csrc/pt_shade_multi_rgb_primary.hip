@@ -3,9 +3,12 @@
 
 namespace slrhip {
 
+void launchShadeMultiRGBPrimarySeeded(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);      // pt_shade_multi_rgb_primary_seeded.hip
+
 void launchShadeMultiRGBPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream) {
+    if (!pb.primaryRng) { launchShadeMultiRGBPrimarySeeded(sc, pb, rp, parity, stream); return; }      // no stream plane in this window (render_plan.h, planPrimary)
     const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    hipLaunchKernelGGL((k_shade<RGB, false, true, true, false, true>), grid, block, 0, stream, sc, pb, rp, parity);
+    hipLaunchKernelGGL((k_shade<RGB, false, true, true, false, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
 }
 
 } // namespace slrhip

@@ -74,9 +74,15 @@ struct WsFeatureIO {
 // passes of one pixel: all but identical camera rays in a consumer wave, and consecutive record addresses.  finish writes
 // {triangle, t, b1, b2} — what the render's client writes to PathBuffers::hit — to the sample's entry of the result window, which
 // nobody else touches until the sample finishes (writeResult), and the instance to its plane.
+// STREAMS: the producer also leaves every sample's stream behind the camera draws (PathBuffers::primaryRng) for the fused start of
+// k_shade.  A template argument: the store and the four words kept for it cost the producer wave 48 B more scratch per lane, and where
+// one producer feeds 15 consumers (large trees, instanced scenes) it is the pass's limit — there the plan keeps the plane off
+// (render_plan.h) and the producer is the one it was.
+template <bool STREAMS>
 struct WsPrimaryIO {
     FeatureParams fp;             // the camera arguments of the launch; records = the entry of (pixel 0, the launch's first pass); errorWord = the render's
     int32_t* instances;           // that entry of PathBuffers::primaryInstance, or nullptr
+    uint4* streams;               // that entry of PathBuffers::primaryRng
     uint64_t* totals;
     uint32_t stride;              // float4 per entry (RGB 1, spectral 4: the record is the first)
     uint32_t windowPasses;        // passes of the window (>= fp.numPasses, the launch's): the distance of two pixels' entries
@@ -84,7 +90,13 @@ struct WsPrimaryIO {
     __device__ __forceinline__ uint32_t tag() const { return 0u; }
     __device__ __forceinline__ void makeRay(const DevScene& sc, uint32_t i, float4& o, float4& d) const {
         uint32_t xy;
-        primaryCameraRay(sc.camera, fp, i, o, d, xy);
+        Rng after;
+        primaryCameraRay(sc.camera, fp, i, o, d, xy, after);
+        if constexpr (!STREAMS) return;
+        // the stream behind the camera draws, for the launch of k_shade that starts the sample (its fused start goes on from here instead
+        // of seeding again); the producer's lanes hold consecutive samples: 1 KiB contiguous per wave
+        ntStore4(reinterpret_cast<float4*>(streams + primaryLaunchEntry(i, fp.numPasses, windowPasses)),
+                 make_float4(__uint_as_float(after.s0), __uint_as_float(after.s1), __uint_as_float(after.s2), __uint_as_float(after.s3)));
     }
     // Scene::intersect of PathTracingRenderer.cpp:147, counted where it is traced: one atomic per workgroup
     __device__ __forceinline__ void produced(uint32_t rays) const {
@@ -92,9 +104,7 @@ struct WsPrimaryIO {
     }
     template <bool INST>
     __device__ __forceinline__ void finish(uint32_t slot, uint32_t hitTri, float hitT, float hitB1, float hitB2, int32_t hitInst) const {
-        // windowEntry(pixel, pass of the launch, windowPasses) relative to the launch's first entry; a launch of the whole window: slot itself
-        size_t entry = slot;
-        if (windowPasses != fp.numPasses) entry += (size_t)(slot / fp.numPasses) * (windowPasses - fp.numPasses);
+        const size_t entry = primaryLaunchEntry(slot, fp.numPasses, windowPasses);
         ntStore4(fp.records + entry * stride, make_float4(__uint_as_float(hitTri), hitT, hitB1, hitB2));
         if (INST) __builtin_nontemporal_store(hitInst, instances + entry);
     }
@@ -140,11 +150,11 @@ void launchFeatureTrace(const DevScene& sc, const FeatureParams& fp, int numCUs,
     launchRingWs(sc, WsFeatureIO{fp}, fp.numPixels * fp.numPasses, sceneConsumers(sc), numCUs, stream);
 }
 
-void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
-                   hipStream_t stream) {
+template <bool STREAMS>
+static void launchPrimaryWith(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
+                              hipStream_t stream) {
     const uint32_t n = rp.numPixels * numPasses;
-    if (n == 0) return;
-    WsPrimaryIO io{};
+    WsPrimaryIO<STREAMS> io{};
     io.stride = rp.spectral ? 4u : 1u;
     io.windowPasses = rp.sppCount;
     const size_t first = windowEntry(0u, firstPass, rp.sppCount);
@@ -153,6 +163,7 @@ void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams
     io.fp.rngSeed = rp.rngSeed; io.fp.timeStart = rp.timeStart; io.fp.timeEnd = rp.timeEnd;
     io.fp.imageWidth = rp.imageWidth; io.fp.imageHeight = rp.imageHeight;
     io.instances = pb.primaryInstance ? pb.primaryInstance + first : nullptr;
+    io.streams = STREAMS ? pb.primaryRng + first : nullptr;
     io.totals = pb.totals;
     // Consumers per producer.  Where k_trace_ws runs 7 (small trees) this pass runs 3: its producer wave seeds a stream and samples the
     // camera for every ray, a camera ray needs few nodes, and with 7 consumers the producer was the limit (headline frame: 306 ms
@@ -161,6 +172,14 @@ void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams
     const int ncTrace = sceneConsumers(sc);
     const int nc = envNc == 3 || envNc == 7 || envNc == 15 ? envNc : (ncTrace == 7 && !sc.instances ? 3 : ncTrace);
     launchRingWs(sc, io, n, nc, numCUs, stream);
+}
+
+void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
+                   hipStream_t stream) {
+    const uint32_t n = rp.numPixels * numPasses;
+    if (n == 0) return;
+    if (pb.primaryRng) launchPrimaryWith<true>(sc, pb, rp, firstPass, numPasses, numCUs, stream);
+    else launchPrimaryWith<false>(sc, pb, rp, firstPass, numPasses, numCUs, stream);
 }
 
 } // namespace slrhip

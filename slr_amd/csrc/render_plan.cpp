@@ -123,7 +123,8 @@ WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthO
     return w;
 }
 
-PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment) {
+PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment,
+                        bool quantized) {
     PrimaryPlan p;
     if ((configFlags & (SLRHIP_FLAG_NO_PRIMARY_PASS | SLRHIP_FLAG_COUNT_TRAVERSAL)) != 0 || numPixels == 0 || sppCount == 0 ||
         numPixels > kPrimaryMaxSamples)
@@ -133,6 +134,9 @@ PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFl
     p.passesPerLaunch = std::min(sppCount, kPrimaryMaxSamples / numPixels);
     p.numLaunches = (sppCount + p.passesPerLaunch - 1) / p.passesPerLaunch;
     p.instanceEntries = instanced ? (uint64_t)numPixels * sppCount : 0u;
+    // 16 B per sample, what an RGB result entry takes: the plane is as large as the window's results, whatever planWindows made of the
+    // budget (a single pass may exceed it, and so may its plane).  Not where the pass's producer wave is the limit (render_plan.h).
+    p.rngEntries = instanced || quantized ? 0u : (uint64_t)numPixels * sppCount;
     return p;
 }
 

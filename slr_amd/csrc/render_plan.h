@@ -64,11 +64,16 @@ struct PrimaryPlan {
     uint32_t passesPerLaunch = 0;              // numPixels x passesPerLaunch <= kPrimaryMaxSamples
     uint32_t numLaunches = 0;                  // ceil(sppCount / passesPerLaunch)
     uint64_t instanceEntries = 0;              // int32 entries of PathBuffers::primaryInstance: numPixels x sppCount in instanced scenes, else 0
+    uint64_t rngEntries = 0;                   // uint4 entries of PathBuffers::primaryRng: numPixels x sppCount when the pass is on and keeps the plane, else 0
 };
 // Two classes of render keep the pass off because it measured slower there: spectral contexts (`spectral`) and
 // scenes with an environment light (`environment`: many camera rays leave the scene, their paths end in the fused visit and the
 // slot waits for the next launch).
-PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment);
+// `quantized`: the scene's tree is the quantized one (large scenes).  There and in instanced scenes the pass runs 15 (or 7) consumer waves
+// per producer and the producer wave is its limit: the stream plane stays off (rngEntries 0), the fused start seeds its own stream as
+// before — with the plane grid10m rendered 0.6 % slower, the producer's +30 ms against k_shade's -20 ms.
+PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment,
+                        bool quantized = false);
 
 // RenderParams::tailSlots of a window: 0 = the tail kernel stays off.  `asked`: the caller's flag or the automatic slot count;
 // `envTail`: SLRHIP_TAIL_SLOTS (-1 = unset, 0 = off, n = the bound); `available`: the tail kernel exists for this scene and the

@@ -370,13 +370,20 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     rp.workItems = window.workItems; rp.runLength = window.runLength; rp.numRuns = window.numRuns;
     // the primary pass of the window (render_plan.cpp, planPrimary); its instance plane is allocated before anything is queued
     const PrimaryPlan primary = planPrimary(rp.numPixels, sppCount, ctx->config.flags, ctx->scene.instances != nullptr, rp.spectral != 0,
-                                            ctx->scene.hasEnv != 0);
+                                            ctx->scene.hasEnv != 0, ctx->scene.nodesQ != nullptr);
     rp.primary = primary.on ? 1u : 0u;
     pb.primaryInstance = nullptr;
     if (primary.instanceEntries) {
         HIP_TRY(ctx->primaryInstance.alloc((size_t)primary.instanceEntries));
         pb.primaryInstance = ctx->primaryInstance.ptr;
     }
+    // ... and so is the plane of the streams the pass leaves behind the camera draws (the fused start of k_shade goes on from them)
+    pb.primaryRng = nullptr;
+    if (primary.rngEntries) {
+        HIP_TRY(ctx->primaryRng.alloc((size_t)primary.rngEntries));
+        pb.primaryRng = ctx->primaryRng.ptr;
+    }
+    ctx->primaryRngEntries = pb.primaryRng ? ctx->primaryRng.count : 0u;       // what this window bound, not what the plan said
     // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
     // it is asked for zero passes
     launchResetSlots(pb, rp, ctx->firstRenderCall, stream);

@@ -177,6 +177,47 @@ int slrhip_debug_primary_plan(uint32_t numPixels, uint32_t numPasses, uint32_t c
     return SLRHIP_OK;
 }
 
+// Diagnostic (include/slrhip_debug.h): where the primary pass's launches put their samples, with the helper the kernels call.
+int slrhip_debug_primary_entries(uint32_t numPixels, uint32_t firstPass, uint32_t numPasses, uint32_t windowPasses, uint64_t* entries) {
+    if (!entries) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_entries: null argument");
+    if (numPasses == 0 || (uint64_t)firstPass + numPasses > windowPasses || (uint64_t)numPixels * numPasses > kPrimaryMaxSamples)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_entries: the launch's passes must be 1 or more, inside the window, and under 2^31 samples");
+    const size_t first = windowEntry(0u, firstPass, windowPasses);       // launchPrimary's own arithmetic
+    for (uint32_t i = 0; i < numPixels * numPasses; ++i) entries[i] = first + primaryLaunchEntry(i, numPasses, windowPasses);
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the stream plane of a window as renderWindow plans it.
+int slrhip_debug_primary_stream_plan(uint32_t numPixels, uint32_t numPasses, uint32_t configFlags, int32_t sceneClass, uint64_t* entries) {
+    if (!entries) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_stream_plan: null argument");
+    *entries = planPrimary(numPixels, numPasses, configFlags, (sceneClass & 1) != 0, (sceneClass & 2) != 0, (sceneClass & 4) != 0, (sceneClass & 8) != 0).rngEntries;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the entries of the stream plane the last window bound.
+int slrhip_debug_primary_stream_entries(slrhip_ctx* ctx, uint64_t* entries) {
+    if (!ctx || !entries) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_stream_entries: null argument");
+    *entries = ctx->primaryRngEntries;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the camera draws forward and recovered, on the device.
+int slrhip_debug_camera_draws(int32_t device, uint32_t n, const uint32_t* tuples, uint32_t* out) {
+    if (!tuples || !out) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_camera_draws: null argument");
+    if (n == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevArray<uint4> dIn;
+    DevArray<uint32_t> dOut;
+    HIP_TRY(dIn.alloc(n));
+    HIP_TRY(dOut.alloc((size_t)n * 16u));
+    HIP_TRY(hipMemcpy(dIn.ptr, tuples, (size_t)n * sizeof(uint4), hipMemcpyHostToDevice));
+    launchCameraDraws(n, dIn.ptr, dOut.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dOut.ptr, (size_t)n * 16u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
 } // extern "C"
 
 // ---- the tree read-outs (include/slrhip_debug.h): one description of the arrays for the context's tree and the host-built one ----
