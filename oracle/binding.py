@@ -65,6 +65,19 @@ class OracleLib:
     def scene(self, scene):
         return OracleScene(self, scene)
 
+    def eval_spectrum(self, scene, index, offsets):
+        """ContinuousSpectrum::evaluate of spectrum `index` of the scene's table at createWithEqualOffsets(offset, .) for every
+        offset (spectral build): float32 [len(offsets)][16]."""
+        f = self._f("eval_spectrum")
+        f.argtypes = [C.POINTER(abi.SceneDesc), C.c_uint32, C.c_float, C.c_void_p]
+        d = scene.desc()
+        out = np.zeros((len(offsets), 16), np.float32)
+        for k, off in enumerate(offsets):
+            rc = f(C.byref(d), int(index), float(off), out[k].ctypes.data)
+            if rc != 0:
+                raise RuntimeError("%seval_spectrum failed: %d" % (self.prefix, rc))
+        return out
+
     def rng(self, seed, n):
         u = np.zeros(n, dtype=np.uint32)
         f = np.zeros(n, dtype=np.float32)

@@ -81,6 +81,15 @@ class SceneBuilder:
         """Spectrum("ID": "D65") * scale (API.cpp:405-406,443-462); `rgb` is its RGB-mode value."""
         return self.sset.d65(scale, rgb)
 
+    def spectrum_regular(self, lambda_min, lambda_max, values, rgb=(0, 0, 0)):
+        """Spectrum::create(type, minLambda, maxLambda, values, n): a RegularContinuousSpectrum in the spectral build (API.cpp:1142-1144)."""
+        return self.sset.regular(lambda_min, lambda_max, values, rgb=rgb)
+
+    def spectrum_irregular(self, lambdas, values, rgb=(0, 0, 0)):
+        """Spectrum::create(type, lambdas, values, n): an IrregularContinuousSpectrum in the spectral build (API.cpp:1145-1147);
+        the wavelengths ascend."""
+        return self.sset.irregular(lambdas, values, rgb=rgb)
+
     def spectrum_ior(self, name, which, rgb):
         """Spectrum("ID": name, which): eta (0) or k (1) of spectrum_library.cpp; `rgb` is its RGB-mode value."""
         return self.sset.ior(name, which, rgb)
@@ -513,6 +522,115 @@ def material_zoo_nested():
         x, z = -1.2 + 0.22 * (i % 11), -0.3 * (i // 11)
         b.add_quad([(x, 0.01, z), (x + 0.2, 0.01, z), (x + 0.2, 0.01, z - 0.2), (x, 0.01, z - 0.2)], (0, 1, 0), (1, 0, 0), m)
     return b.build(cornell_camera(1.0), name="material_zoo_nested"), mats
+
+
+def sample_wavelengths(offset):
+    """float32 [16]: lambda_i of WavelengthSamples::createWithEqualOffsets (SpectrumTypes.h:54-64) as the device's wavelengthOf
+    (pt_bsdf.h) and the oracle compute it, operation by operation: 360 + ((830 - 360) * (float(i) + offset)) / 16."""
+    f = np.float32
+    i = np.arange(16, dtype=f)
+    out = f(360.0) + (f(830.0) - f(360.0)) * (i + f(offset)) / f(16.0)
+    assert out.dtype == f
+    return out
+
+
+# the special wavelength offsets of the spectrum tests: 1 - 2^-24 is the largest float below 1, at which 15 + offset rounds to 16
+# and lambda_15 is exactly 830 nm
+SPECTRUM_ZOO_OFFSETS = (0.0, 0.37, 0.5, float(np.float32(1.0) - np.float32(2.0 ** -24)))
+
+
+def spectrum_zoo_offsets(count=64, seed=360830):
+    """float32 wavelength offsets for the spectrum tests: SPECTRUM_ZOO_OFFSETS, then `count` seeded random ones in [0, 1)."""
+    return np.concatenate([np.array(SPECTRUM_ZOO_OFFSETS, np.float32), np.random.default_rng(seed).random(count).astype(np.float32)])
+
+
+SPECTRUM_ZOO_CLUSTER = 32          # samples of irr_cluster inside one 1-nm cell of the cell table
+
+# what spectrum_zoo(fit_lds=True) leaves out: the two long tables (1400 and 1000 floats) and what is built on them
+SPECTRUM_ZOO_LARGE = ("irr_dense700", "reg_wide", "reg_wide_emitted", "irr_low300", "irr_on_samples300")
+
+
+def spectrum_zoo(fit_lds):
+    """Edge-case spectra for the function-level tests of the device's spectrum evaluation (evalSpectrum, pt_bsdf.h), in a closed
+    Cornell box with one floor quad per material.  Returns (scene, {name: spectrum index}, {name: material index}).
+
+    Irregular spectra of more than 255 samples get no cell table (scene_prep.cpp, prepareSpectra) and are searched on the device;
+    the others start from the table's byte.  Sizes in pool floats: irr_dense700 1400, reg_wide 1000 (twice: the emitter's scaled
+    copy), irr_low300 and irr_on_samples300 600 each, irr_256 512, irr_255 510 + 118 (table), irr_cluster 74 + 118, an upsampled spectrum
+    384, the walls' own spectra 4 x 384 + D65.
+    fit_lds=True leaves out SPECTRUM_ZOO_LARGE and the checker texture so that materials, lights, spectrum records and pool stay
+    within the shade kernel's LDS tables (32, 16, 96, 6144 floats) and the kernels that stage them are chosen; its mirror takes
+    irr_255 as eta.  fit_lds=False is everything, which does not fit (pool > 6144 floats) and is read from HBM.
+    All values are seeded; the RGB values of the spectra are arbitrary (spectral contexts only)."""
+    f = np.float32
+    r = np.random.default_rng(20241020)
+    b = SceneBuilder()
+    cornell_walls(b)
+
+    def lambdas(n, lo, hi):
+        lam = np.unique(r.uniform(lo, hi, 4 * n).astype(f))[:: 4][:n]         # sorted, distinct in float32
+        assert len(lam) == n and (np.diff(lam) > 0).all()
+        return lam
+
+    def values(n):
+        return r.uniform(0.05, 0.95, n).astype(f)
+
+    on_samples = np.unique(np.concatenate([sample_wavelengths(off) for off in SPECTRUM_ZOO_OFFSETS]))
+    rgb = (0.5, 0.4, 0.3)
+    # every array is drawn in both zoos, in one order, so that the spectra they share hold the same numbers
+    dense700 = lambdas(700, 300.0, 900.0), values(700)
+    wide = values(1000)
+    low300 = lambdas(300, 100.0, 350.0), values(300)
+    # every sample wavelength of the special offsets, 360 nm first, among 300 samples: the search and the walk stop ON a sample,
+    # and the first wavelength's lower bound is one of the first few indices
+    on300 = np.unique(np.concatenate([on_samples, lambdas(300 - len(on_samples), 400.0, 830.0)])), values(300)
+    assert len(on300[0]) == 300
+    # SPECTRUM_ZOO_CLUSTER samples inside the 1-nm cell [389, 390), all below lambda_1 = 389.375 nm of offset 0: the walk from the
+    # cell table's entry crosses the whole cluster
+    cluster = np.concatenate([[300.0, 380.0], lambdas(SPECTRUM_ZOO_CLUSTER, 389.01, 389.37), [400.0, 500.0, 700.0]]).astype(f)
+    assert (np.diff(cluster) > 0).all()
+    specs = {}
+    if not fit_lds:
+        specs["irr_dense700"] = b.spectrum_irregular(*dense700, rgb)
+    specs["irr_256"] = b.spectrum_irregular(lambdas(256, 360.0, 830.0), values(256), rgb)
+    specs["irr_255"] = b.spectrum_irregular(lambdas(255, 360.0, 830.0), values(255), rgb)
+    specs["irr_2"] = b.spectrum_irregular([400.0, 700.0], [0.25, 0.75], rgb)
+    specs["irr_inside"] = b.spectrum_irregular([450.0, 500.0, 610.0, 700.0], values(4), rgb)
+    specs["irr_below"] = b.spectrum_irregular([100.0, 200.0, 300.0], values(3), rgb)
+    specs["irr_above"] = b.spectrum_irregular([900.0, 1000.0, 2000.0], values(3), rgb)
+    specs["irr_on_samples"] = b.spectrum_irregular(on_samples, values(len(on_samples)), rgb)
+    specs["irr_cluster"] = b.spectrum_irregular(cluster, values(len(cluster)), rgb)
+    specs["reg_2"] = b.spectrum_regular(400.0, 700.0, values(2), rgb)
+    specs["reg_narrow"] = b.spectrum_regular(500.0, 510.0, values(11), rgb)
+    if not fit_lds:
+        specs["reg_wide"] = b.spectrum_regular(100.0, 2000.0, wide, rgb)
+    specs["reg_exact"] = b.spectrum_regular(360.0, 830.0, values(17), rgb)
+    specs["up_black"] = b.spectrum_srgb_nonlinear(0.0, 0.0, 0.0)
+    specs["up_sat"] = b.spectrum_srgb_nonlinear(1.0, 0.0, 0.0)
+    specs["up_white"] = b.spectrum_srgb_nonlinear(1.0, 1.0, 1.0)
+    # a chromaticity left of the Meng grid (u < 0): UpsampledContinuousSpectrum::evaluate returns zero (SpectrumTypes.h:241-242)
+    specs["up_outside"] = b.sset.upsampled(spectra.REFLECTANCE, spectra.XYY, 0.05, 0.05, 0.5, rgb=rgb)
+    if not fit_lds:
+        specs["reg_wide_emitted"] = b.sset.regular(100.0, 2000.0, wide, rgb, scale=4.0)
+        # two more spectra without a cell table, for the ends of the device's binary search: irr_low300 lies wholly below the
+        # visible range (the search ends past the last sample)
+        specs["irr_low300"] = b.spectrum_irregular(*low300, rgb)
+        specs["irr_on_samples300"] = b.spectrum_irregular(*on300, rgb)
+    assert not fit_lds or not set(specs) & set(SPECTRUM_ZOO_LARGE)
+
+    mats = {"matte_" + name: b.matte(s) for name, s in specs.items() if name != "reg_wide_emitted"}
+    dense = specs["irr_255" if fit_lds else "irr_dense700"]
+    white = specs["up_white"]                                 # no further upsampled spectrum (384 pool floats each)
+    mats["mirror"] = b.metal(white, dense, specs["irr_256"])                                   # eta and k slots
+    mats["emit_irr_256"] = b.matte(white, emittance=specs["irr_256"])
+    if not fit_lds:
+        mats["emit_reg_wide"] = b.matte(white, emittance=specs["reg_wide_emitted"])
+        # texturizeMat.  Only here: a scene with any texture is shaded by the kernels that read their tables from HBM (launchShade)
+        mats["checker"] = b.matte(b.checker_spectrum(specs["irr_255"], specs["irr_dense700"], (0.0, 0.0), (3.0, 3.0)))
+    for i, m in enumerate(mats.values()):
+        x, z = -1.38 + 0.46 * (i % 6), 1.2 - 0.7 * (i // 6)                   # (the camera sees the floor from z = 1.3 on)
+        b.add_quad([(x, 0.01, z), (x + 0.42, 0.01, z), (x + 0.42, 0.01, z - 0.6), (x, 0.01, z - 0.6)], (0, 1, 0), (1, 0, 0), m)
+    return b.build(cornell_camera(1.0), name="spectrum_zoo_" + ("lds" if fit_lds else "hbm")), specs, mats
 
 
 NESTED_LIBM_FREE = ("sum_of_mix_and_mirror", "mix_of_lambert_and_sum_with_inverse", "sum_of_two_sums", "mix_of_mix_and_glass")

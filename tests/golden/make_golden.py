@@ -329,7 +329,38 @@ def main_mixes(only):
             make(name, scenes.feature_mix(features, 1.0), build, size, size, 8, 2, rays=aimed_rays())
 
 
+def main_spectrum_zoo(only):
+    """Edge-case spectra (scenes.spectrum_zoo, the whole zoo): ContinuousSpectrum::evaluate of the compiled spectral reference on
+    every spectrum at the four special wavelength offsets and 64 random ones, and its BSDF answers (16 queries) for the matte
+    material of every spectrum and for the mirror whose eta and k are the two irregular spectra without a cell table."""
+    spec = ob.load("ref_spectral")
+    if spec is None:
+        raise SystemExit("reference library for spectrum_zoo_kat not built")
+    sc, specs, mats = scenes.spectrum_zoo(False)
+    ref = spec.scene(sc)
+    offsets = scenes.spectrum_zoo_offsets()
+    q = scenes.bsdf_queries(16, 7)
+    # the three spectra that the zoo adds for the ends of the device's search and walk have no stored BSDF answers (the file stays
+    # under 1 MiB): their values are in `eval`, from which the tests rebuild the Lambert answers
+    extra = ("matte_irr_low300", "matte_irr_on_samples300", "matte_irr_cluster")
+    kat = {name: m for name, m in mats.items() if (name.startswith("matte_") and name not in extra) or name == "mirror"}
+    mattes = {name: m for name, m in mats.items() if name.startswith("matte_")}
+    out = dict(scene_arrays(sc))
+    out.update(offsets=offsets, queries=q, spectrum_names=np.array(list(specs)), spectrum_indices=np.array(list(specs.values()), np.uint32),
+               material_names=np.array(list(kat)), material_indices=np.array(list(kat.values()), np.uint32),
+               matte_names=np.array(list(mattes)), matte_indices=np.array(list(mattes.values()), np.uint32),
+               matte_spectra=np.array([list(specs.values()).index(int(sc.materials[m]["spectrum"][0])) for m in mattes.values()], np.uint32),
+               eval=np.stack([spec.eval_spectrum(sc, s, offsets) for s in specs.values()]))
+    for mname, m in kat.items():
+        out["out_" + mname] = np.stack([ref.bsdf_kat(m, q, float(off), 0.5) for off in offsets])
+    np.savez_compressed(os.path.join(HERE, "spectrum_zoo_kat.npz"), **out)
+    print("spectrum_zoo_kat", out["eval"].shape, "non-zero", float((out["eval"] != 0).mean()))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "spectrum_zoo_kat":
+        main_spectrum_zoo(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mixes":
         main_mixes(sys.argv[2:])
         sys.exit(0)

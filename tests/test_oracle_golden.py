@@ -284,3 +284,26 @@ def test_light_sampling_known_answers(oracle_rgb, oracle_spectral, mode):
     env_picks = (g["env_out"][:, 0] < 0).mean()
     assert 0.2 < env_picks < 0.5            # 1 / (1 + number of triangle lights) of the selection samples
     assert len(np.unique(g["zoo_out"][:, 0])) > 2
+
+
+def test_spectrum_zoo_known_answers(oracle_spectral):
+    """Edge-case spectra (scenes.spectrum_zoo; tests/golden/spectrum_zoo_kat.npz from the compiled spectral reference): its
+    ContinuousSpectrum::evaluate on every spectrum — irregular with 2 to 700 samples, inside / outside the visible range, sample
+    wavelengths on tabulated ones, regular narrower and wider than [360, 830], upsampled with 0, 3 and 4 points — at offsets 0, 0.37,
+    0.5, 1 - 2^-24 and 64 random ones, and its BSDF answers for the matte material of every spectrum and a mirror with irregular eta
+    and k: every float bit-equal, none NaN."""
+    g = load_golden("spectrum_zoo_kat")
+    scene = scene_from_golden(g)
+    offsets = g["offsets"]
+    assert [float(o) for o in offsets[:4]] == [0.0, float(np.float32(0.37)), 0.5, 1.0 - 2.0 ** -24] and len(offsets) == 68
+    assert not np.isnan(g["eval"]).any()
+    for name, s, want in zip(g["spectrum_names"], g["spectrum_indices"], g["eval"]):
+        got = oracle_spectral.eval_spectrum(scene, int(s), offsets)
+        assert got.view(np.uint32).tobytes() == want.view(np.uint32).tobytes(), str(name)
+    assert {int(scene.spectra["reserved"][s]) for n, s in zip(g["spectrum_names"], g["spectrum_indices"]) if str(n).startswith("up_")} == {0, 3, 4}
+    sc = oracle_spectral.scene(scene)
+    for name, m in zip(g["material_names"], g["material_indices"]):
+        want = g["out_" + str(name)]
+        got = np.stack([sc.bsdf_kat(int(m), g["queries"], float(off), 0.5) for off in offsets])
+        assert_bit_equal(got, want, "spectrum zoo " + str(name))
+        assert (want[:, :, 3] != 0).mean() > 0.5, name
