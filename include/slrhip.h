@@ -1493,6 +1493,61 @@ int slrhip_set_vertices(slrhip_ctx* ctx, const slrhip_vertex* device_src, uint32
 /* The SLRHIP_GEOMETRY_* bits of the calls since the last read, then cleared; waits for `stream`.  0 before any scene.              */
 int slrhip_geometry_status(slrhip_ctx* ctx, uint32_t* bits, void* stream);
 
+/* ---- changing materials, spectra and lights without a scene upload ---------------------------------------------------------------
+ * The last part of a scene description that a second frame could only change through slrhip_upload_scene: a wall's colour, a lobe's
+ * roughness, a lamp's spectrum or intensity, a lamp switched on or off, a checker texture's spectra and mapping, a MULTI record's
+ * factors, a material's type.  slrhip_set_materials takes the WHOLE tables again — materials, spectra, spectrum data, textures, in the
+ * types and with the meaning of the slrhip_scene_desc fields of the same names, all HOST memory — and replaces the scene's.  The tree,
+ * the kept geometry (SLRHIP_FLAG_DYNAMIC_GEOMETRY), slrhip_rebuild_top_level's tables, the environment, the camera, the image
+ * textures' texels and everything accumulated since slrhip_render_begin (sensor, statistics, clamp, feature, albedo and motion
+ * state) stay; samples rendered after the call see the new tables.
+ *
+ * The contract, as for slrhip_set_vertices: from the call on the context is indistinguishable, in every bit of every frame, query,
+ * feature and albedo buffer and counter, from a context freshly uploaded with the scene description whose four tables are the call's.
+ *
+ * The light list.  Triangles whose material has an emittance are the scene's lights, in triangle order.  While the set of emitting
+ * materials (among those that triangles name) stays as it is, the call does no per-triangle work and runs on every context.  When
+ * it changes, the list is rebuilt ON THE DEVICE from the kept index and vertex arrays — a ballot / scan / scatter over the triangles,
+ * no atomics, the order taken from the triangle index — which needs a context that keeps its geometry (SLRHIP_FLAG_DYNAMIC_GEOMETRY,
+ * and a scene slrhip_set_vertices covers).  The light distribution is uniform (every light's importance is 1), so its tables have a
+ * closed form, PMF[i] = 1 / n and CDF[i] = i / n, which is bit for bit the upload's compensated sum for n <= 2^24.
+ *
+ * Ordering.  The call first waits for the device (albedo, feature and query calls may still read the old tables); it may allocate and
+ * it copies from the host, so it can NOT be captured in a graph — like slrhip_set_environment, unlike slrhip_set_vertices.  Its launches
+ * run on `stream`.  The library caches no graph across calls, so none outlives the tables.
+ *
+ * Errors, decided on the host, synchronous, with nothing changed.  SLRHIP_ERR_INVALID_ARGUMENT: a null context or descriptor, non-zero
+ * `reserved`, a null material or spectrum table, num_materials or num_textures other than the uploaded scene's (triangles name
+ * materials by index, and texture coordinates exist only if the scene had textures), and everything slrhip_upload_scene refuses these
+ * tables for, with its code and message.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.  SLRHIP_ERR_UNSUPPORTED: a texture that
+ * changes its kind, an IMAGE_SPECTRUM texture that changes width, height or first texel, a material whose alpha-map assignment
+ * changes (the leaf records carry it), an emitting material on an instanced triangle, no emitting triangle and no environment, more
+ * than 2^24 lights, a change of the emitting set in a context that does not keep its geometry.  A HIP failure after these checks
+ * leaves the context without a scene, as a failed upload does.                                                                    */
+typedef struct slrhip_materials_desc {
+    const slrhip_material* materials;
+    uint32_t num_materials;               /* as uploaded */
+    const slrhip_spectrum* spectra;
+    uint32_t num_spectra;
+    const float* spectrum_data;
+    uint32_t num_spectrum_data;
+    const slrhip_texture* textures;
+    uint32_t num_textures;                /* as uploaded */
+    uint32_t reserved[2];                 /* 0 */
+} slrhip_materials_desc;
+int slrhip_set_materials(slrhip_ctx* ctx, const slrhip_materials_desc* desc, void* stream);
+
+/* New texels for ONE IMAGE_SPECTRUM texture of the uploaded scene, in place: the next frame of an animated image.  `texture` is its index
+ * in the texture table; width, height and first texel stay as uploaded.  `device_src`: DEVICE memory, 4-byte aligned, [height][width][3]
+ * floats in the stored form of the context's mode — (r, g, b) in RGB mode, (u, v, s) in spectral mode.  Nothing is converted: the
+ * image textures' spectral form is a reflectance upsampling (not slrhip_env_texels_to_uvs) and stays with the caller, as on upload.
+ * SLRHIP_TEXELS_STORE_HALF rounds every float to binary16 first.  One launch, one lane per texel, ordered on `stream`; the call allocates
+ * nothing, copies nothing from the host and does not synchronise, so it can be captured in a graph.  Nothing accumulated is reset.
+ * SLRHIP_ERR_INVALID_ARGUMENT: a null context or pointer, a misaligned pointer, unknown flag bits, a texture index out of range or of a
+ * texture that is no image.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene.                                                        */
+#define SLRHIP_TEXELS_STORE_HALF 1u
+int slrhip_set_texture_texels(slrhip_ctx* ctx, uint32_t texture, const float* device_src, uint32_t flags, void* stream);
+
 const char* slrhip_last_error_string(void);
 int slrhip_version(void);
 

@@ -223,6 +223,31 @@ int slrhip_debug_geometry_update_check2(int32_t have_scene, int32_t dynamic, int
  * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room.                                          */
 int slrhip_debug_geometry(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
 
+/* The checks of slrhip_set_materials (slr_amd/csrc/materials_prep.h, prepareMaterialsUpdate — the function the entry point calls),
+ * evaluated on the HOST without a context: `desc` against the state a context of mode `mode` (SLRHIP_MODE_*) would keep after
+ * uploading `uploaded` (NULL: a context without a scene), which keeps its geometry (geometry_kept != 0) or not; the environment is
+ * `uploaded`'s.  SLRHIP_OK if the call would go ahead, else the code it returns, with the reason in slrhip_last_error_string.  With
+ * facts != NULL and a scene, facts[3 m .. 3 m + 2] receive material m's triangle count, its "used by an instanced triangle" bit and its
+ * alpha-map texture (0xFFFFFFFF: none) — num_facts: room at facts, at least 3 x uploaded->num_materials.  A descriptor the upload's own
+ * material passes refuse returns their code and message.  No GPU is touched and no tree is built.                                    */
+int slrhip_debug_materials_update_check(int32_t mode, const slrhip_scene_desc* uploaded, int32_t geometry_kept, const slrhip_materials_desc* desc,
+                                        uint32_t* facts, size_t num_facts);
+
+/* The tables slrhip_set_materials and slrhip_set_texture_texels replace, read back to HOST memory as 32-bit words.  what:
+ *   0  the summary, 32 words: [0] lights, [1] 1 if the shade tables are staged (they fit the LDS limits), [2 .. 7] the ends of the
+ *      blob's six segments in float4, [8] hasMicrofacet, [9] hasMulti, [10] materials, [11] spectra, [12] floats of the spectrum pool,
+ *      [13] textures, [14] image texels, [15] the largest power of two <= lights, [16] the lights' total importance (float bits),
+ *      [17] float4 of the blob; [24] the launches of the last slrhip_set_materials call (0: none since the upload), [25] 1 if that call
+ *      rebuilt the light list; the rest 0
+ *   1  the material records of the context's mode: DevMaterial, 20 words each (RGB), or DevMaterialS, 8 words each (spectral)
+ *   2  the spectrum records, 8 words each          3  the spectrum pool          4  the lights' PMF, one float each
+ *   5  the lights' CDF, lights + 1 floats           6  the shade-table blob (nothing when the tables are not staged)
+ *   7  the image textures' texels, 3 floats each    8  the texture records, 16 words each      9  the materials' texture slots, 4 words each
+ * The light records and ShadeTri::light have read-outs already (slrhip_debug_geometry what 2 and 3, slrhip_debug_tree what 4).
+ * num_words: room at host_dst, at least that many.  Synchronises; changes nothing.  SLRHIP_ERR_NO_SCENE before slrhip_upload_scene,
+ * SLRHIP_ERR_INVALID_ARGUMENT for a null argument, an unknown `what` or too little room.                                             */
+int slrhip_debug_materials(slrhip_ctx* ctx, uint32_t what, void* host_dst, size_t num_words);
+
 /* The tree builders (slr_amd/csrc/bvh.cpp, sbvh.cpp, bvh_device.hip), as the summary of the two read-outs below names them. */
 #define SLRHIP_TREE_HOST_SAH 0u              /* binned SAH over object partitions, on the host                                    */
 #define SLRHIP_TREE_HOST_SPATIAL_SPLITS 1u   /* the same with spatial splits (SLRHIP_FLAG_BVH_SPATIAL_SPLITS, SLRHIP_BVH=sbvh)   */

@@ -239,6 +239,19 @@ class EnvironmentDesc(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+# slrhip_set_texture_texels' flag (SLRHIP_TEXELS_*)
+TEXELS_STORE_HALF = 1   # round every float to binary16 first
+
+
+class MaterialsDesc(C.Structure):
+    """slrhip_materials_desc: the four tables of slrhip_set_materials, HOST pointers, typed and counted as SceneDesc's fields of the same names."""
+    _fields_ = [("materials", C.c_void_p), ("num_materials", C.c_uint32),
+                ("spectra", C.c_void_p), ("num_spectra", C.c_uint32),
+                ("spectrum_data", C.c_void_p), ("num_spectrum_data", C.c_uint32),
+                ("textures", C.c_void_p), ("num_textures", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # Context.denoise's default sigma_distance: the accepted relative change of the camera distance per pixel of tap offset
 # (DESIGN.md records how it was picked on the Cornell scenes)
 DENOISE_SIGMA_DISTANCE = 0.1
@@ -356,6 +369,15 @@ class Scene:
         d.textures, d.num_textures = (self.textures.ctypes.data if len(self.textures) else None), len(self.textures)
         d.texture_texels, d.num_texture_texels = (texels.ctypes.data if len(texels) else None), len(texels)
         d.instances, d.num_instances = (self.instances.ctypes.data if len(self.instances) else None), len(self.instances)
+        return d
+
+    def materials_desc(self):
+        """The ctypes descriptor of slrhip_set_materials: this scene's material, spectrum and texture tables."""
+        d = MaterialsDesc()
+        d.materials, d.num_materials = self.materials.ctypes.data, len(self.materials)
+        d.spectra, d.num_spectra = self.spectra.ctypes.data, len(self.spectra)
+        d.spectrum_data, d.num_spectrum_data = self.spectrum_data.ctypes.data, len(self.spectrum_data)
+        d.textures, d.num_textures = (self.textures.ctypes.data if len(self.textures) else None), len(self.textures)
         return d
 
 

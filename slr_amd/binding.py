@@ -31,6 +31,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_debug_tree", "slrhip_debug_host_tree", "slrhip_debug_quantize_nodes",
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
+           "slrhip_set_materials", "slrhip_set_texture_texels", "slrhip_debug_materials_update_check", "slrhip_debug_materials",
            "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
@@ -193,6 +194,14 @@ def load_library():
     # (and one from before the vertices of instanced scenes could move lacks this one)
     if path == LIB_PATH or hasattr(lib, "slrhip_debug_geometry_update_check2"):
         lib.slrhip_debug_geometry_update_check2.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    # (and one from before materials could change without an upload lacks these four)
+    for name, argtypes in (("slrhip_set_materials", [C.c_void_p, C.POINTER(abi.MaterialsDesc), C.c_void_p]),
+                           ("slrhip_set_texture_texels", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+                           ("slrhip_debug_materials_update_check", [C.c_int32, C.POINTER(abi.SceneDesc), C.c_int32, C.POINTER(abi.MaterialsDesc),
+                                                                    C.c_void_p, C.c_size_t]),
+                           ("slrhip_debug_materials", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t])):
+        if path == LIB_PATH or hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     if path == LIB_PATH or hasattr(lib, "slrhip_sample_luminance"):
         lib.slrhip_sample_luminance.restype = C.c_float
     # (and one from before the primary pass lacks these two)
@@ -468,6 +477,65 @@ class Context:
                        mesh_levels=more[16:17 + depth].copy(), mesh_level_nodes=read(7, mesh_nodes), mesh_roots=read(9, meshes),
                        packet_boxes=read(10, packets * 8, np.float32).reshape(packets, 2, 4))
         return out
+
+    # ---- changing materials, spectra, textures and lights without a scene upload (slrhip_set_materials / slrhip_set_texture_texels) ----
+    def set_materials(self, scene, stream=None):
+        """Replaces the material, spectrum, spectrum-data and texture tables of the uploaded scene with those of `scene` (an abi.Scene; only
+        its tables are used): slrhip_set_materials.  The tree, the kept geometry and everything accumulated stay; when the set of
+        emitting materials changes the light list is rebuilt on the device, which needs a context that keeps its geometry
+        (abi.FLAG_DYNAMIC_GEOMETRY).  Synchronises the device first."""
+        d = scene.materials_desc()
+        _check(self.lib, self.lib.slrhip_set_materials(self.handle, C.byref(d), self._stream_handle(stream)), "slrhip_set_materials")
+
+    def set_texture_texels_into(self, texture, device_ptr, flags=0, stream=None):
+        """slrhip_set_texture_texels over a DEVICE pointer (an integer address): [height][width][3] float32 of image texture `texture`,
+        4-byte aligned, read in order on `stream`; returns at once."""
+        _check(self.lib, self.lib.slrhip_set_texture_texels(self.handle, texture, device_ptr, flags, self._stream_handle(stream)),
+               "slrhip_set_texture_texels")
+
+    def set_texture_texels(self, texture, texels, store_half=False, stream=None):
+        """New texels for image texture `texture` of the uploaded scene, in place (slrhip_set_texture_texels): [height, width, 3]
+        float32 in the stored form of the context's mode — (r, g, b), or (u, v, s) in spectral mode; store_half=True rounds them to
+        binary16 first.  A torch CUDA tensor (contiguous) is passed without a copy and read in order on `stream` (default:
+        torch.cuda.current_stream()); a numpy array is copied to the device first, and that call synchronises.  The size must be the
+        uploaded image's: the library reads width x height texels."""
+        flags = abi.TEXELS_STORE_HALF if store_half else 0
+        if isinstance(texels, np.ndarray):
+            a = np.ascontiguousarray(texels, np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("texels: a [height, width, 3] array expected")
+            with DeviceBlocks() as dev:
+                self.set_texture_texels_into(texture, dev.put(a), flags, stream)
+                self.synchronize()                     # the staging block is freed on the way out
+            return
+        import torch
+        if not (isinstance(texels, torch.Tensor) and texels.is_cuda and texels.dtype == torch.float32 and texels.dim() == 3
+                and texels.shape[2] == 3 and texels.is_contiguous()):
+            raise ValueError("texels: a contiguous [height, width, 3] float32 CUDA tensor (or a numpy array) expected")
+        if texels.device.index != self.device:
+            raise SlrHipError("set_texture_texels: the tensor is on device %r, the context on device %d" % (texels.device.index, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.set_texture_texels_into(texture, texels.data_ptr(), flags, s)
+
+    def debug_materials(self):
+        """Diagnostic (slrhip_debug_materials): the tables set_materials and set_texture_texels replace, as a dict — lights, staged (the
+        shade tables fit the LDS limits), table_end [6], has_microfacet, has_multi, light_pow2, importance, launches (of the last
+        set_materials call), rebuilt (that call rebuilt the light list), materials [m, 20 or 8] uint32, spectra [s, 8] uint32,
+        pool float32, pmf, cdf, blob [b, 4] uint32, texels [t, 3] float32, textures [n, 16] uint32, mat_tex [m, 4] int32.  Synchronises."""
+        def read(what, words, dtype=np.uint32):
+            out = np.zeros(words, dtype)
+            _check(self.lib, self.lib.slrhip_debug_materials(self.handle, what, out.ctypes.data, out.nbytes // 4), "slrhip_debug_materials")
+            return out
+        head = read(0, 32)
+        lights, staged = int(head[0]), bool(head[1])
+        nm, ns, pool, nt, texels, blob = int(head[10]), int(head[11]), int(head[12]), int(head[13]), int(head[14]), int(head[17])
+        per = 8 if self.mode == abi.MODE_SPECTRAL else 20
+        return dict(lights=lights, staged=staged, table_end=head[2:8].copy(), has_microfacet=bool(head[8]), has_multi=bool(head[9]),
+                    light_pow2=int(head[15]), importance=head[16:17].view(np.float32)[0], launches=int(head[24]), rebuilt=bool(head[25]),
+                    materials=read(1, nm * per).reshape(nm, per), spectra=read(2, ns * 8).reshape(ns, 8), pool=read(3, pool, np.float32),
+                    pmf=read(4, lights, np.float32), cdf=read(5, lights + 1, np.float32), blob=read(6, blob * 4).reshape(blob, 4),
+                    texels=read(7, texels * 3, np.float32).reshape(texels, 3), textures=read(8, nt * 16).reshape(nt, 16),
+                    mat_tex=read(9, nm * 4, np.int32).reshape(nm, 4))
 
     def set_camera(self, camera):
         """Replaces the camera of the uploaded scene (slrhip_set_camera; an abi.Camera): later launches see it, nothing is reset."""
@@ -1182,6 +1250,23 @@ def geometry_update_check2(have_scene, dynamic, instanced_kept, tree_builder, nu
     lib = load_library()
     _check(lib, lib.slrhip_debug_geometry_update_check2(int(have_scene), int(dynamic), int(instanced_kept), tree_builder, num_instances, num_vertices,
                                                         device_src, first, count), "slrhip_debug_geometry_update_check2")
+
+
+def materials_update_check(mode, uploaded, geometry_kept, scene, reserved=(0, 0), want_facts=False):
+    """slrhip_debug_materials_update_check: the checks of Context.set_materials on the HOST, without a context — the tables of `scene` (an
+    abi.Scene, an abi.MaterialsDesc, or None) against a context of `mode` that uploaded `uploaded` (an abi.Scene, or None: no scene) and
+    keeps its geometry or not.  Raises SlrHipError as the call would; with want_facts returns [materials, 3] uint32: triangle count, used by
+    an instanced triangle, alpha-map texture (0xFFFFFFFF: none)."""
+    lib = load_library()
+    up = uploaded.desc(mode) if uploaded is not None else None
+    d = scene.materials_desc() if isinstance(scene, abi.Scene) else scene
+    if isinstance(scene, abi.Scene):
+        d.reserved[0], d.reserved[1] = reserved
+    facts = np.zeros((len(uploaded.materials) if uploaded is not None else 0, 3), np.uint32)
+    _check(lib, lib.slrhip_debug_materials_update_check(mode, C.byref(up) if up is not None else None, int(bool(geometry_kept)),
+                                                        C.byref(d) if d is not None else None, facts.ctypes.data if want_facts and facts.size else None,
+                                                        facts.size), "slrhip_debug_materials_update_check")
+    return facts if want_facts else None
 
 
 def instance_world_box(mesh_lo, mesh_hi, local_to_world):

@@ -44,4 +44,9 @@ struct GeometryUpdate {
 // The launches of one call, in order on `stream`; returns how many there were.
 uint32_t launchGeometryUpdate(const GeometryUpdate& u, hipStream_t stream);
 
+// k_geometry_lights alone: the light records (both copies) of the lights whose `tri` and `material` words stand, from the kept vertices.
+// Reads u.numLights, lightTris, stagedLights, triangles, vertices, numTriangles, numVertices.  slrhip_set_materials fills a rebuilt
+// light list with it.  Returns the launches (0 without lights).
+uint32_t launchGeometryLights(const GeometryUpdate& u, hipStream_t stream);
+
 } // namespace slrhip

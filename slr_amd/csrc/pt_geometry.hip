@@ -305,12 +305,18 @@ uint32_t launchInstancedRefit(const GeometryUpdate& u, hipStream_t stream) {
 
 } // namespace
 
+uint32_t launchGeometryLights(const GeometryUpdate& u, hipStream_t stream) {
+    if (!u.numLights) return 0u;
+    hipLaunchKernelGGL(k_geometry_lights, gridOf(u.numLights, 256u), dim3(256), 0, stream, u);
+    return 1u;
+}
+
 uint32_t launchGeometryUpdate(const GeometryUpdate& u, hipStream_t stream) {
     uint32_t launches = 0;
     hipLaunchKernelGGL(k_vertices_store, gridOf(u.count, 256u), dim3(256), 0, stream, u); ++launches;
     hipLaunchKernelGGL(k_geometry_leaves, gridOf(u.numLeafTris, 256u), dim3(256), 0, stream, u); ++launches;
     hipLaunchKernelGGL(k_geometry_triangles, gridOf(u.numTriangles, 256u), dim3(256), 0, stream, u); ++launches;
-    if (u.numLights) { hipLaunchKernelGGL(k_geometry_lights, gridOf(u.numLights, 256u), dim3(256), 0, stream, u); ++launches; }
+    launches += launchGeometryLights(u, stream);
     if (u.numInstances) return launches + launchInstancedRefit(u, stream);
     // from the deepest level to the root; consecutive levels that fit one workgroup share a launch (as launchInstanceUpdate does)
     for (uint32_t level = u.numLevels; level-- > 0u;) {

@@ -35,13 +35,6 @@ struct KahanF {
     }
 };
 
-// What the material pass learns about each material that later passes need.
-struct MaterialFacts {
-    std::vector<char> emitting;
-    std::vector<int32_t> alphaOfMaterial;         // alpha texture of the material, -1 = none
-    bool anyAlpha = false;
-};
-
 // --- the descriptor's own consistency: sizes, the Meng-15 tables, the environment map, triangle indices ------------------------
 int checkDescriptor(const slrhip_scene_desc& d, bool spectral, std::string* err) {
     if (!d.vertices || !d.triangles || !d.materials || !d.spectra || d.num_triangles == 0 || d.num_vertices == 0)
@@ -75,8 +68,13 @@ int checkDescriptor(const slrhip_scene_desc& d, bool spectral, std::string* err)
     return SLRHIP_OK;
 }
 
+} // namespace
+
 // --- textures: checkerboard spectrum / float / normal textures, image textures --------------------------------
-int prepareTextures(const slrhip_scene_desc& d, bool spectral, PreparedScene& p, bool* anyImageTexture, std::string* err) {
+int prepareTextures(const slrhip_scene_desc& d, bool spectral, const KeptTexels* kept, PreparedScene& p, bool* anyImageTexture, std::string* err) {
+    const bool haveTexels = kept ? kept->numTexels != 0 : d.texture_texels != nullptr;
+    const uint64_t numTexels = kept ? kept->numTexels : d.num_texture_texels;
+    const bool haveUpsampling = kept ? kept->upsampling : d.upsampling != nullptr;
     const uint32_t numTextures = d.textures ? d.num_textures : 0u;
     if (numTextures > 32767u) return reject(err, SLRHIP_ERR_UNSUPPORTED, "more than 32767 textures");
     p.textures.resize(numTextures);
@@ -103,9 +101,9 @@ int prepareTextures(const slrhip_scene_desc& d, bool spectral, PreparedScene& p,
         else if (t.kind == SLRHIP_TEXTURE_IMAGE_SPECTRUM) {
             // ImageSpectrumTexture: width, height and the first texel travel in the record (DevTexture, device_types.h)
             const uint64_t w = t.reserved[0], h = t.reserved[1], first = t.reserved[2];
-            if (w == 0 || h == 0 || w > 65535 || h > 65535 || !d.texture_texels || first + w * h > d.num_texture_texels)
+            if (w == 0 || h == 0 || w > 65535 || h > 65535 || !haveTexels || first + w * h > numTexels)
                 return reject(err, SLRHIP_ERR_INVALID_ARGUMENT, "image texture outside slrhip_scene_desc::texture_texels");
-            if (spectral && !d.upsampling)
+            if (spectral && !haveUpsampling)
                 return reject(err, SLRHIP_ERR_INVALID_ARGUMENT, "image textures in spectral mode need slrhip_scene_desc::upsampling");
             dt.spec0 = (int32_t)w; dt.spec1 = (int32_t)h; dt.pad = (uint32_t)first;
             *anyImageTexture = true;
@@ -113,7 +111,7 @@ int prepareTextures(const slrhip_scene_desc& d, bool spectral, PreparedScene& p,
         else if (t.kind != SLRHIP_TEXTURE_CHECKER_FLOAT) return reject(err, SLRHIP_ERR_UNSUPPORTED, "unknown texture kind");
         p.textures[i] = dt;
     }
-    if (*anyImageTexture) p.texTexels.assign(d.texture_texels, d.texture_texels + (size_t)d.num_texture_texels * 3);
+    if (*anyImageTexture && !kept) p.texTexels.assign(d.texture_texels, d.texture_texels + (size_t)d.num_texture_texels * 3);
     return SLRHIP_OK;
 }
 
@@ -148,6 +146,8 @@ int prepareMaterialTextures(const slrhip_scene_desc& d, PreparedScene& p, Materi
     }
     return SLRHIP_OK;
 }
+
+namespace {
 
 // MultiBSDF of two earlier materials — single lobes, or MULTI records of single lobes (include/slrhip.h); the record carries
 // indices, scales, flags
@@ -229,6 +229,8 @@ DevMaterialS spectralRecord(const DevMaterial& dm, int32_t a, int32_t b, int32_t
     ds.spec[0] = a; ds.spec[1] = b; ds.spec[2] = c; ds.spec[3] = emittance;
     return ds;
 }
+
+} // namespace
 
 // --- materials: one record per mode ----------------------------------------------------------------------------------------------
 int prepareMaterials(const slrhip_scene_desc& d, bool spectral, PreparedScene& p, MaterialFacts& f, std::string* err) {
@@ -316,6 +318,24 @@ int prepareSpectra(const slrhip_scene_desc& d, bool spectral, PreparedScene& p, 
     while (pool.size() % 4) pool.push_back(0.0f);          // the shade kernel stages the pool into LDS 16 bytes at a time
     return SLRHIP_OK;
 }
+
+// --- what slrhip_set_materials needs to know about the triangles: a histogram by material ---------------------------------------
+MaterialUsage materialUsage(const slrhip_scene_desc& d, const MaterialFacts& f) {
+    MaterialUsage u;
+    u.triangles.assign(d.num_materials, 0u);
+    u.instanced.assign(d.num_materials, 0);
+    u.alpha = f.alphaOfMaterial;
+    u.emitting = f.emitting;
+    for (uint32_t i = 0; i < d.num_triangles; ++i) ++u.triangles[d.triangles[i].material];
+    for (uint32_t k = 0; k < (d.instances ? d.num_instances : 0u); ++k) {
+        const slrhip_instance& in = d.instances[k];
+        for (uint32_t t = 0; t < in.num_triangles && (uint64_t)in.first_triangle + t < d.num_triangles; ++t)
+            u.instanced[d.triangles[in.first_triangle + t].material] = 1;
+    }
+    return u;
+}
+
+namespace {
 
 // --- accelerator -------------------------------------------------------------------------------------------------------------------
 // Host build (binned SAH, bvh.cpp / spatial splits, sbvh.cpp) unless the context asks for the device build (bvh_device.hip: LBVH,
@@ -460,6 +480,8 @@ void prepareUpsampling(const slrhip_scene_desc& d, PreparedScene& p) {
     p.gridWidth = t->grid_width; p.gridHeight = t->grid_height;
 }
 
+} // namespace
+
 // --- the tables the shade kernels stage in LDS, packed in the order of ShadeLds' segments (DevScene::shadeTables) ---------------
 void packShadeTables(bool spectral, PreparedScene& p) {
     p.tablesFit = p.materials.size() <= (size_t)kLdsMaterials && p.lightTris.size() <= (size_t)kLdsLights &&
@@ -484,8 +506,6 @@ void packShadeTables(bool spectral, PreparedScene& p) {
     append(p.lightCDF.data(), p.lightCDF.size() * sizeof(float));
     while (seg < 6) { p.tableEnd[seg] = (uint32_t)blob.size(); ++seg; }
 }
-
-} // namespace
 
 // --- camera constants, PerspectiveCamera.cpp:15-24, :55 -------------------------------------------------------------------------
 DevCamera prepareCamera(const slrhip_camera& c) {
@@ -523,10 +543,11 @@ int prepareScene(const slrhip_scene_desc& d, const slrhip_config& config, Prepar
     MaterialFacts facts;
     bool anyImageTexture = false;
     PREP_TRY(checkDescriptor(d, spectral, err));
-    PREP_TRY(prepareTextures(d, spectral, p, &anyImageTexture, err));
+    PREP_TRY(prepareTextures(d, spectral, nullptr, p, &anyImageTexture, err));
     PREP_TRY(prepareMaterialTextures(d, p, facts, err));
     PREP_TRY(prepareMaterials(d, spectral, p, facts, err));
     PREP_TRY(prepareSpectra(d, spectral, p, err));
+    p.usage = materialUsage(d, facts);
     PREP_TRY(prepareTree(d, config, facts, p, err));
     PREP_TRY(prepareTriangles(d, facts, p, err));
     prepareTexcoords(d, facts, p);

@@ -14,6 +14,21 @@ namespace slrhip {
 
 enum class TreeBuild { Host, Device, Instanced };
 
+// What the material pass learns about each material that later passes need.
+struct MaterialFacts {
+    std::vector<char> emitting;
+    std::vector<int32_t> alphaOfMaterial;         // alpha texture of the material, -1 = none
+    bool anyAlpha = false;
+};
+
+// What slrhip_set_materials needs to know about the triangles, per material (materialUsage): the context keeps it from the upload on.
+struct MaterialUsage {
+    std::vector<uint32_t> triangles;              // triangles that name the material
+    std::vector<char> instanced;                  // ... one of them inside an instance's range
+    std::vector<int32_t> alpha;                   // MaterialFacts::alphaOfMaterial
+    std::vector<char> emitting;                   // MaterialFacts::emitting, as the context's light list stands
+};
+
 struct PreparedScene {
     std::vector<DevTexture> textures;
     std::vector<float> texTexels;                 // the image textures' texels (3 floats each), empty unless one is in use
@@ -48,6 +63,8 @@ struct PreparedScene {
     std::vector<float4> shadeTables;              // DevScene::shadeTables, empty when the tables exceed the LDS limits
     bool tablesFit = false;
     uint32_t tableEnd[6] = {};
+
+    MaterialUsage usage;                          // for slrhip_set_materials (materials_prep.h)
 };
 
 // The builder behind a prepared scene's tree, as include/slrhip_debug.h numbers them (SLRHIP_TREE_*): 0 host SAH, 1 host with spatial
@@ -60,6 +77,19 @@ inline uint32_t treeBuilderOf(const PreparedScene& p) {
 
 // Checks the descriptor and derives every host-side record.  Returns SLRHIP_OK, or an SLRHIP_ERR_* code with the message in *err.
 int prepareScene(const slrhip_scene_desc& d, const slrhip_config& config, PreparedScene* out, std::string* err);
+
+// ---- the passes of prepareScene that slrhip_set_materials runs again on new tables (materials_prep.cpp); messages and codes are the upload's ----
+// The image textures' texels of a scene in place: how many there are and whether the Meng-15 tables are (they stay on the device).
+struct KeptTexels { uint64_t numTexels; bool upsampling; };
+// `kept` == nullptr: the texels and the tables are the descriptor's, and the texels are copied into p.texTexels.
+int prepareTextures(const slrhip_scene_desc& d, bool spectral, const KeptTexels* kept, PreparedScene& p, bool* anyImageTexture, std::string* err);
+int prepareMaterialTextures(const slrhip_scene_desc& d, PreparedScene& p, MaterialFacts& f, std::string* err);
+int prepareMaterials(const slrhip_scene_desc& d, bool spectral, PreparedScene& p, MaterialFacts& f, std::string* err);
+int prepareSpectra(const slrhip_scene_desc& d, bool spectral, PreparedScene& p, std::string* err);
+// Packs p.shadeTables / tablesFit / tableEnd from the records and the light arrays of p (which it sizes the light segments by).
+void packShadeTables(bool spectral, PreparedScene& p);
+// The triangle histogram by material; the triangle and instance ranges have passed the descriptor checks.
+MaterialUsage materialUsage(const slrhip_scene_desc& d, const MaterialFacts& f);
 
 // The camera constants (PerspectiveCamera's constructor, libm on the host): slrhip_upload_scene's and slrhip_set_camera's.
 DevCamera prepareCamera(const slrhip_camera& c);

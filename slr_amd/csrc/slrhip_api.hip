@@ -43,11 +43,6 @@ int deviceError(uint32_t bits) {
     return fail(SLRHIP_ERR_HIP, what);
 }
 
-uint32_t prevPowerOf2(uint32_t x) {   // defines.h:136-143
-    x |= x >> 1; x |= x >> 2; x |= x >> 4; x |= x >> 8; x |= x >> 16;
-    return x - (x >> 1);
-}
-
 } // namespace
 
 // Sum the sharded statistics words (pt_kernels.h: totalIndex).
@@ -211,6 +206,12 @@ static int commitScene(slrhip_ctx* ctx, const slrhip_scene_desc& d, const Prepar
     HIP_TRY(hipMemset(ctx->queryError.ptr, 0, sizeof(uint32_t)));
     bindScene(ctx, d, p, numNodes, quantized);
     ctx->envOwnMap = false;
+    // what slrhip_set_materials checks new tables against
+    ctx->matKept.usage = p.usage;
+    ctx->matKept.textures = p.textures;
+    ctx->matKept.numTexTexels = p.texTexels.size() / 3u;
+    ctx->matKept.upsampling = p.gridWidth != 0;
+    ctx->matLastLaunches = 0; ctx->matLastRebuilt = false;
     ctx->bvhDepth = depth;
     ctx->bvhLeafRefs = leafRefs;
     ctx->treeBuilder = treeBuilderOf(p);

@@ -1,5 +1,5 @@
 // slrhip_ctx.h — the context behind the C ABI of include/slrhip.h and what its translation units share: slrhip_api.hip,
-// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_toplevel.hip, slrhip_geometry.hip, slrhip_diagnostics.hip.  Internal: not installed.
+// slrhip_buffers.hip, slrhip_image.hip, slrhip_environment.hip, slrhip_instances.hip, slrhip_toplevel.hip, slrhip_geometry.hip, slrhip_materials.hip, slrhip_diagnostics.hip.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 
 #include "../../include/slrhip.h"
 #include "bvh.h"
+#include "materials_prep.h"
 #include "pt_clamp.h"
 #include "pt_kernels.h"
 #include "pt_motion.h"
@@ -135,6 +136,12 @@ struct slrhip_ctx {
     bool geoInstanced = false;
     DevArray<uint32_t> geoMeshLevelNodes, geoMeshRoots;
     std::vector<uint32_t> geoMeshLevelFirst;
+    // slrhip_set_materials (slrhip_materials.hip): what it checks new tables against, the emitting bit per material and the workgroup
+    // offsets of its light-list rebuild (allocated by the first call that rebuilds), and its last call for slrhip_debug_materials
+    slrhip::MaterialsKept matKept;
+    DevArray<uint32_t> matEmitMask, matOffsets;
+    uint32_t matLastLaunches = 0;
+    bool matLastRebuilt = false;
     DevArray<slrhip::DevMaterial> materials;
     DevArray<slrhip::DevMaterialS> materialsS;
     DevArray<slrhip::DevSpectrum> spectra;
@@ -236,6 +243,11 @@ int clearStatistics(slrhip_ctx* ctx, hipStream_t stream);
 // the result window's budget (render_plan.cpp, planWindows): 16 GiB by default, SLRHIP_RESULT_WINDOW_MB overrides
 uint64_t resultWindowBudget();
 long autoStripesOverride(); int pairsMask(); uint32_t runLengthOverride();      // overrides of the render plan, each read once per process
+
+inline uint32_t prevPowerOf2(uint32_t x) {   // defines.h:136-143
+    x |= x >> 1; x |= x >> 2; x |= x >> 4; x |= x >> 8; x |= x >> 16;
+    return x - (x >> 1);
+}
 
 inline size_t frameFloats(const RenderParams& rp) { return (size_t)rp.imageWidth * rp.imageHeight * (rp.spectral ? 16 : 3); }
 inline ClampParams clampParams(const slrhip_ctx* ctx) { return ClampParams{ctx->clamp.on ? ctx->clamp.records.ptr : nullptr, ctx->clampLimit, ctx->clampFlags}; }
