@@ -34,7 +34,8 @@ extern "C" {
                             *    (TRACE_BATCH, TRACE_POOL, SPECTRAL_QUAD, QUAD_LAYOUT, slrhip_trace_rays_timed, slrhip_debug_read_rays);
                             *    kernel classes of slrhip_profile = {TRACE, SHADE, TAIL}: a wavefront iteration is two launches;
                             *    slrhip_bsdf_queries moved to slrhip_debug.h.  The number is frozen here: later additions append.
-                            *    Appended since: SLRHIP_FLAG_NO_PRIMARY_PASS (bit 8; the primary pass is on by default).           */
+                            *    Appended since: SLRHIP_FLAG_NO_PRIMARY_PASS (bit 8; the primary pass is on by default),
+                            *    SLRHIP_FLAG_PRIMARY_RING (bit 11).                                                                  */
 
 /* ---- status codes -------------------------------------------------------------- */
 enum {
@@ -351,6 +352,11 @@ typedef struct slrhip_profile {
 } slrhip_profile;
 
 /* config.flags */
+#define SLRHIP_FLAG_PRIMARY_RING 2048u  /* keep the primary pass on the wave-specialised ring kernel (a producer wave makes the camera rays, consumer
+                                         * waves trace them) where it would run the direct kernel (one lane makes, traces and stores a sample:
+                                         * scenes without instances whose tree is not the quantized one).  Same records, same samples, same
+                                         * counters, same frame to the last bit; the comparator of the tests.  Nothing changes where the ring
+                                         * kernel runs anyway, or where the pass is off.                                                      */
 #define SLRHIP_FLAG_DYNAMIC_INSTANCED 1024u /* together with SLRHIP_FLAG_DYNAMIC_GEOMETRY (alone it means nothing): also keep what slrhip_set_vertices
                                          * works from for a scene WITH instances, and accept the call on it.  Memory: as below (a leaf record is
                                          * the top level's or a mesh's) + 4 B per mesh node + 4 B per mesh.  With 512 alone a scene with

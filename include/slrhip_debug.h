@@ -71,6 +71,27 @@ int slrhip_debug_primary_stream_plan(uint32_t num_pixels, uint32_t num_passes, u
  * window of the context bound it: pixels x passes of that window when it ran the pass, 0 when it did not (no plane is bound then).    */
 int slrhip_debug_primary_stream_entries(slrhip_ctx* ctx, uint64_t* entries);
 
+/* The kernel of a window's primary pass (slr_amd/csrc/render_plan.h, PrimaryPlan::kernel), evaluated on the HOST with the function the
+ * render calls: the arguments of slrhip_debug_primary_stream_plan.  *direct = 1 where the pass runs the direct kernel (one lane makes,
+ * traces and stores a sample: scenes without instances whose tree is not the quantized one, without SLRHIP_FLAG_PRIMARY_RING), 0 where it
+ * runs the ring kernel or does not run at all (slrhip_debug_primary_plan's plan[0] tells the two apart).  No GPU is touched.              */
+int slrhip_debug_primary_kernel_plan(uint32_t num_pixels, uint32_t num_passes, uint32_t config_flags, int32_t scene_class, uint32_t* direct);
+
+/* The kernel the primary pass of the context's last window was launched with: 0 = that window ran no pass, 1 = the ring kernel, 2 = the
+ * direct kernel — so that a test can tell that it compared what it meant to.                                                             */
+int slrhip_debug_primary_kernel(slrhip_ctx* ctx, uint32_t* kernel);
+
+/* One launch of the primary pass of the render last begun on `ctx` (slrhip_render_begin: its pixel list, seed, camera and image size),
+ * with the kernel named: `kernel` 0 = ring, 1 = direct.  The launch takes the passes [first_pass, first_pass + num_passes) of a window of
+ * `window_passes` passes that starts at pass 0 of the render, and writes into the caller's DEVICE memory laid out as the window is:
+ * records[pixel x window_passes + pass] = {triangle, t, b1, b2} (16 bytes; in a spectral context the first 16 of 64), and — unless
+ * `streams` is null — streams[the same entry] = the sample's xorshift128 state behind the camera draws (16 bytes).  Entries outside the
+ * launch's passes are not touched.  The rays are counted as any primary launch counts them (slrhip_counters::extension_rays).
+ * Synchronises; a device-side error word set by the launch is SLRHIP_ERR_HIP.  SLRHIP_ERR_UNSUPPORTED: `kernel` = 1 on a scene with
+ * instances or on the quantized tree.  SLRHIP_ERR_INVALID_ARGUMENT as slrhip_debug_primary_entries.                                      */
+int slrhip_debug_primary_pass(slrhip_ctx* ctx, uint32_t kernel, uint32_t first_pass, uint32_t num_passes, uint32_t window_passes, void* records,
+                              void* streams);
+
 /* The camera draws of `n` samples on device `device`, forward and recovered (slr_amd/csrc/pt_camera.h): tuples[4 i ..] = seed, pixel x,
  * pixel y, pass; out[16 i ..] = the draws drawCameraSample makes (p.x, p.y, wavelength offset, wavelength selection, two lens draws; float
  * bits), the four words of the stream it leaves, and the same six draws as recoverCameraDraws rebuilds them from that stream and the

@@ -273,6 +273,7 @@ FLAG_TIME_KERNELS, FLAG_COUNT_TRAVERSAL, FLAG_BVH_DEVICE_BUILD, FLAG_TEST_DEVICE
 FLAG_NO_PRIMARY_PASS = 256      # the primary pass (camera rays traced before a window's iterations) is on by default; this turns it off
 FLAG_DYNAMIC_GEOMETRY = 512     # keep the vertex and index arrays on the device, so that Context.set_vertices can move vertices without an upload
 FLAG_DYNAMIC_INSTANCED = 1024   # with FLAG_DYNAMIC_GEOMETRY: also for scenes with instances (the mesh trees' level list and roots are kept as well)
+FLAG_PRIMARY_RING = 2048        # keep the primary pass on the ring kernel where it would run the direct kernel (same frame; the tests' comparator)
 MAX_STRIPES = 64
 KERNEL_NAMES = ("trace", "shade", "tail")
 

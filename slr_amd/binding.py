@@ -32,7 +32,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
            "slrhip_set_materials", "slrhip_set_texture_texels", "slrhip_debug_materials_update_check", "slrhip_debug_materials",
-           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_primary_kernel_plan", "slrhip_debug_primary_kernel", "slrhip_debug_primary_pass", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -214,6 +214,11 @@ def load_library():
         lib.slrhip_debug_primary_stream_entries.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.slrhip_debug_primary_stream_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]
         lib.slrhip_debug_camera_draws.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    # (and one from before the direct kernel of the primary pass lacks these three)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_primary_pass"):
+        lib.slrhip_debug_primary_kernel_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]
+        lib.slrhip_debug_primary_kernel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.slrhip_debug_primary_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -635,6 +640,18 @@ class Context:
         n = C.c_uint64()
         _check(self.lib, self.lib.slrhip_debug_primary_samples(self.handle, C.byref(n)), "slrhip_debug_primary_samples")
         return n.value
+
+    def primary_kernel(self):
+        """Diagnostic (slrhip_debug_primary_kernel): the kernel of the last window's primary pass: 0 = no pass, 1 = ring, 2 = direct."""
+        k = C.c_uint32(0)
+        _check(self.lib, self.lib.slrhip_debug_primary_kernel(self.handle, C.byref(k)), "slrhip_debug_primary_kernel")
+        return int(k.value)
+
+    def primary_pass(self, kernel, first_pass, num_passes, window_passes, records, streams=0):
+        """Diagnostic (slrhip_debug_primary_pass): one launch of the primary pass of the render last begun, `kernel` 0 = ring, 1 = direct,
+        into the caller's device memory (addresses as integers; streams 0 = no stream plane)."""
+        _check(self.lib, self.lib.slrhip_debug_primary_pass(self.handle, kernel, first_pass, num_passes, window_passes, records, streams or None),
+               "slrhip_debug_primary_pass")
 
     def primary_stream_entries(self):
         """Diagnostic (slrhip_debug_primary_stream_entries): entries of the stream plane the last window bound; 0 = it ran no primary pass."""

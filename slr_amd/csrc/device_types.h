@@ -29,6 +29,10 @@ inline const char* tuningEnv(const char* name) {
 #endif
 }
 
+// The kernel of a window's primary pass: the host's choice (render_plan.h, planPrimary), an argument of launchPrimary (pt_kernels.h).
+// The numbers are what slrhip_debug_primary_kernel reports (include/slrhip_debug.h).
+enum class PrimaryKernel : uint32_t { None = 0, Ring = 1, Direct = 2 };
+
 static const uint32_t kInvalidChild = 0xFFFFFFFFu;
 static const uint32_t kLeafFlag = 0x80000000u;
 static const uint32_t kLeafCountShift = 27;

@@ -300,8 +300,14 @@ int traceWsBlocksPerCU(bool quantizedTree);
 // [firstPass, firstPass + numPasses) of the window (relative to rp.sppBegin) through the wave-specialised consumer, made on the spot
 // by the producer wave; the hit record goes to the sample's entry of the result window (PathBuffers::results, primaryInstance),
 // errors to the render's error word, the ray count to T_EXT_RAYS.  numPixels x numPasses < 2^31 (render_plan.h, planPrimary).
-void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
-                   hipStream_t stream);
+// `kernel` is the plan's choice (render_plan.h, PrimaryPlan::kernel), made on the host: the ring kernel above, or the direct kernel
+// (pt_primary_direct.hip, launchPrimaryDirect: one lane makes, traces and stores one sample; scenes without instances on the float
+// nodes only).  Same records, same streams, same count, to the bit.
+void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, PrimaryKernel kernel,
+                   int numCUs, hipStream_t stream);
+// records / streams: the entry of (pixel 0, firstPass) of the window; streams may be nullptr (no plane)
+void launchPrimaryDirect(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, float4* records,
+                         uint4* streams, int numCUs, hipStream_t stream);
 // ray queries (slrhip_intersect_rays / slrhip_test_visibility) through the same consumer (pt_trace_indexed.hip): rays = n slrhip_ray records (2 x float4);
 // visible == nullptr: closest hit into hits (slrhip_hit) and, if given, instances; else visibility into visible.  n < 2^31.
 void launchQueryWs(const DevScene& sc, const float4* rays, uint32_t n, float4* hits, int32_t* instances, uint32_t* visible, uint32_t* errorWord,

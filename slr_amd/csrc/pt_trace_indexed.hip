@@ -3,7 +3,9 @@
 //
 //   WsQueryIO    ray queries (slrhip_intersect_rays / slrhip_test_visibility): index = entry of the caller's slrhip_ray array
 //   WsFeatureIO  the first-hit trace of the feature, albedo and motion passes: index = sample of the window, camera ray made on the spot
-//   WsPrimaryIO  the primary pass of a render window: the same producer, the path tracer's own hit record
+//   WsPrimaryIO  the primary pass of a render window: the same producer, the path tracer's own hit record — on instanced scenes,
+//                on the quantized tree and with SLRHIP_FLAG_PRIMARY_RING; elsewhere the plan (render_plan.h) names the direct kernel of
+//                pt_primary_direct.hip, where the lane that traces a camera ray makes it, and launchPrimary below hands the launch over
 //
 // A client is a by-value kernel argument, plain data, with
 //   errorWord()              the ERR_* word of its API family
@@ -174,10 +176,17 @@ static void launchPrimaryWith(const DevScene& sc, const PathBuffers& pb, const R
     launchRingWs(sc, io, n, nc, numCUs, stream);
 }
 
-void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, int numCUs,
-                   hipStream_t stream) {
+void launchPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t firstPass, uint32_t numPasses, PrimaryKernel kernel,
+                   int numCUs, hipStream_t stream) {
     const uint32_t n = rp.numPixels * numPasses;
     if (n == 0) return;
+    if (kernel == PrimaryKernel::Direct) {
+        // the plan's choice for scenes without instances on the float nodes (render_plan.h): the same entries of the same planes
+        const size_t first = windowEntry(0u, firstPass, rp.sppCount);
+        launchPrimaryDirect(sc, pb, rp, firstPass, numPasses, pb.results + first * (rp.spectral ? 4u : 1u), pb.primaryRng ? pb.primaryRng + first : nullptr,
+                            numCUs, stream);
+        return;
+    }
     if (pb.primaryRng) launchPrimaryWith<true>(sc, pb, rp, firstPass, numPasses, numCUs, stream);
     else launchPrimaryWith<false>(sc, pb, rp, firstPass, numPasses, numCUs, stream);
 }

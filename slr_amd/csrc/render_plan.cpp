@@ -137,6 +137,7 @@ PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFl
     // 16 B per sample, what an RGB result entry takes: the plane is as large as the window's results, whatever planWindows made of the
     // budget (a single pass may exceed it, and so may its plane).  Not where the pass's producer wave is the limit (render_plan.h).
     p.rngEntries = instanced || quantized ? 0u : (uint64_t)numPixels * sppCount;
+    p.kernel = p.rngEntries && !(configFlags & SLRHIP_FLAG_PRIMARY_RING) ? PrimaryKernel::Direct : PrimaryKernel::Ring;
     return p;
 }
 

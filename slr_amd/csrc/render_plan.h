@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/slrhip.h"
+#include "device_types.h"
 
 namespace slrhip {
 
@@ -61,6 +62,7 @@ WindowPlan planWindow(uint32_t numPixels, uint32_t sppCount, uint32_t runLengthO
 const uint32_t kPrimaryMaxSamples = 0x7FFFFFFFu;        // ring indices of one launch (pt_trace_ws.h, wsProduceIndexed)
 struct PrimaryPlan {
     bool on = false;
+    PrimaryKernel kernel = PrimaryKernel::None;      // the kernel of the pass's launches (below); None: the pass is off
     uint32_t passesPerLaunch = 0;              // numPixels x passesPerLaunch <= kPrimaryMaxSamples
     uint32_t numLaunches = 0;                  // ceil(sppCount / passesPerLaunch)
     uint64_t instanceEntries = 0;              // int32 entries of PathBuffers::primaryInstance: numPixels x sppCount in instanced scenes, else 0
@@ -72,6 +74,11 @@ struct PrimaryPlan {
 // `quantized`: the scene's tree is the quantized one (large scenes).  There and in instanced scenes the pass runs 15 (or 7) consumer waves
 // per producer and the producer wave is its limit: the stream plane stays off (rngEntries 0), the fused start seeds its own stream as
 // before — with the plane grid10m rendered 0.6 % slower, the producer's +30 ms against k_shade's -20 ms.
+// The kernel: exactly where the pass keeps the stream plane — no instances, tree not quantized — it is the direct kernel
+// (pt_primary_direct.hip: the lane that traces a camera ray makes it; the 64 samples of a wave are passes of one pixel and walk the
+// tree together), unless SLRHIP_FLAG_PRIMARY_RING keeps the ring kernel on (the comparator); everywhere else the ring
+// kernel (pt_trace_indexed.hip) as before: the direct kernel's traversal has no quantized-node path, and on large and instanced trees
+// the rays of a pixel part ways at the leaves.
 PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment,
                         bool quantized = false);
 

@@ -385,6 +385,7 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
         pb.primaryRng = ctx->primaryRng.ptr;
     }
     ctx->primaryRngEntries = pb.primaryRng ? ctx->primaryRng.count : 0u;       // what this window bound, not what the plan said
+    ctx->primaryKernel = PrimaryKernel::None;                                  // ... and what it launched (set where the pass is launched, below)
     // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
     // it is asked for zero passes
     launchResetSlots(pb, rp, ctx->firstRenderCall, stream);
@@ -417,9 +418,10 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     if (primary.on) {
         if (timeKernels) { HIP_TRY(hipEventCreate(&primaryTimer.t0)); HIP_TRY(hipEventCreate(&primaryTimer.t1)); HIP_TRY(hipEventRecord(primaryTimer.t0, stream)); }
         for (uint32_t first = 0; first < sppCount; first += primary.passesPerLaunch)
-            launchPrimary(ctx->scene, pb, rp, first, std::min(primary.passesPerLaunch, sppCount - first), ctx->numCUs, stream);
+            launchPrimary(ctx->scene, pb, rp, first, std::min(primary.passesPerLaunch, sppCount - first), primary.kernel, ctx->numCUs, stream);
         if (timeKernels) HIP_TRY(hipEventRecord(primaryTimer.t1, stream));
         HIP_TRY(hipGetLastError());
+        ctx->primaryKernel = primary.kernel;
     }
 
     // The block of kCheckEvery iterations is the same sequence of launches every time (the parity alternates inside it and is

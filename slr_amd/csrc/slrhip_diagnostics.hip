@@ -201,6 +201,57 @@ int slrhip_debug_primary_stream_entries(slrhip_ctx* ctx, uint64_t* entries) {
     return SLRHIP_OK;
 }
 
+// Diagnostic (include/slrhip_debug.h): the kernel of a window's primary pass as renderWindow plans it.
+int slrhip_debug_primary_kernel_plan(uint32_t numPixels, uint32_t numPasses, uint32_t configFlags, int32_t sceneClass, uint32_t* direct) {
+    if (!direct) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_kernel_plan: null argument");
+    *direct = planPrimary(numPixels, numPasses, configFlags, (sceneClass & 1) != 0, (sceneClass & 2) != 0, (sceneClass & 4) != 0, (sceneClass & 8) != 0).kernel ==
+                      PrimaryKernel::Direct
+                  ? 1u
+                  : 0u;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the kernel the last window's primary pass was launched with.
+int slrhip_debug_primary_kernel(slrhip_ctx* ctx, uint32_t* kernel) {
+    if (!ctx || !kernel) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_kernel: null argument");
+    *kernel = (uint32_t)ctx->primaryKernel;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): one launch of the primary pass, either kernel, into the caller's planes.
+int slrhip_debug_primary_pass(slrhip_ctx* ctx, uint32_t kernel, uint32_t firstPass, uint32_t numPasses, uint32_t windowPasses, void* records,
+                              void* streams) {
+    if (!ctx || !records) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_pass: null argument");
+    if (!ctx->haveRender) return fail(SLRHIP_ERR_NO_SCENE, "slrhip_debug_primary_pass: call slrhip_render_begin first");
+    if (kernel > 1u) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_pass: kernel is 0 (ring) or 1 (direct)");
+    RenderParams rp = ctx->params;
+    PathBuffers pb = ctx->buffers;
+    if (numPasses == 0 || (uint64_t)firstPass + numPasses > windowPasses || (uint64_t)rp.numPixels * numPasses > kPrimaryMaxSamples ||
+        (uint64_t)rp.numPixels * windowPasses > 0xFFFFFFFFull)
+        return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_pass: the launch's passes must be 1 or more, inside the window, and under 2^31 samples");
+    if (kernel == 1u && (ctx->scene.instances || ctx->scene.nodesQ))
+        return fail(SLRHIP_ERR_UNSUPPORTED, "slrhip_debug_primary_pass: the direct kernel traces scenes without instances on the float nodes only");
+    if (rp.numSlots == 0) return SLRHIP_OK;       // an empty shard
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    rp.sppBegin = 0; rp.sppCount = windowPasses;
+    pb.results = static_cast<float4*>(records);
+    pb.primaryRng = static_cast<uint4*>(streams);
+    pb.primaryInstance = nullptr;
+    if (ctx->scene.instances) {                   // the ring kernel's instance plane: the context's own, as a window of this size binds it
+        HIP_TRY(ctx->primaryInstance.alloc((size_t)rp.numPixels * windowPasses));
+        pb.primaryInstance = ctx->primaryInstance.ptr;
+    }
+    HIP_TRY(hipMemset(pb.errorWord, 0, sizeof(uint32_t)));
+    launchPrimary(ctx->scene, pb, rp, firstPass, numPasses, kernel ? PrimaryKernel::Direct : PrimaryKernel::Ring, ctx->numCUs, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t bits = 0;
+    HIP_TRY(hipMemcpy(&bits, pb.errorWord, sizeof(bits), hipMemcpyDeviceToHost));
+    if (bits) return fail(SLRHIP_ERR_HIP, "slrhip_debug_primary_pass: device-side error word set: " + std::to_string(bits));
+    return SLRHIP_OK;
+}
+
 // Diagnostic (include/slrhip_debug.h): the camera draws forward and recovered, on the device.
 int slrhip_debug_camera_draws(int32_t device, uint32_t n, const uint32_t* tuples, uint32_t* out) {
     if (!tuples || !out) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_camera_draws: null argument");
