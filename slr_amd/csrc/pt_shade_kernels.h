@@ -444,6 +444,13 @@ __device__ __forceinline__ void stageShadeTables(const DevScene& sc, ShadeLds<SP
 #ifndef SLR_WAVES_RGB
 #define SLR_WAVES_RGB 2
 #endif
+// Measurement builds only (what a wave is worth): -DSLR_WAVES_RGB_CAP=N also CAPS the RGB kernels of the translation unit
+// at N waves per SIMD — the compiler pads the kernel's register allocation so that no more fit.  Never set in the committed build.
+#ifdef SLR_WAVES_RGB_CAP
+#define SLR_SHADE_WAVES(rgb, mf) (rgb) ? SLR_WAVES_RGB : ((mf) ? SLR_WAVES_SPECTRAL_GLOSSY : SLR_WAVES_SPECTRAL), (rgb) ? SLR_WAVES_RGB_CAP : 8
+#else
+#define SLR_SHADE_WAVES(rgb, mf) (rgb) ? SLR_WAVES_RGB : ((mf) ? SLR_WAVES_SPECTRAL_GLOSSY : SLR_WAVES_SPECTRAL)
+#endif
 // The texture behind a material's spectrum slot, evaluated at the hit's texture coordinate.
 //   CheckerBoardSpectrumTexture (checker_board_textures.h:21-24): one of its two constant spectra.  RGB build: their values are in
 //   the texture record; spectral build: evaluated at the path's wavelengths like any other constant (tables in HBM: textured
@@ -510,7 +517,9 @@ struct SlotLoads {
     }
 };
 
-template <class S, bool LDS_TABLES, bool MF, bool MULTI, bool TEX, bool FUSED>
+// TIGHT (k_shade's fused start without the glossy lobes): the visit holds no address of a state record from its loads
+// to its stores.  The same instructions on the same values; set only where the 14 registers decide a wave per SIMD.
+template <class S, bool LDS_TABLES, bool MF, bool MULTI, bool TEX, bool FUSED, bool TIGHT = false>
 __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, const ShadeLds<S::N != 3>& lds,
                                           const float* lightPMF, const float* lightCDF, uint32_t slot, const SlotLoads<S>& in, uint32_t& flags, uint32_t vis,
                                           S& radiance, bool& emitExt, bool& emitShadow, bool& emitRegen) {
@@ -809,21 +818,25 @@ __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers&
         }
 
         // ---- store path state ---------------------------------------------------------------------------
+        // TIGHT: the records' addresses are made again, from a copy of the slot index that the compiler cannot trace back to the index the
+        // state loads used; otherwise it keeps the loads' seven per-lane 64-bit addresses in registers through the whole visit
+        uint32_t slotOut = slot;
+        if constexpr (TIGHT) asm volatile("" : "+v"(slotOut));
         flags |= sp.validBits();
         if (FUSED && emitRegen) {
             radiance = sp.total();                 // accumulated by the caller: nothing of this path needs to reach HBM any more
         }
         else {
-            pb.flags[slot] = flags;
-            sp.end(pb, slot, rp.numSlots, !emitRegen);
+            pb.flags[slotOut] = flags;
+            sp.end(pb, slotOut, rp.numSlots, !emitRegen);
         }
         if (!emitRegen) {
-            pb.rng[(size_t)slot * pb.hdrStride] = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
-            SpecIO<S>::store(pb.alpha, pb.pdfPrev, slot, rp.numSlots, alpha, bsdfPDFprev);
+            pb.rng[(size_t)slotOut * pb.hdrStride] = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
+            SpecIO<S>::store(pb.alpha, pb.pdfPrev, slotOut, rp.numSlots, alpha, bsdfPDFprev);
         }
         if (emitExt) {
-            pb.rayOrg[(size_t)slot * pb.rayStride] = make_float4(rayOrg.x, rayOrg.y, rayOrg.z, rayTmin);
-            pb.rayDir[(size_t)slot * pb.rayStride] = make_float4(rayDir.x, rayDir.y, rayDir.z, INFINITY);
+            pb.rayOrg[(size_t)slotOut * pb.rayStride] = make_float4(rayOrg.x, rayOrg.y, rayOrg.z, rayTmin);
+            pb.rayDir[(size_t)slotOut * pb.rayStride] = make_float4(rayDir.x, rayDir.y, rayDir.z, INFINITY);
         }
     }
 }
@@ -976,10 +989,14 @@ struct StartLds {
 // that plane, render_plan.h) instead of seeding its own.  A template argument for the reason PRIMARY is one.
 template <class S, bool LDS_TABLES, bool MF, bool MULTI = false, bool TEX = false, bool PRIMARY = false, bool RESUME = false>
 __global__ __launch_bounds__(kShadeBlock)
-__attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_SPECTRAL_GLOSSY : SLR_WAVES_SPECTRAL)))) void k_shade(DevScene sc, PathBuffers pb, RenderParams rp, uint32_t parity) {
+__attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shade(DevScene sc, PathBuffers pb, RenderParams rp, uint32_t parity) {
     __shared__ ShadeLds<S::N != 3> lds;
     __shared__ PushLds pushLds;
     __shared__ StartLds start;
+    // The fused start without the glossy lobes runs at 4 waves per SIMD (128 VGPRs, no scratch) if nothing of one trip occupies registers
+    // through the other; two things did, 140 VGPRs' worth, and are undone where kTight is set.  The other instantiations
+    // are 2 to 3 waves either way and keep their code.
+    constexpr bool kTight = PRIMARY && !MF;
     const uint32_t slot = blockIdx.x * kShadeBlock + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 
@@ -1031,8 +1048,17 @@ __attribute__((amdgpu_waves_per_eu(S::N == 3 ? SLR_WAVES_RGB : (MF ? SLR_WAVES_S
     for (uint32_t trip = 0; trip < 2u; ++trip) {
     bool emitExt = false, emitShadow = false, pathEnded = false;
     S radiance;
+    // kTight: each trip reads the scene's uniform scalars through a copy of its own, opaque to the compiler.  The trips are a loop until
+    // it is unrolled, and loop-invariant code motion runs first: it lifts the float conversions and quotients of these words out of the
+    // visit, where they then sit in seven vector registers (the chip has no scalar float unit) from the top of the kernel to trip 1
+    DevScene scT;
+    if constexpr (kTight) {
+        scT = sc;
+        asm volatile("" : "+s"(scT.envWidth), "+s"(scT.envHeight), "+s"(scT.envMapWidth), "+s"(scT.envMapHeight), "+s"(scT.aggImportance));
+    }
+    const DevScene& scV = kTight ? scT : sc;
     if (curActive)
-        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true>(sc, pb, rp, lds, lightPMF, lightCDF, curSlot, in, flags, curVis, radiance, emitExt, emitShadow, pathEnded);
+        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true, kTight>(scV, pb, rp, lds, lightPMF, lightCDF, curSlot, in, flags, curVis, radiance, emitExt, emitShadow, pathEnded);
 
     // ---- a path that ended: its contribution goes to the result window, in the same launch ------------------------------------
     if (pathEnded) {
