@@ -35,7 +35,7 @@ extern "C" {
                             *    kernel classes of slrhip_profile = {TRACE, SHADE, TAIL}: a wavefront iteration is two launches;
                             *    slrhip_bsdf_queries moved to slrhip_debug.h.  The number is frozen here: later additions append.
                             *    Appended since: SLRHIP_FLAG_NO_PRIMARY_PASS (bit 8; the primary pass is on by default),
-                            *    SLRHIP_FLAG_PRIMARY_RING (bit 11).                                                                  */
+                            *    SLRHIP_FLAG_PRIMARY_RING (bit 11), SLRHIP_FLAG_TRACE_ALL_SHADOW_RAYS (bit 12).                      */
 
 /* ---- status codes -------------------------------------------------------------- */
 enum {
@@ -345,13 +345,19 @@ enum {
 typedef struct slrhip_profile {
     uint64_t launches[SLRHIP_KERNEL_COUNT];
     double   milliseconds[SLRHIP_KERNEL_COUNT];   /* sum of HIP-event durations on the render stream  */
-    uint64_t rays[2];                             /* [0] extension (closest-hit), [1] shadow rays traced */
+    uint64_t rays[2];                             /* [0] extension (closest-hit), [1] shadow rays cast (all of them traced in a COUNT_TRAVERSAL context) */
     uint64_t nodes[2];                            /* 4-wide nodes fetched (128 B each; 64 B quantized)  */
     uint64_t triangles[2];                        /* leaf triangles tested (48 B each)                 */
     uint64_t slot_visits;                         /* live slots processed by SHADE                     */
 } slrhip_profile;
 
 /* config.flags */
+#define SLRHIP_FLAG_TRACE_ALL_SHADOW_RAYS 4096u /* trace every shadow ray.  By default the RGB shade kernel does not trace a light sample that decides
+                                         * nothing: one whose contribution is exactly zero in every component (the light seen from behind, the
+                                         * sample below the surface's horizon) and whose compensated add would leave the path's sum bit for bit
+                                         * as it is.  Such a ray is still counted in slrhip_counters::shadow_rays.  Same samples, same counters,
+                                         * same frame to the last bit; the comparator of the tests.  (SLRHIP_FLAG_COUNT_TRAVERSAL contexts trace
+                                         * every ray as well: their per-ray figures are defined over all of them.)                          */
 #define SLRHIP_FLAG_PRIMARY_RING 2048u  /* keep the primary pass on the wave-specialised ring kernel (a producer wave makes the camera rays, consumer
                                          * waves trace them) where it would run the direct kernel (one lane makes, traces and stores a sample:
                                          * scenes without instances whose tree is not the quantized one).  Same records, same samples, same

@@ -54,6 +54,18 @@ int slrhip_debug_primary_plan(uint32_t num_pixels, uint32_t num_passes, uint32_t
  * for a working one.  Synchronises.                                                                                                 */
 int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples);
 
+/* How many light samples since slrhip_render_begin the shade kernel did not trace because they decide nothing (a contribution of exact
+ * zeros that leaves the path's Kahan sum as it is).  They are part of slrhip_counters::shadow_rays — the rays the
+ * algorithm casts — and of no traversal figure.  0 in spectral contexts, with SLRHIP_FLAG_TRACE_ALL_SHADOW_RAYS and with
+ * SLRHIP_FLAG_COUNT_TRAVERSAL.  Synchronises.                                                                                        */
+int slrhip_debug_shadow_skipped(slrhip_ctx* ctx, uint64_t* rays);
+
+/* The predicate the shade kernel decides that with (slr_amd/csrc/pt_device.h, deadLightSample), on device `device`, for `n` triples:
+ * triples[9 i ..] = the path's radiance sum r[3], its compensation c[3], the light sample's contribution[3]; dead[i] = 1 where every
+ * component of the contribution is +0 or -0 AND the compensated add of it leaves all six words of (r, c) bit for bit as they are,
+ * else 0.  Host arrays; synchronises.                                                                                                */
+int slrhip_debug_dead_light_samples(int32_t device, uint32_t n, const float* triples, uint32_t* dead);
+
 /* Where a launch of the primary pass puts its samples (slr_amd/csrc/pt_kernels.h, primaryLaunchEntry), evaluated on the HOST with the very
  * function its kernel calls: the launch takes the passes [first_pass, first_pass + num_passes) of a window of `window_passes` passes over
  * `num_pixels` pixels and numbers its samples with the pass fastest; entries[i] = the entry of sample i in the result window and in the

@@ -274,6 +274,7 @@ FLAG_NO_PRIMARY_PASS = 256      # the primary pass (camera rays traced before a 
 FLAG_DYNAMIC_GEOMETRY = 512     # keep the vertex and index arrays on the device, so that Context.set_vertices can move vertices without an upload
 FLAG_DYNAMIC_INSTANCED = 1024   # with FLAG_DYNAMIC_GEOMETRY: also for scenes with instances (the mesh trees' level list and roots are kept as well)
 FLAG_PRIMARY_RING = 2048        # keep the primary pass on the ring kernel where it would run the direct kernel (same frame; the tests' comparator)
+FLAG_TRACE_ALL_SHADOW_RAYS = 4096  # trace the light samples that decide nothing as well (same frame, same counters; the tests' comparator)
 MAX_STRIPES = 64
 KERNEL_NAMES = ("trace", "shade", "tail")
 

@@ -32,7 +32,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
            "slrhip_set_materials", "slrhip_set_texture_texels", "slrhip_debug_materials_update_check", "slrhip_debug_materials",
-           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_primary_kernel_plan", "slrhip_debug_primary_kernel", "slrhip_debug_primary_pass", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_shadow_skipped", "slrhip_debug_dead_light_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_primary_kernel_plan", "slrhip_debug_primary_kernel", "slrhip_debug_primary_pass", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -219,6 +219,10 @@ def load_library():
         lib.slrhip_debug_primary_kernel_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]
         lib.slrhip_debug_primary_kernel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.slrhip_debug_primary_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    # (and one from before dead light samples went untraced lacks these two)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_shadow_skipped"):
+        lib.slrhip_debug_shadow_skipped.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.slrhip_debug_dead_light_samples.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.slrhip_bsdf_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.slrhip_sample_seed.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.slrhip_sample_seed.restype = C.c_int32
@@ -639,6 +643,12 @@ class Context:
         """Diagnostic (slrhip_debug_primary_samples): samples since render_begin whose first hit came from the primary pass's record."""
         n = C.c_uint64()
         _check(self.lib, self.lib.slrhip_debug_primary_samples(self.handle, C.byref(n)), "slrhip_debug_primary_samples")
+        return n.value
+
+    def shadow_skipped(self):
+        """Diagnostic (slrhip_debug_shadow_skipped): light samples since render_begin that were counted as shadow rays and not traced."""
+        n = C.c_uint64()
+        _check(self.lib, self.lib.slrhip_debug_shadow_skipped(self.handle, C.byref(n)), "slrhip_debug_shadow_skipped")
         return n.value
 
     def primary_kernel(self):

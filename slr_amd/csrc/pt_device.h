@@ -186,6 +186,18 @@ SLR_DEV void kahanAdd(S& result, S& comp, const S& value) {
     comp = (sumTemp - result) - cInput;
     result = sumTemp;
 }
+// A light sample whose contribution decides nothing (k_shade): every component of `contrib` is a zero of either sign
+// (tested on the bits: a NaN, an infinity and a denormal are no zero whatever the float mode), AND adding it to the path's Kahan pair
+// leaves all six words as they are.  The second half is no formality: with value = 0 the add computes result + (-comp), which moves
+// `result` where comp sits on a rounding boundary of it.  The add is done on copies and the bits are compared; no case is reasoned away.
+SLR_DEV bool deadLightSample(const RGB& result, const RGB& comp, const RGB& contrib) {
+    if (((__float_as_uint(contrib.r) | __float_as_uint(contrib.g) | __float_as_uint(contrib.b)) << 1) != 0u) return false;
+    RGB r = result, c = comp;
+    kahanAdd(r, c, contrib);
+    return ((__float_as_uint(r.r) ^ __float_as_uint(result.r)) | (__float_as_uint(r.g) ^ __float_as_uint(result.g)) |
+            (__float_as_uint(r.b) ^ __float_as_uint(result.b)) | (__float_as_uint(c.r) ^ __float_as_uint(comp.r)) |
+            (__float_as_uint(c.g) ^ __float_as_uint(comp.g)) | (__float_as_uint(c.b) ^ __float_as_uint(comp.b))) == 0u;
+}
 
 // ---- RNGs/XORShiftRNG.cpp:21-36, Core/RandomNumberGenerator.cpp:12-15 ----------------------------
 struct Rng {

@@ -91,7 +91,8 @@ enum { T_EXT_RAYS = 0, T_SHADOW_RAYS = 1, T_NODES_CLOSEST = 2, T_TRIS_CLOSEST = 
        T_WS_NODE_BLOCKS = 13, T_WS_TRI_BLOCKS = 14, T_WS_ACTIVE_LANES = 15,
        T_SAMPLES = 16,          // finished samples accumulated into pixels, summed from the slots' headers at the end of a render call
        T_PRIMARY_STARTS = 17,   // samples that took their first hit from the primary pass's record (k_shade's fused start, k_tail)
-       T_KINDS = 18 };
+       T_SHADOW_SKIPPED = 18,   // light samples k_shade did not trace because they decide nothing (counted in T_SHADOW_RAYS too: rays the algorithm casts)
+       T_KINDS = 19 };
 // device error word bits (PathBuffers::errorWord): set by any kernel path that gives up or drops work
 enum : uint32_t { ERR_RING_SPACE = 1u, ERR_RING_RELEASE = 2u, ERR_CONSUMER_IDLE = 4u, ERR_STACK_OVERFLOW = 8u, ERR_QUEUE_OVERFLOW = 16u };
 static const uint32_t kTotalStride = 16;                   // 64-bit words: one 128-byte line
@@ -177,7 +178,7 @@ struct PathBuffers {
 
 struct RenderParams {
     uint32_t numSlots;            // 256 x shade workgroups
-    uint32_t numBlocks;           // numSlots / 256
+    uint32_t traceAllShadows;     // SLRHIP_FLAG_TRACE_ALL_SHADOW_RAYS or _COUNT_TRAVERSAL: k_shade's RGB kernels trace dead light samples too
     uint32_t numPixels, stripes;  // stripes: slots per pixel the slot count was sized for (slrhip_config::stripes or the automatic choice)
     uint32_t sppBegin, sppCount;  // the passes of the current window
     uint32_t workItems;           // numPixels x sppCount (< 2^32: slrhip_render sizes the windows)

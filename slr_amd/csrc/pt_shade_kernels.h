@@ -522,8 +522,11 @@ struct SlotLoads {
 template <class S, bool LDS_TABLES, bool MF, bool MULTI, bool TEX, bool FUSED, bool TIGHT = false>
 __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, const ShadeLds<S::N != 3>& lds,
                                           const float* lightPMF, const float* lightCDF, uint32_t slot, const SlotLoads<S>& in, uint32_t& flags, uint32_t vis,
-                                          S& radiance, bool& emitExt, bool& emitShadow, bool& emitRegen) {
+                                          S& radiance, bool& emitExt, bool& emitShadow, bool& emitRegen, bool* deadShadow = nullptr) {
     constexpr bool leader = true;
+    // Light samples that decide nothing are not traced (step 3): k_shade's RGB kernels, whose Kahan pair is in registers.
+    // The spectral kernels (the pair is in HBM) and k_tail (it traces its shadow ray inline) keep their code.
+    constexpr bool kSkipDead = S::N == 3 && FUSED;
     // ---- the state loads that depend on the flags; the others were requested by the caller (SlotLoads) -----------
     const uint4 r4 = in.r4;
     // The path's radiance sum (Kahan pair) and the pending light sample: RGB keeps them in registers (3 x 16 B,
@@ -737,8 +740,10 @@ __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers&
                         sdir = (lp - surf.p) / dist;
                         shadowTmax = dist * (1 - kRayEpsilon);
                     }
+                    // (written for a sample that turns out dead as well, below: nothing reads it then.  Holding the direction back until that
+                    // is known costs k_shade's tight instantiations the register that decides their fourth wave: measured)
                     if (leader) pb.shadowDir[slot] = make_float4(sdir.x, sdir.y, sdir.z, shadowTmax);
-                    emitShadow = true;
+                    if constexpr (!kSkipDead) emitShadow = true;
                     // contribution if visible :181-202
                     float dist2;
                     V3 shadowDir;
@@ -770,7 +775,20 @@ __device__ __forceinline__ void logicSlot(const DevScene& sc, const PathBuffers&
                         MISWeight = (lightPDF * lightPDF) / (lightPDF * lightPDF + bsdfPDF * bsdfPDF);
                     float G = absDot(shadowDir_sn, gNorm_sn) * cosLight / dist2;
                     S contrib = alpha * Le * fs * (G * MISWeight / lightPDF);
-                    SpecIO<S>::store(pb.nee, nullptr, slot, rp.numSlots, contrib, 0.0f);
+                    if constexpr (kSkipDead) {
+                        // The reference traces every shadow ray and then adds what came back.  Where the sample is a zero that leaves the
+                        // Kahan pair as it is (deadLightSample; this step is the last of the visit to touch the pair, the resolve of the next
+                        // visit the first), nothing can depend on the ray: no pending sample, no queue entry, no flag bit —
+                        // and a path whose BSDF sample fails below ends here instead of waiting an iteration for it.  The ray still counts
+                        // as cast (T_SHADOW_RAYS, by the caller).  RenderParams::traceAllShadows keeps every ray: the comparator.
+                        const bool dead = !rp.traceAllShadows && deadLightSample(sp.r, sp.c, contrib);
+                        if (dead) *deadShadow = true;
+                        else {
+                            SpecIO<S>::store(pb.nee, nullptr, slot, rp.numSlots, contrib, 0.0f);
+                            emitShadow = true;
+                        }
+                    }
+                    else SpecIO<S>::store(pb.nee, nullptr, slot, rp.numSlots, contrib, 0.0f);
                 }
                 float uComp = rng.nextFloat();
                 float u0 = rng.nextFloat();
@@ -976,6 +994,22 @@ struct StartLds {
     uint32_t waveBase[kShadeBlock / 64 + 1];
     uint32_t wentIdle;                          // lanes of the workgroup that found the queue exhausted in this launch
 };
+// Light samples of this launch that were not traced (logicSlot, step 3), per wave.  RGB kernels only: an instantiation that never
+// names it allocates nothing.
+struct DeadLds {
+    uint32_t count[kShadeBlock / 64];
+};
+
+// The rays the algorithm casts are the reference's whether or not they are traced: the workgroup's untraced light samples go to
+// T_SHADOW_RAYS (k_trace_ws counts the traced ones) and to T_SHADOW_SKIPPED, one atomic each (no return) per workgroup and launch on the
+// workgroup's shard line, and none where the count is zero.  Called by every thread behind a barrier that follows the waves' writes.
+__device__ __forceinline__ void countDeadShadows(const PathBuffers& pb, const DeadLds& dl) {
+    if (threadIdx.x != 0) return;
+    const uint32_t n = dl.count[0] + dl.count[1] + dl.count[2] + dl.count[3];
+    if (n == 0u) return;
+    atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_SHADOW_RAYS, blockIdx.x % kShards)], (unsigned long long)n);
+    atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_SHADOW_SKIPPED, blockIdx.x % kShards)], (unsigned long long)n);
+}
 
 #ifndef SLR_SHADE_EARLY
 #define SLR_SHADE_EARLY 1          // 0 (variant builds): the slot's state records are requested after the table barrier
@@ -993,10 +1027,12 @@ __attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shad
     __shared__ ShadeLds<S::N != 3> lds;
     __shared__ PushLds pushLds;
     __shared__ StartLds start;
+    __shared__ DeadLds deadLds;
     // The fused start without the glossy lobes runs at 4 waves per SIMD (128 VGPRs, no scratch) if nothing of one trip occupies registers
     // through the other; two things did, 140 VGPRs' worth, and are undone where kTight is set.  The other instantiations
     // are 2 to 3 waves either way and keep their code.
     constexpr bool kTight = PRIMARY && !MF;
+    constexpr bool kSkipDead = S::N == 3;          // logicSlot traces no light sample that decides nothing (RGB)
     const uint32_t slot = blockIdx.x * kShadeBlock + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 
@@ -1041,12 +1077,13 @@ __attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shad
     // from 120 VGPRs to 200 (the visit's inputs as loop-carried values; 141 unrolled) and the headline frame from 300 ms to 364 ms —
     // measured, DESIGN.md 7.17.
     bool shadow0 = false, shadow1 = false;         // the shadow rays of the two trips: one reservation for both, after the loop
+    uint32_t deadWave = 0u;                        // light samples of this wave's lanes that were not traced, both trips (wave-uniform)
     uint32_t curSlot = slot, curVis = vis;
     bool curActive = state0 == ST_FIRST_HIT || state0 == ST_NEXT_HIT || state0 == ST_FINISH;
     uint4 curHdr = make_uint4(0u, 0u, 0u, 0u);     // trip 1: the new sample's header, from registers
 #pragma clang loop unroll(full)
     for (uint32_t trip = 0; trip < 2u; ++trip) {
-    bool emitExt = false, emitShadow = false, pathEnded = false;
+    bool emitExt = false, emitShadow = false, pathEnded = false, deadShadow = false;
     S radiance;
     // kTight: each trip reads the scene's uniform scalars through a copy of its own, opaque to the compiler.  The trips are a loop until
     // it is unrolled, and loop-invariant code motion runs first: it lifts the float conversions and quotients of these words out of the
@@ -1058,7 +1095,8 @@ __attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shad
     }
     const DevScene& scV = kTight ? scT : sc;
     if (curActive)
-        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true, kTight>(scV, pb, rp, lds, lightPMF, lightCDF, curSlot, in, flags, curVis, radiance, emitExt, emitShadow, pathEnded);
+        logicSlot<S, LDS_TABLES, MF, MULTI, TEX, true, kTight>(scV, pb, rp, lds, lightPMF, lightCDF, curSlot, in, flags, curVis, radiance, emitExt, emitShadow, pathEnded, &deadShadow);
+    if constexpr (kSkipDead) deadWave += (uint32_t)__popcll(__ballot(deadShadow));
 
     // ---- a path that ended: its contribution goes to the result window, in the same launch ------------------------------------
     if (pathEnded) {
@@ -1071,7 +1109,11 @@ __attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shad
     shadow0 = emitShadow;
     // ---- stream compaction of the shadow rays (extension rays need no queue: the traversal kernel reads the state flag); with the
     //      fused start, after the second trip ----------
-    if (!PRIMARY) blockPush(pushLds, emitShadow, slot, false, 0u, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
+    if (!PRIMARY) {
+        if constexpr (kSkipDead) { if (lane == 0) deadLds.count[wave] = deadWave; }     // published by blockPush's barriers
+        blockPush(pushLds, emitShadow, slot, false, 0u, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
+        if constexpr (kSkipDead) countDeadShadows(pb, deadLds);
+    }
     if (rp.countSlots) {
         const uint64_t ma = __ballot(emitExt || emitShadow || pathEnded);
         if (lane == 0 && ma) atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_SLOT_VISITS, blockIdx.x % kShards)], (unsigned long long)__popcll(ma));
@@ -1142,7 +1184,11 @@ __attribute__((amdgpu_waves_per_eu(SLR_SHADE_WAVES(S::N == 3, MF)))) void k_shad
             atomicAdd((unsigned long long*)&pb.totals[totalIndex(T_PRIMARY_STARTS, blockIdx.x % kShards)], (unsigned long long)n);
     }
     }
-    if (PRIMARY) blockPush(pushLds, shadow0, slot, shadow1, curSlot, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
+    if (PRIMARY) {
+        if constexpr (kSkipDead) { if (lane == 0) deadLds.count[wave] = deadWave; }
+        blockPush(pushLds, shadow0, slot, shadow1, curSlot, pb.shadowQueue, pb.queueCount + parity * kQueueSetWords, rp.shardCapacity, pb.errorWord);
+        if constexpr (kSkipDead) countDeadShadows(pb, deadLds);
+    }
 }
 
 // Start of a render window: every slot wants a sample (ST_REGEN), the queues are at their beginning.  `clearSensor`: the first

@@ -596,12 +596,16 @@ int slrhip_render_begin(slrhip_ctx* ctx, const slrhip_render_settings* st, slrhi
 
     bindBuffers(ctx, plan);
     RenderParams rp{};
-    rp.numSlots = plan.numSlots; rp.numBlocks = rp.numSlots / 256u; rp.numWaves = rp.numSlots / 64u;
+    rp.numSlots = plan.numSlots; rp.numWaves = rp.numSlots / 64u;
     rp.numPixels = plan.numPixels; rp.stripes = plan.stripes;
     rp.runLength = 1;                                     // the window's passes, runs and tail bound: renderWindow
     rp.rngSeed = st->rng_seed; rp.timeStart = st->time_start; rp.timeEnd = st->time_end;
     rp.imageWidth = plan.width; rp.imageHeight = plan.height;
     rp.countSlots = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) ? 1u : 0u;
+#ifndef SLR_FORCE_TRACE_ALL_SHADOWS
+#define SLR_FORCE_TRACE_ALL_SHADOWS 0      // 1 (variant builds): every context traces every shadow ray — the same kernels without the rays removed
+#endif
+    rp.traceAllShadows = (SLR_FORCE_TRACE_ALL_SHADOWS || (ctx->config.flags & (SLRHIP_FLAG_TRACE_ALL_SHADOW_RAYS | SLRHIP_FLAG_COUNT_TRAVERSAL))) ? 1u : 0u;
     rp.shardCapacity = plan.shardCapacity;
     rp.spectral = spectral ? 1u : 0u;
     rp.injectError = (ctx->config.flags & SLRHIP_FLAG_TEST_DEVICE_ERROR) ? 1u : 0u;
@@ -744,6 +748,17 @@ int slrhip_debug_primary_samples(slrhip_ctx* ctx, uint64_t* samples) {
     uint64_t t[T_KINDS];
     if (const int rc = readTotals(ctx, t)) return rc;
     *samples = t[T_PRIMARY_STARTS];
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): light samples k_shade did not trace, as it counted them (they are in shadow_rays as well).
+int slrhip_debug_shadow_skipped(slrhip_ctx* ctx, uint64_t* rays) {
+    if (!ctx || !rays) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_shadow_skipped: null argument");
+    *rays = 0;
+    if (!ctx->haveRender) return SLRHIP_OK;
+    uint64_t t[T_KINDS];
+    if (const int rc = readTotals(ctx, t)) return rc;
+    *rays = t[T_SHADOW_SKIPPED];
     return SLRHIP_OK;
 }
 

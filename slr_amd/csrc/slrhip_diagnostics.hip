@@ -3,9 +3,18 @@
 #include <memory>
 
 #include "../../include/slrhip_debug.h"
+#include "pt_device.h"
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
+
+// slrhip_debug_dead_light_samples: deadLightSample — the very function logicSlot decides with — on the caller's triples, one a lane
+static __global__ void k_dead_light_samples(uint32_t n, const float* triples, uint32_t* dead) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* t = triples + (size_t)i * 9u;
+    dead[i] = deadLightSample(RGB(t[0], t[1], t[2]), RGB(t[3], t[4], t[5]), RGB(t[6], t[7], t[8])) ? 1u : 0u;
+}
 
 // The kernels' hit record is (triangle, t, b1, b2) — Moller-Trumbore's barycentrics; the ABI reports Intersection::u, ::v =
 // (b0, b1) with b0 = 1 - b1 - b2 exactly as Triangle::intersect computes it (TriangleMesh.cpp:159,172-173).
@@ -266,6 +275,23 @@ int slrhip_debug_camera_draws(int32_t device, uint32_t n, const uint32_t* tuples
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dOut.ptr, (size_t)n * 16u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): the device's dead-sample predicate on the caller's (sum, compensation, contribution) triples.
+int slrhip_debug_dead_light_samples(int32_t device, uint32_t n, const float* triples, uint32_t* dead) {
+    if (!triples || !dead) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_dead_light_samples: null argument");
+    if (n == 0) return SLRHIP_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevArray<float> dIn;
+    DevArray<uint32_t> dOut;
+    HIP_TRY(dIn.alloc((size_t)n * 9u));
+    HIP_TRY(dOut.alloc(n));
+    HIP_TRY(hipMemcpy(dIn.ptr, triples, (size_t)n * 9u * sizeof(float), hipMemcpyHostToDevice));
+    k_dead_light_samples<<<(n + 255u) / 256u, 256, 0, nullptr>>>(n, dIn.ptr, dOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(dead, dOut.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SLRHIP_OK;
 }
 
