@@ -93,6 +93,20 @@ int slrhip_debug_primary_kernel_plan(uint32_t num_pixels, uint32_t num_passes, u
  * direct kernel — so that a test can tell that it compared what it meant to.                                                             */
 int slrhip_debug_primary_kernel(slrhip_ctx* ctx, uint32_t* kernel);
 
+/* The k_shade instantiation of a window (slr_amd/csrc/render_plan.h, planShadeVariant), evaluated on the HOST with the function the render
+ * calls, from what the render looks at: the context's mode (`spectral`), whether the scene's shading tables fit the LDS limits
+ * (`shade_tables`), whether it has a microfacet lobe, a MultiBSDF material, how many textures, whether the window runs the primary pass
+ * (`primary`) and keeps its stream plane (`primary_rng`).  plan[0..6] = the instantiation: spectral, tables in LDS, glossy lobes,
+ * MultiBSDF code, texture code, fused start (PRIMARY), resumed stream (RESUME), 0 or 1 each; plan[7] = 1 where the table of built kernels
+ * (slr_amd/csrc/pt_shade.hip) has that k_shade, plan[8] = 1 where it has the k_tail that finishes its windows.  No GPU is touched.      */
+int slrhip_debug_shade_plan(uint32_t spectral, uint32_t shade_tables, uint32_t has_microfacet, uint32_t has_multi, uint32_t num_textures,
+                            uint32_t primary, uint32_t primary_rng, uint32_t* plan);
+
+/* The k_shade instantiation of the context's last window, recorded on the host where it is launched: kernel[0..6] as plan[0..6] above,
+ * kernel[7] = 1 once that window launched it, kernel[8] = 1 once the tail kernel, its twin without a start of its own, finished the
+ * window — so that a test can tell which kernels it compared.                                                                          */
+int slrhip_debug_shade_kernel(slrhip_ctx* ctx, uint32_t* kernel);
+
 /* One launch of the primary pass of the render last begun on `ctx` (slrhip_render_begin: its pixel list, seed, camera and image size),
  * with the kernel named: `kernel` 0 = ring, 1 = direct.  The launch takes the passes [first_pass, first_pass + num_passes) of a window of
  * `window_passes` passes that starts at pass 0 of the render, and writes into the caller's DEVICE memory laid out as the window is:

@@ -259,7 +259,7 @@ struct Continuous1D {
     // :181-184 index with no clamp and assert smp < 1.  theta / pi and phi / 2pi DO round up to 1.0f — a direction out of a
     // bump-mapped frame (three unit vectors, not orthogonal: SurfaceObject.cpp:123-134) is not a unit vector, its y below -1 is
     // clamped and acos gives (float)pi — and the reference then reads one float past its table: no answer to restate.  The
-    // last cell, as the device does (envAreaPDF, pt_shade_kernels.h).
+    // last cell, as the device does (envAreaPDF, pt_env_sphere.h).
     float evaluatePDF(float smp) const { return PDF[std::min((uint32_t)(int32_t)(smp * numValues), numValues - 1)]; }
 };
 // Core/distributions.cpp:186-224  RegularConstantContinuous2D

@@ -32,7 +32,7 @@ EXPORTS = ["slrhip_create", "slrhip_destroy", "slrhip_upload_scene", "slrhip_ren
            "slrhip_set_vertices", "slrhip_geometry_status", "slrhip_debug_geometry_update_check", "slrhip_debug_geometry",
            "slrhip_debug_geometry_update_check2",
            "slrhip_set_materials", "slrhip_set_texture_texels", "slrhip_debug_materials_update_check", "slrhip_debug_materials",
-           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_shadow_skipped", "slrhip_debug_dead_light_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_primary_kernel_plan", "slrhip_debug_primary_kernel", "slrhip_debug_primary_pass", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
+           "slrhip_bsdf_queries", "slrhip_debug_work_distribution", "slrhip_debug_render_plan", "slrhip_debug_primary_plan", "slrhip_debug_primary_samples", "slrhip_debug_shadow_skipped", "slrhip_debug_dead_light_samples", "slrhip_debug_primary_entries", "slrhip_debug_primary_stream_entries", "slrhip_debug_primary_stream_plan", "slrhip_debug_primary_kernel_plan", "slrhip_debug_primary_kernel", "slrhip_debug_shade_plan", "slrhip_debug_shade_kernel", "slrhip_debug_primary_pass", "slrhip_debug_camera_draws", "slrhip_sample_seed", "slrhip_upsample", "slrhip_resolve_upsampled", "slrhip_spectrum_to_rgb", "slrhip_tonemap_bgr8", "slrhip_save_bmp",
            "slrhip_last_error_string", "slrhip_version"]
 
 
@@ -219,6 +219,10 @@ def load_library():
         lib.slrhip_debug_primary_kernel_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]
         lib.slrhip_debug_primary_kernel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.slrhip_debug_primary_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    # (and one from before the table of shade kernels lacks these two)
+    if path == LIB_PATH or hasattr(lib, "slrhip_debug_shade_kernel"):
+        lib.slrhip_debug_shade_plan.argtypes = [C.c_uint32] * 7 + [C.POINTER(C.c_uint32)]
+        lib.slrhip_debug_shade_kernel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     # (and one from before dead light samples went untraced lacks these two)
     if path == LIB_PATH or hasattr(lib, "slrhip_debug_shadow_skipped"):
         lib.slrhip_debug_shadow_skipped.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -656,6 +660,13 @@ class Context:
         k = C.c_uint32(0)
         _check(self.lib, self.lib.slrhip_debug_primary_kernel(self.handle, C.byref(k)), "slrhip_debug_primary_kernel")
         return int(k.value)
+
+    def shade_kernel(self):
+        """Diagnostic (slrhip_debug_shade_kernel): the last window's k_shade instantiation as a tuple (spectral, tables in LDS, glossy
+        lobes, MultiBSDF, textures, PRIMARY, RESUME), whether it was launched, and whether the tail kernel, its twin, was."""
+        k = (C.c_uint32 * 9)()
+        _check(self.lib, self.lib.slrhip_debug_shade_kernel(self.handle, k), "slrhip_debug_shade_kernel")
+        return tuple(int(x) for x in k[:7]), bool(k[7]), bool(k[8])
 
     def primary_pass(self, kernel, first_pass, num_passes, window_passes, records, streams=0):
         """Diagnostic (slrhip_debug_primary_pass): one launch of the primary pass of the render last begun, `kernel` 0 = ring, 1 = direct,

@@ -33,6 +33,22 @@ inline const char* tuningEnv(const char* name) {
 // The numbers are what slrhip_debug_primary_kernel reports (include/slrhip_debug.h).
 enum class PrimaryKernel : uint32_t { None = 0, Ring = 1, Direct = 2 };
 
+// One instantiation of k_shade, and of k_tail (which has neither `primary` nor `resume`): the host's choice (render_plan.h,
+// planShadeVariant), the key of the table of built kernels (pt_shade.hip) and what slrhip_debug_shade_kernel reports, in this order.
+struct ShadeVariant {
+    bool spectral;      // Spec16 instead of RGB
+    bool ldsTables;     // material / light / spectrum tables staged in LDS
+    bool glossy;        // GGX / Ward / Ashikhmin lobes compiled in
+    bool multi;         // MultiBSDF code
+    bool textures;      // texture code
+    bool primary;       // the fused start: windows with a primary pass
+    bool resume;        // ... that goes on from the stream the pass left instead of seeding its own
+};
+inline bool operator==(const ShadeVariant& a, const ShadeVariant& b) {
+    return a.spectral == b.spectral && a.ldsTables == b.ldsTables && a.glossy == b.glossy && a.multi == b.multi && a.textures == b.textures &&
+           a.primary == b.primary && a.resume == b.resume;
+}
+
 static const uint32_t kInvalidChild = 0xFFFFFFFFu;
 static const uint32_t kLeafFlag = 0x80000000u;
 static const uint32_t kLeafCountShift = 27;

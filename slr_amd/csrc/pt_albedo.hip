@@ -7,8 +7,13 @@
 // texture coordinate (texturizeMat), BSDF::getBaseColor(All) of the lobe (bsdfBaseColor, pt_bsdf.h) or of the MultiBSDF
 // (bsdfBaseColorMulti, pt_bsdf_multi.h) — and adds it to the pixel with plain float32 adds.  The tables are read from HBM, as
 // k_bsdf_queries reads them.  The sample's wavelength offset is not in the record: the fold draws it again from (seed, pixel, pass).
-#include "pt_shade_kernels.h"
+#include "pt_bsdf.h"
+#include "pt_bsdf_multi.h"
+#include "pt_camera.h"
 #include "pt_luminance.h"
+#include "pt_shade_tables.h"
+#include "pt_tex.h"
+#include "pt_tex_spectrum.h"
 
 namespace slrhip {
 

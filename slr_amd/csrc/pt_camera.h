@@ -1,6 +1,6 @@
 // pt_camera.h — the camera half of Job::kernel (Renderers/PathTracingRenderer.cpp:100-120) as device functions: the sample's
 // draws and PerspectiveCamera::sample + PerspectiveIDF::sample (Cameras/PerspectiveCamera.cpp:33-74).  One statement of the
-// reference's arithmetic, used by the path tracer's startSample (pt_shade_kernels.h), by the producer waves of the feature trace
+// reference's arithmetic, used by the path tracer's startSample (pt_sample_start.h), by the producer waves of the feature trace
 // and the primary pass (pt_trace_indexed.hip) and by slrhip_camera_rays (k_camera_rays, pt_features.hip).
 #pragma once
 #include "pt_device.h"

@@ -8,11 +8,12 @@
 
 namespace slrhip {
 
-// Limits of the shading tables staged in LDS by k_shade / k_tail (ShadeLds, pt_shade_kernels.h); larger scenes read them from HBM.
+// Limits of the shading tables staged in LDS by k_shade / k_tail (ShadeLds, pt_shade_tables.h); larger scenes read them from HBM.
 static const int kLdsMaterials = 32;
 static const int kLdsLights = 16;
 static const int kLdsSpectra = 96;
 static const int kLdsPoolFloats = 6144;     // 24 KiB: the spectrum sample tables of a scene (spectral mode), staged per workgroup
+static const int kShadeBlock = 256;         // slots per workgroup of the kernels that walk the slots: numSlots = 256 x workgroups
 
 // Scene arrays resident in HBM (uploaded once by slrhip_upload_scene).
 struct DevScene {
@@ -282,12 +283,13 @@ template <> struct FoldClampArgs<true> : ClampParams {};
 // statRecords != nullptr (slrhip_statistics_begin): the instantiation that also updates the per-pixel noise records
 // clamp.records != nullptr (slrhip_clamp_begin): the instantiation that puts every sample through clampSample first
 void launchFold(const PathBuffers& pb, const RenderParams& rp, float4* statRecords, const ClampParams& clamp, hipStream_t stream);
-// one wavefront iteration = launchShade(parity) then launchTraceWs(parity)
-void launchShade(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);
+// one wavefront iteration = launchShade(parity) then launchTraceWs(parity).  `v`: the window's k_shade instantiation (render_plan.h,
+// planShadeVariant), looked up in the table of built kernels (pt_shade.hip); false: the table has no such row and nothing was launched
+bool launchShade(const ShadeVariant& v, const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);
 void launchCountSamples(const PathBuffers& pb, const RenderParams& rp, hipStream_t stream);
-// the rest of a render call in one launch (after tailMode was raised): list the live slots, then one lane per path to its end
-void launchTail(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t liveSlots, int numCUs, hipStream_t stream);
-bool tailKernelAvailable(const DevScene& sc, bool spectral);      // not built for spectral scenes with MultiBSDF materials or textures
+// the rest of a render call in one launch (after tailMode was raised): list the live slots, then one lane per path to its end, with
+// the k_tail twin of `v` (every k_shade row has one); false as above
+bool launchTail(const ShadeVariant& v, const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t liveSlots, int numCUs, hipStream_t stream);
 void launchResolve(const PathBuffers& pb, const RenderParams& rp, float* dst, hipStream_t stream);
 void launchBsdfQueries(const DevScene& sc, bool spectral, uint32_t material, uint32_t n, const float* in, float wlOffset, uint32_t wl,
                        float4* geo, float4* misc, float4* fsSample, float4* fsEval, hipStream_t stream);

@@ -1,14 +1,8 @@
-// pt_shade_multi_rgb_primary.hip — one k_shade instantiation with the fused start (PRIMARY, see pt_shade_kernels.h); one per file
+// pt_shade_multi_rgb_primary.hip — the all-lobes k_shade<RGB> of MultiBSDF scenes with the fused start, resuming (PRIMARY, RESUME); one per file
 #include "pt_shade_kernels.h"
 
 namespace slrhip {
 
-void launchShadeMultiRGBPrimarySeeded(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream);      // pt_shade_multi_rgb_primary_seeded.hip
-
-void launchShadeMultiRGBPrimary(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream) {
-    if (!pb.primaryRng) { launchShadeMultiRGBPrimarySeeded(sc, pb, rp, parity, stream); return; }      // no stream plane in this window (render_plan.h, planPrimary)
-    const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    hipLaunchKernelGGL((k_shade<RGB, false, true, true, false, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
-}
+template ShadeKernel shadeKernel<RGB, false, true, true, false, true, true>();
 
 } // namespace slrhip

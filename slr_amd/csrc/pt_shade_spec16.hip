@@ -1,14 +1,11 @@
-// pt_shade_spec16.hip — k_shade instantiations (see pt_shade_kernels.h)
+// pt_shade_spec16.hip — k_shade<Spec16> (the table: pt_shade.hip)
 #include "pt_shade_kernels.h"
 
 namespace slrhip {
 
-void launchShadeSpec16(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, bool lds, bool glossy, hipStream_t stream) {
-    const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    if (lds && !glossy) hipLaunchKernelGGL((k_shade<Spec16, true, false>), grid, block, 0, stream, sc, pb, rp, parity);
-    else if (lds) hipLaunchKernelGGL((k_shade<Spec16, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
-    else if (!glossy) hipLaunchKernelGGL((k_shade<Spec16, false, false>), grid, block, 0, stream, sc, pb, rp, parity);
-    else hipLaunchKernelGGL((k_shade<Spec16, false, true>), grid, block, 0, stream, sc, pb, rp, parity);
-}
+template ShadeKernel shadeKernel<Spec16, true, false>();
+template ShadeKernel shadeKernel<Spec16, true, true>();
+template ShadeKernel shadeKernel<Spec16, false, false>();
+template ShadeKernel shadeKernel<Spec16, false, true>();
 
 } // namespace slrhip

@@ -1,11 +1,8 @@
-// pt_shade_tex_rgb.hip — one k_shade instantiation (see pt_shade_kernels.h); one per file: each takes a minute or more to compile
+// pt_shade_tex_rgb.hip — the all-lobes k_shade<RGB> of textured scenes; one per file: each takes a minute or more to compile
 #include "pt_shade_kernels.h"
 
 namespace slrhip {
 
-void launchShadeTexRGB(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream) {
-    const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    hipLaunchKernelGGL((k_shade<RGB, false, true, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
-}
+template ShadeKernel shadeKernel<RGB, false, true, true, true>();
 
 } // namespace slrhip

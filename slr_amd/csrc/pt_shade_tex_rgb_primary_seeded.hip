@@ -1,11 +1,8 @@
-// pt_shade_tex_rgb_primary_seeded.hip — one k_shade instantiation with the fused start (PRIMARY, see pt_shade_kernels.h), seeding its own stream; one per file
+// pt_shade_tex_rgb_primary_seeded.hip — the all-lobes k_shade<RGB> of textured scenes with the fused start, seeding its stream (PRIMARY); one per file
 #include "pt_shade_kernels.h"
 
 namespace slrhip {
 
-void launchShadeTexRGBPrimarySeeded(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream) {
-    const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    hipLaunchKernelGGL((k_shade<RGB, false, true, true, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
-}
+template ShadeKernel shadeKernel<RGB, false, true, true, true, true>();
 
 } // namespace slrhip

@@ -1,11 +1,8 @@
-// pt_shade_tex_spec.hip — one k_shade instantiation (see pt_shade_kernels.h); one per file: each takes a minute or more to compile
+// pt_shade_tex_spec.hip — the all-lobes k_shade<Spec16> of textured scenes; one per file
 #include "pt_shade_kernels.h"
 
 namespace slrhip {
 
-void launchShadeTexSpec(const DevScene& sc, const PathBuffers& pb, const RenderParams& rp, uint32_t parity, hipStream_t stream) {
-    const dim3 grid(rp.numSlots / kShadeBlock), block(kShadeBlock);
-    hipLaunchKernelGGL((k_shade<Spec16, false, true, true, true>), grid, block, 0, stream, sc, pb, rp, parity);
-}
+template ShadeKernel shadeKernel<Spec16, false, true, true, true>();
 
 } // namespace slrhip

@@ -1,7 +1,7 @@
 // pt_surface.h — the surface point of a triangle hit as device functions: Triangle::getSurfacePoint (Surface/TriangleMesh.cpp:
 // 180-215), BumpSingleSurfaceObject::getSurfacePoint (Core/SurfaceObject.cpp:123-134) and TransformedSurfaceObject::
 // getSurfacePoint (:329-336).  One statement of the reference's arithmetic, used by the path tracer (logicSlot,
-// pt_shade_kernels.h) and by the feature pass (k_feature_fold, pt_features.hip).
+// pt_shade_visit.h) and by the feature pass (k_feature_fold, pt_features.hip).
 #pragma once
 #include "pt_device.h"
 #include "pt_tex.h"

@@ -14,7 +14,11 @@
 // A sample's contribution is a function of (pixel, pass) alone and the sensor adds the contributions in pass order (k_fold), so
 // the image is the same to the last bit whether the tail kernel or the wavefront kernels finish the window, at any slot count.
 #pragma once
-#include "pt_shade_kernels.h"
+#include "pt_sample_start.h"
+#include "pt_shade_tables.h"
+#include "pt_shade_variants.h"
+#include "pt_shade_visit.h"
+#include "pt_slot_state.h"
 #include "pt_traverse.h"
 
 namespace slrhip {
@@ -143,5 +147,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(SLR
         if (idleNow) atomicAdd(&pb.tailIdled[0], idleNow);      // the host checks it against the list length, then clears the live count
     }
 }
+
+// pt_shade_variants.h: a translation unit (pt_tail_*.hip) builds a k_tail by instantiating this
+template <class S, bool LDS_TABLES, bool MF, bool MULTI, bool TEX>
+TailKernel tailKernel() { return &k_tail<S, LDS_TABLES, MF, MULTI, TEX>; }
 
 } // namespace slrhip

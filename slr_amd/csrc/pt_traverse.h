@@ -22,7 +22,7 @@ static const int kTopStride = 9;       // float4 per staged node: 8 + 1 pad -> 1
 
 struct HitRec {
     uint32_t tri;
-    float t, b1, b2;       // Moller-Trumbore's own barycentrics: b0 = 1 - b1 - b2 is re-derived where it is needed (pt_shade_kernels.h)
+    float t, b1, b2;       // Moller-Trumbore's own barycentrics: b0 = 1 - b1 - b2 is re-derived where it is needed (logicSlot, pt_shade_visit.h)
     int32_t inst;          // INST: the instance the hit went through, -1 = a loose triangle
 };
 struct TravCount {

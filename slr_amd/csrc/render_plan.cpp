@@ -141,6 +141,25 @@ PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFl
     return p;
 }
 
+ShadeVariant planShadeVariant(bool spectral, bool shadeTables, bool hasMicrofacet, bool hasMulti, uint32_t numTextures, bool primary, bool primaryRng) {
+    const bool allLobes = hasMulti || numTextures != 0;
+    ShadeVariant v;
+    v.spectral = spectral;
+    v.ldsTables = shadeTables && !allLobes;
+    // The microfacet (GGX) code costs ~45 VGPRs, so scenes without such lobes get kernels without it.
+    v.glossy = hasMicrofacet || allLobes;
+    v.multi = allLobes;
+    v.textures = numTextures != 0;
+    v.primary = primary && !spectral;
+    v.resume = v.primary && primaryRng;
+    return v;
+}
+
+ShadeVariant tailVariant(ShadeVariant v) {
+    v.primary = v.resume = false;
+    return v;
+}
+
 // The end of the window (pt_tail_kernels.h): once at most tailSlots slots are alive the traversal kernel raises the tail-mode word
 // instead of tracing, the rest of the block of iterations is no-ops, and the tail kernel finishes every remaining path and sample
 // in one launch.  The image does not depend on who finishes a sample (the sensor adds in pass order).  On with the automatic slot

@@ -82,9 +82,18 @@ struct PrimaryPlan {
 PrimaryPlan planPrimary(uint32_t numPixels, uint32_t sppCount, uint32_t configFlags, bool instanced, bool spectral, bool environment,
                         bool quantized = false);
 
+// The k_shade instantiation of a window, from what the scene and the window's plan say: the context's mode, DevScene::shadeTables
+// != nullptr (the tables fit the LDS limits), ::hasMicrofacet, ::hasMulti, ::numTextures, RenderParams::primary and
+// PathBuffers::primaryRng != nullptr (the pass keeps the stream plane).  MultiBSDF and textured scenes run one all-lobes kernel per
+// mode with the tables in HBM (a component is re-read per use), and the textured one has the MultiBSDF code too; the fused start is
+// built for RGB only (planPrimary keeps the pass off in spectral contexts), and only it can resume a stream.
+ShadeVariant planShadeVariant(bool spectral, bool shadeTables, bool hasMicrofacet, bool hasMulti, uint32_t numTextures, bool primary, bool primaryRng);
+// ... and the k_tail instantiation that finishes its window: the same code without a start of its own.
+ShadeVariant tailVariant(ShadeVariant v);
+
 // RenderParams::tailSlots of a window: 0 = the tail kernel stays off.  `asked`: the caller's flag or the automatic slot count;
-// `envTail`: SLRHIP_TAIL_SLOTS (-1 = unset, 0 = off, n = the bound); `available`: the tail kernel exists for this scene and the
-// build does not count traversal steps; never more than numSlots / `divisor` (SLR_TAIL_DIVISOR of slrhip_api.hip).
+// `envTail`: SLRHIP_TAIL_SLOTS (-1 = unset, 0 = off, n = the bound); `available`: the context does not count traversal steps
+// (every shade kernel has its tail kernel); never more than numSlots / `divisor` (SLR_TAIL_DIVISOR of slrhip_api.hip).
 uint32_t tailSlots(uint32_t numSlots, uint32_t divisor, bool asked, long envTail, bool available);
 
 // The blocks of a slrhip_render_adaptive call, as pass counts: sppMin (>= 2), then sppStep (>= 1) as often as it fits, the last one

@@ -10,6 +10,7 @@
 #include <chrono>
 
 #include "pt_refit.h"
+#include "pt_shade_variants.h"
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
@@ -277,7 +278,9 @@ static int runTail(slrhip_ctx* ctx, const PathBuffers& pb, const RenderParams& r
         ~Timer() { if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
     } timer;
     if (timed) { HIP_TRY(hipEventCreate(&timer.t0)); HIP_TRY(hipEventCreate(&timer.t1)); HIP_TRY(hipEventRecord(timer.t0, s)); }
-    launchTail(ctx->scene, pb, rp, status[S_LIVE], ctx->numCUs, s);
+    if (!launchTail(ctx->shadeVariant, ctx->scene, pb, rp, status[S_LIVE], ctx->numCUs, s))
+        return fail(SLRHIP_ERR_HIP, "slrhip_render: no k_tail is built for the window's shade variant (internal error)");
+    ctx->tailLaunched = true;
     if (timed) HIP_TRY(hipEventRecord(timer.t1, s));
     HIP_TRY(hipGetLastError());
     const uint32_t liveBefore = status[S_LIVE];
@@ -315,7 +318,8 @@ static hipError_t launchBlock(slrhip_ctx* ctx, const PathBuffers& pb, const Rend
         const uint32_t parity = (uint32_t)(k & 1);
         hipEvent_t* ev = timed ? &ctx->events[(size_t)k * kEventsPerIteration] : nullptr;
         if (ev && e == hipSuccess) e = hipEventRecord(ev[0], s);
-        launchShade(ctx->scene, pb, rp, parity, s);
+        if (!launchShade(ctx->shadeVariant, ctx->scene, pb, rp, parity, s)) return hipErrorInvalidDeviceFunction;      // (renderWindow has checked the row)
+        ctx->shadeLaunched = true;
         if (ev && e == hipSuccess) e = hipEventRecord(ev[1], s);
         launchTraceWs(ctx->scene, pb, rp, parity, traceBlocks, count, s);
         if (ev && e == hipSuccess) e = hipEventRecord(ev[2], s);
@@ -386,6 +390,11 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     }
     ctx->primaryRngEntries = pb.primaryRng ? ctx->primaryRng.count : 0u;       // what this window bound, not what the plan said
     ctx->primaryKernel = PrimaryKernel::None;                                  // ... and what it launched (set where the pass is launched, below)
+    // the k_shade instantiation of the window, chosen once (render_plan.cpp, planShadeVariant); a variant no file builds is refused here
+    ctx->shadeVariant = planShadeVariant(rp.spectral != 0, ctx->scene.shadeTables != nullptr, ctx->scene.hasMicrofacet != 0, ctx->scene.hasMulti != 0,
+                                         ctx->scene.numTextures, rp.primary != 0, pb.primaryRng != nullptr);
+    ctx->shadeLaunched = ctx->tailLaunched = false;
+    if (!findShadeKernel(ctx->shadeVariant)) return fail(SLRHIP_ERR_HIP, "slrhip_render: no k_shade is built for the window's shade variant (internal error)");
     // the first window after render_begin also clears the sensor (the buffers are reused across render_begin calls), even when
     // it is asked for zero passes
     launchResetSlots(pb, rp, ctx->firstRenderCall, stream);
@@ -398,7 +407,7 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
     static const long envTail = [] { const char* e = getenv("SLRHIP_TAIL_SLOTS"); return e ? atol(e) : -1L; }();
     const bool counting = (ctx->config.flags & SLRHIP_FLAG_COUNT_TRAVERSAL) != 0;
     rp.tailSlots = tailSlots(rp.numSlots, SLR_TAIL_DIVISOR, (ctx->config.flags & SLRHIP_FLAG_TAIL_KERNEL) != 0 || ctx->config.stripes == 0, envTail,
-                             tailKernelAvailable(ctx->scene, rp.spectral != 0) && !counting);
+                             !counting);
 
     const bool timeKernels = (ctx->config.flags & SLRHIP_FLAG_TIME_KERNELS) != 0;
     if (timeKernels && ctx->events.empty()) {
@@ -442,7 +451,7 @@ int slrhip::renderWindow(slrhip_ctx* ctx, uint32_t sppBegin, uint32_t sppCount, 
         HIP_TRY(hipEventRecord(ctx->userReady, stream));          // the reset kernel above and whatever the caller queued before
         HIP_TRY(hipStreamWaitEvent(s, ctx->userReady, 0));
         HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        (void)launchBlock(ctx, pb, rp, traceBlocks, false, s);
+        (void)launchBlock(ctx, pb, rp, traceBlocks, false, s);      // untimed: its only early return is a missing k_shade row, refused above
         hipError_t ce = hipStreamEndCapture(s, &block.graph);
         if (ce == hipSuccess) ce = hipGraphInstantiate(&block.exec, block.graph, nullptr, nullptr, 0);
         if (ce != hipSuccess) return fail(SLRHIP_ERR_HIP, std::string("slrhip_render: hipGraph capture failed: ") + hipGetErrorString(ce));

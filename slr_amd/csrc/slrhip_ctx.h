@@ -176,6 +176,8 @@ struct slrhip_ctx {
     DevArray<uint4> primaryRng;                   // windows with a primary pass: the stream after the camera draws, one entry per sample of the window (renderWindow)
     uint64_t primaryRngEntries = 0;               // ... as the last window bound it to PathBuffers::primaryRng; 0: that window had no pass (slrhip_debug_primary_stream_entries)
     slrhip::PrimaryKernel primaryKernel = slrhip::PrimaryKernel::None;      // the kernel the last window's primary pass was launched with; None: it ran no pass (slrhip_debug_primary_kernel)
+    slrhip::ShadeVariant shadeVariant = {};       // the last window's k_shade instantiation (renderWindow), and whether launchShade launched it
+    bool shadeLaunched = false, tailLaunched = false;      // ... and launchTail its twin (slrhip_debug_shade_kernel)
     DevArray<uint32_t> flags, visible, shadowQueue, tailList, queueCount, activeSlots, blockDead;
     DevArray<uint64_t> totals;
     DevArray<float> resolveScratch;

@@ -4,6 +4,7 @@
 
 #include "../../include/slrhip_debug.h"
 #include "pt_device.h"
+#include "pt_shade_variants.h"
 #include "slrhip_ctx.h"
 
 using namespace slrhip;
@@ -224,6 +225,31 @@ int slrhip_debug_primary_kernel_plan(uint32_t numPixels, uint32_t numPasses, uin
 int slrhip_debug_primary_kernel(slrhip_ctx* ctx, uint32_t* kernel) {
     if (!ctx || !kernel) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_primary_kernel: null argument");
     *kernel = (uint32_t)ctx->primaryKernel;
+    return SLRHIP_OK;
+}
+
+static void variantWords(const ShadeVariant& v, uint32_t* out) {
+    const bool f[7] = {v.spectral, v.ldsTables, v.glossy, v.multi, v.textures, v.primary, v.resume};
+    for (int i = 0; i < 7; ++i) out[i] = f[i] ? 1u : 0u;
+}
+
+// Diagnostic (include/slrhip_debug.h): the k_shade instantiation of a window as renderWindow plans it, and its rows in the table.
+int slrhip_debug_shade_plan(uint32_t spectral, uint32_t shadeTables, uint32_t hasMicrofacet, uint32_t hasMulti, uint32_t numTextures, uint32_t primary,
+                            uint32_t primaryRng, uint32_t* plan) {
+    if (!plan) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_shade_plan: null argument");
+    const ShadeVariant v = planShadeVariant(spectral != 0, shadeTables != 0, hasMicrofacet != 0, hasMulti != 0, numTextures, primary != 0, primaryRng != 0);
+    variantWords(v, plan);
+    plan[7] = findShadeKernel(v) ? 1u : 0u;
+    plan[8] = findTailKernel(tailVariant(v)) ? 1u : 0u;
+    return SLRHIP_OK;
+}
+
+// Diagnostic (include/slrhip_debug.h): what the last window's launchShade and launchTail launched.
+int slrhip_debug_shade_kernel(slrhip_ctx* ctx, uint32_t* kernel) {
+    if (!ctx || !kernel) return fail(SLRHIP_ERR_INVALID_ARGUMENT, "slrhip_debug_shade_kernel: null argument");
+    variantWords(ctx->shadeVariant, kernel);
+    kernel[7] = ctx->shadeLaunched ? 1u : 0u;
+    kernel[8] = ctx->tailLaunched ? 1u : 0u;
     return SLRHIP_OK;
 }
 

@@ -625,7 +625,7 @@ def spectrum_zoo(fit_lds):
     mats["emit_irr_256"] = b.matte(white, emittance=specs["irr_256"])
     if not fit_lds:
         mats["emit_reg_wide"] = b.matte(white, emittance=specs["reg_wide_emitted"])
-        # texturizeMat.  Only here: a scene with any texture is shaded by the kernels that read their tables from HBM (launchShade)
+        # texturizeMat.  Only here: a scene with any texture is shaded by the kernels that read their tables from HBM (planShadeVariant, render_plan.cpp)
         mats["checker"] = b.matte(b.checker_spectrum(specs["irr_255"], specs["irr_dense700"], (0.0, 0.0), (3.0, 3.0)))
     for i, m in enumerate(mats.values()):
         x, z = -1.38 + 0.46 * (i % 6), 1.2 - 0.7 * (i // 6)                   # (the camera sees the floor from z = 1.3 on)
