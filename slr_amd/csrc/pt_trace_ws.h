@@ -278,14 +278,42 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const IO& io, WsLd
         // (not `else`: a lane that has just entered or left an instance goes on with its node or triangle step in the same turn)
         if (slot != kIdle && !(INST && (cur & kLeafFlag) != 0 && !isTriLeaf(cur))) {
             bool finished = false;
-            if (!isTriLeaf(cur)) {
+            // Two schedules of the same steps, by tree class (measured per class, as the consumer count is):
+            //  * float nodes without instances (kOneTrip): the kind of this turn's step — a node, or ONE triangle of the leaf packet
+            //    the lane stands at — is fixed here, before any load, and one round trip serves both kinds.  A lane needs the three
+            //    16-byte pieces of its triangle record OR the near planes of its node, never both, so the same three loads fetch
+            //    either into the same twelve registers (their base differs from lane to lane: a 64-bit address each); the far planes
+            //    and the children are loaded by the node lanes alone.  The loads of the lanes at a leaf are on their way while the
+            //    node lanes do their slab test and stack work.  A lane whose node step ends on a leaf tests that leaf's first
+            //    triangle in its NEXT turn.
+            //  * quantized nodes, instanced scenes: the node block with its loads, then the triangle block with its own loads for
+            //    every lane that stands at a leaf now — a lane whose node step ended on a leaf tests the first triangle in the same turn.
+            // Either way a ray visits the same nodes and tests the same triangles in the same order.
+            constexpr bool kOneTrip = !QUANT && !INST;
+            const bool atLeaf = isTriLeaf(cur);
+            const char* nb = QUANT ? reinterpret_cast<const char*>(sc.nodesQ) : reinterpret_cast<const char*>(nodes4);
+            const char* tb = reinterpret_cast<const char*>(tris4);
+            const uint32_t nOff = cur * (QUANT ? 64u : 128u);
+            // float4 index inside a 128-byte node: 0..2 = min xyz, 3..5 = max xyz, 6 = children (QBVH.h:66-71 folded into offsets)
+            const uint32_t nx = idx > 0.0f ? 0u : 48u, ny = idy > 0.0f ? 16u : 64u, nz = idz > 0.0f ? 32u : 80u;
+            float4 s0, s1, s2;
+            if (kOneTrip) {
+                const char* row = (atLeaf ? tb : nb) + (atLeaf ? (cur & kLeafIndexMask) * 48u : nOff);
+                s0 = *reinterpret_cast<const float4*>(row + (atLeaf ? 0u : nx));
+                s1 = *reinterpret_cast<const float4*>(row + (atLeaf ? 16u : ny));
+                s2 = *reinterpret_cast<const float4*>(row + (atLeaf ? 32u : nz));
+            }
+            // dbg.triBlocks = triangle blocks executed: counted by the first active lane, summed over lanes at the end
+            const auto countTriBlock = [&](bool lanes) {
+                if (__ballot(lanes) && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)__ballot(true)) - 1u) ++dbg.triBlocks;
+            };
+            if (COUNT && kOneTrip) countTriBlock(atLeaf);
+            if (!atLeaf) {
                 if (COUNT) { const bool sh = (slot & kShadowBit) != 0; cnt.nodes[0] += sh ? 0u : 1u; cnt.nodes[1] += sh ? 1u : 0u; }
                 float4 nX, nY, nZ, fX, fY, fZ, ch;
                 if (QUANT) {
                     // 64-byte node, 8-bit child boxes (device_types.h QNodeQ): plane = fma(byte, scale, origin), rounded outwards by
                     // the host, so the boxes are supersets of the float boxes and the set of hits is unchanged
-                    const char* nb = reinterpret_cast<const char*>(sc.nodesQ);
-                    const uint32_t nOff = cur * 64u;
                     const float4 v0 = *reinterpret_cast<const float4*>(nb + nOff);
                     const float4 v1 = *reinterpret_cast<const float4*>(nb + (nOff + 16u));
                     const float4 v2 = *reinterpret_cast<const float4*>(nb + (nOff + 32u));
@@ -304,20 +332,17 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const IO& io, WsLd
 #undef WS_DEQ
                 }
                 else {
-                    // float4 index inside a 128-byte node: 0..2 = min xyz, 3..5 = max xyz, 6 = children (QBVH.h:66-71 folded into
-                    // offsets).  32-bit byte offsets from the (uniform) array base: SGPR-base + VGPR-offset addressing, one VALU op
-                    // per load instead of a 64-bit address computation (node array < 4 GiB: checked at upload)
-                    const int nx = idx > 0.0f ? 0 : 3, fx = 3 - nx;
-                    const int ny = idy > 0.0f ? 1 : 4, fy = 5 - ny;
-                    const int nz = idz > 0.0f ? 2 : 5, fz = 7 - nz;
-                    const char* nb = reinterpret_cast<const char*>(nodes4);
-                    const uint32_t nOff = cur * 128u;
-                    nX = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)nx * 16u));
-                    nY = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)ny * 16u));
-                    nZ = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)nz * 16u));
-                    fX = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)fx * 16u));
-                    fY = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)fy * 16u));
-                    fZ = *reinterpret_cast<const float4*>(nb + (nOff + (uint32_t)fz * 16u));
+                    // 32-bit byte offsets from the (uniform) array base: SGPR-base + VGPR-offset addressing, one VALU op per load
+                    // instead of a 64-bit address computation (node array < 4 GiB: checked at upload)
+                    if (kOneTrip) { nX = s0; nY = s1; nZ = s2; }
+                    else {
+                        nX = *reinterpret_cast<const float4*>(nb + (nOff + nx));
+                        nY = *reinterpret_cast<const float4*>(nb + (nOff + ny));
+                        nZ = *reinterpret_cast<const float4*>(nb + (nOff + nz));
+                    }
+                    fX = *reinterpret_cast<const float4*>(nb + (nOff + (48u - nx)));
+                    fY = *reinterpret_cast<const float4*>(nb + (nOff + (80u - ny)));
+                    fZ = *reinterpret_cast<const float4*>(nb + (nOff + (112u - nz)));
                     ch = *reinterpret_cast<const float4*>(nb + (nOff + 96u));
                 }
                 const uint32_t c[4] = {__float_as_uint(ch.x), __float_as_uint(ch.y), __float_as_uint(ch.z), __float_as_uint(ch.w)};
@@ -346,22 +371,29 @@ __device__ __forceinline__ void wsConsume(const DevScene& sc, const IO& io, WsLd
                 if (next != kInvalidChild) cur = next;
                 else wsPop(finished);
             }
-            // a lane whose node step ended on a leaf tests that leaf's first triangle in the same iteration
-            if (COUNT && __ballot(!finished && isTriLeaf(cur)) && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)__ballot(true)) - 1u)
-                ++dbg.triBlocks;      // counted by the first active lane; summed over lanes at the end
-            if (!finished && isTriLeaf(cur)) {
+            const bool triStep = kOneTrip ? atLeaf : !finished && isTriLeaf(cur);
+            if (COUNT && !kOneTrip) countTriBlock(triStep);
+            if (triStep) {
                 // ONE triangle of the leaf packet per step; the reference tests them in order (QBVH.h:322-327)
+                float4 a, b, c;
+                if (kOneTrip) { a = s0; b = s1; c = s2; }
+                else {
+                    const uint32_t tOff = (cur & kLeafIndexMask) * 48u;
+                    a = *reinterpret_cast<const float4*>(tb + tOff);
+                    b = *reinterpret_cast<const float4*>(tb + (tOff + 16u));
+                    c = *reinterpret_cast<const float4*>(tb + (tOff + 32u));
+                }
                 const uint32_t first = cur & kLeafIndexMask;
                 const uint32_t count = (cur >> kLeafCountShift) & 0xF;
-                const char* tb = reinterpret_cast<const char*>(tris4);
-                const uint32_t tOff = first * 48u;
-                const float4 a = *reinterpret_cast<const float4*>(tb + tOff);
-                const float4 b = *reinterpret_cast<const float4*>(tb + (tOff + 16u));
-                const float4 c = *reinterpret_cast<const float4*>(tb + (tOff + 32u));
                 const uint32_t triIdx = __float_as_uint(a.w);
                 const bool anyHit = (slot & kShadowBit) != 0;
                 if (COUNT) { cnt.tris[0] += anyHit ? 0u : 1u; cnt.tris[1] += anyHit ? 1u : 0u; }
                 const TriHit th = triangleTest(sc, a, b, c, V3(ox, oy, oz), V3(dx, dy, dz), tmin, tmax);
+                // One trip: the triangle test reads no fourth word of the record's last piece, the node block reads all four of its
+                // plane.  Left to itself the compiler loads three words for every lane and the fourth in the node block: an eighth
+                // request per node visit into the vector L1, the unit this kernel is bound by (measured: +12 % tag look-ups, the gain
+                // gone).  Naming the word here (no instruction) keeps the shared load whole.
+                if (kOneTrip) asm volatile("" :: "v"(c.w));
                 if (th.accept) {
                     if (anyHit) {
                         hitTri = triIdx;
